@@ -62,7 +62,12 @@ def parse():
     ap.add_argument('--no-step-profile', action='store_true', help='skip the in_scope_step block (a rocprofv3 kernel trace of one '
                     'optimisation iteration per configuration, taken in a child process)')
     ap.add_argument('--step-worker', default='', help=argparse.SUPPRESS)       # child mode of the in_scope_step block
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='after the timed steps, write what the last one computed '
+                    '(rank 0) as DIR/<name>.npy, float32, at most 64 MB in all')
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return a
 
 
 class RasterStep:
@@ -132,6 +137,31 @@ class RasterStep:
                                                        self.gv[k].data_ptr(), B, self.V, F, 3, self.stream), 'lasr_face_gather_backward_csr')
         torch.sum(self.gv, dim=1, out=self.mesh_grad)
         return self.mesh_grad
+
+
+# --dump-outputs: byte budget per array of the timed step.  An array over its budget is written as a fixed, seeded choice of
+# whole frames (dim 0, ascending), so the same arguments give the same sample in every run and every build.
+DUMP_BUDGET = {'soft_colors': 32 << 20, 'grad_faces': 12 << 20, 'grad_textures': 12 << 20, 'mesh_grad': 1 << 20}
+DUMP_SEED = 0
+
+
+def dump_outputs(job, out_dir):
+    """What the last timed step computed: the forward image, the backward's per-face gradients and the mesh gradient the step
+    returns (after the all-reduce for N > 1).  Returns {name: {'shape': full shape, 'frames': written rows or None (all)}}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'soft_colors': job.colors, 'grad_faces': job.gf, 'grad_textures': job.gt, 'mesh_grad': job.mesh_grad}
+    info = {}
+    for name, x in arrays.items():
+        rows = None
+        if x.numel() * 4 > DUMP_BUDGET[name]:
+            k = DUMP_BUDGET[name] // (x[0].numel() * 4)
+            if k < 1:
+                raise SystemExit('--dump-outputs: one frame of %s (%s) exceeds its %d-byte budget' % (name, tuple(x.shape), DUMP_BUDGET[name]))
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(x.shape[0], k, replace=False))
+            x = x[torch.from_numpy(rows).to(x.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), x.detach().float().cpu().numpy())
+        info[name] = {'shape': list(arrays[name].shape), 'frames': None if rows is None else rows.tolist()}
+    return info
 
 
 def collect_kernel_times(h, stream):
@@ -888,16 +918,10 @@ def main():
     local = int(os.environ.get('LOCAL_RANK', 0))
     if world != a.gpus and world > 1:
         raise SystemExit('--gpus %d but WORLD_SIZE=%d' % (a.gpus, world))
-    if not torch.cuda.is_available():
-        raise SystemExit('bench.py needs an MI355X (no HIP device visible); there is no CPU fallback')
-    backend = os.environ.get('LASR_BENCH_BACKEND', 'nccl')       # 'nccl' == RCCL on ROCm.  'gloo': functional check of the
-    if backend != 'nccl':                                        # multi-rank path with all ranks sharing GPU 0 (1-GPU box)
-        local = 0
-    elif a.gpus > torch.cuda.device_count():
-        raise SystemExit('--gpus %d but only %d HIP device(s) visible' % (a.gpus, torch.cuda.device_count()))
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
         # called as `python bench.py --gpus N`: launch one process per GPU ourselves (scripts/template.sh:26 does the same
-        # with torch.distributed.launch) and relay rank 0's JSON line
+        # with torch.distributed.launch) and relay rank 0's JSON line.  This parent never opens the GPU (each rank checks the
+        # devices), so N ranks sharing one GPU are N processes holding it, not N + 1.
         import socket
         import subprocess
         with socket.socket() as sk:
@@ -907,6 +931,13 @@ def main():
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(a.gpus),
                '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
         raise SystemExit(subprocess.call(cmd, env=env))
+    if not torch.cuda.is_available():
+        raise SystemExit('bench.py needs an MI355X (no HIP device visible); there is no CPU fallback')
+    backend = os.environ.get('LASR_BENCH_BACKEND', 'nccl')       # 'nccl' == RCCL on ROCm.  'gloo': functional check of the
+    if backend != 'nccl':                                        # multi-rank path with all ranks sharing GPU 0 (1-GPU box)
+        local = 0
+    elif a.gpus > torch.cuda.device_count():
+        raise SystemExit('--gpus %d but only %d HIP device(s) visible' % (a.gpus, torch.cuda.device_count()))
     torch.cuda.set_device(local)
     dev = torch.device('cuda', local)
     dist = None
@@ -949,6 +980,8 @@ def main():
         dist.all_gather_object(ids, (rank, torch.cuda.current_device(), os.getpid()))
         device_ids = [d for _, d, _ in sorted(ids)]
         assert len({p for _, _, p in ids}) == world          # one process per rank
+    # before the legs below, which run the same buffers again (the relaxed-math pass among them)
+    dumped = dump_outputs(job, a.dump_outputs) if a.dump_outputs and rank == 0 else None
 
     # ---- roofline leg: per-kernel HIP-event timing inside the library (separate pass) ----
     h = job.h
@@ -1001,6 +1034,8 @@ def main():
                          'raster_source_sha': raster_source_hash(),
                          'valu_issue': vi},
         }
+        if dumped is not None:
+            out['dump_outputs'] = {'dir': os.path.abspath(a.dump_outputs), 'seed': DUMP_SEED, 'arrays': dumped}
         if world == 1:
             # informational: the opt-in relaxed forward arithmetic (per-call flag LASR_SR_RELAXED_MATH, image within ~1e-5 of
             # the default path; `value` above is the default, reference-faithful arithmetic)

@@ -53,19 +53,21 @@ def test_bench_two_ranks_self_launch(cuda):
     assert 'ms' in av['one_all_reduce'] and av['buckets_25MB'].get('collectives_per_message', 3) >= 2
 
 
-def test_bench_eight_ranks_self_launch_on_one_gpu(cuda):
+def test_bench_four_ranks_self_launch_on_one_gpu(cuda):
     # The driver's 8-GPU line is `python bench.py --gpus 8`; no 8-GPU node is available to the builder, so the launcher
     # plumbing (self-launch, rendezvous, rank -> frames sharding, max-over-ranks timing, object gather, the data-parallel
-    # optimisation leg, rank 0's single JSON line) runs here with eight ranks sharing GPU 0 over gloo, at tiny sizes.
-    out = run_bench(['--gpus', '8', '--steps', '2', '--warmup', '1', '--frames', '4', '--lasr-iters', '2'],
+    # optimisation leg, rank 0's single JSON line) runs here with more than two ranks sharing GPU 0 over gloo, at tiny sizes.
+    # Four ranks, not eight: with this test's own process that is five processes holding the one GPU open (the self-launching
+    # parent does not open it); a shared GPU is not given more than six.
+    out = run_bench(['--gpus', '4', '--steps', '2', '--warmup', '1', '--frames', '4', '--lasr-iters', '2'],
                     {'LASR_BENCH_BACKEND': 'gloo'}, timeout=1500)
-    assert out['n_gpus'] == 8 and out['world_size'] == 8 and len(out['rank_device_ids']) == 8 and out['backend'] == 'gloo'
-    assert abs(out['value'] - 8 * 4 * 2 / (out['ms_per_step'] * 2e-3)) <= 1e-6 * out['value']
-    assert out['config']['parallelism'].startswith('dp8')
+    assert out['n_gpus'] == 4 and out['world_size'] == 4 and len(out['rank_device_ids']) == 4 and out['backend'] == 'gloo'
+    assert abs(out['value'] - 4 * 4 * 2 / (out['ms_per_step'] * 2e-3)) <= 1e-6 * out['value']
+    assert out['config']['parallelism'].startswith('dp4')
     dp = out['optimize_py_dp']
-    assert dp['world_size'] == 8 and dp['overlap']['pairs_per_s'] > 0 and dp['no_overlap']['pairs_per_s'] > 0
+    assert dp['world_size'] == 4 and dp['overlap']['pairs_per_s'] > 0 and dp['no_overlap']['pairs_per_s'] > 0
     av = dp['allreduce_variants']
-    assert av['world_size'] == 8 and set(av) >= {'one_all_reduce', 'reduce_scatter_all_gather', 'buckets_25MB', 'env', 'message_bytes'}
+    assert av['world_size'] == 4 and set(av) >= {'one_all_reduce', 'reduce_scatter_all_gather', 'buckets_25MB', 'env', 'message_bytes'}
     assert 'ms' in av['one_all_reduce']
 
 
@@ -79,6 +81,23 @@ def test_bench_single_gpu_line_has_every_block(cuda):
     assert c['kind'] == 'port' and c['cores'] >= 1 and c['value'] > 0 and c['one_thread_frames_per_s'] > 0
     assert l['mfma_instruction'] == 'v_mfma_f32_16x16x4_f32' and set(l['sizes']) == {'S0', 'dog15', 'batch256'}
     assert all(v['us_per_call'] > 0 and v['mfma_instructions'] > 0 for v in l['sizes'].values())
+
+
+def test_bench_dumps_the_same_outputs_from_run_to_run(cuda, tmp_path):
+    # --dump-outputs: the last timed step's image and gradients, float32; with the same arguments the same inputs, and the
+    # kernels of the step use no atomics, so two runs write the same bits
+    args = ['--steps', '2', '--warmup', '1', '--frames', '64', '--lasr-iters', '0', '--no-cpu-baseline', '--no-lbs', '--no-sweep']
+    outs = [run_bench(args + ['--dump-outputs', str(tmp_path / d)]) for d in ('a', 'b')]
+    info = outs[0]['dump_outputs']['arrays']
+    assert outs[1]['dump_outputs']['arrays'] == info and set(info) == {'soft_colors', 'grad_faces', 'grad_textures', 'mesh_grad'}
+    assert info['soft_colors']['shape'] == [64, 4, 256, 256] and len(info['soft_colors']['frames']) == 32
+    assert info['mesh_grad'] == {'shape': [2, 1212, 3], 'frames': None}
+    for name in info:
+        a, b = (np.load(str(tmp_path / d / (name + '.npy'))) for d in ('a', 'b'))
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0, name
+        np.testing.assert_array_equal(a, b, err_msg=name)
+    img = np.load(str(tmp_path / 'a' / 'soft_colors.npy'))
+    assert 0 <= img.min() < img.max() <= 1
 
 
 def test_rccl_executes_on_this_box(cuda):

@@ -312,11 +312,10 @@ def test_obj_material_parsing(tmp_path):
         obj_io.parse_obj_materials(os.path.join(str(tmp_path), 'bare.obj'))
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/database/misc/spot/spot_triangulated.obj'), reason='reference data not present')
 def test_obj_material_parsing_on_the_reference_model():
-    # the model scripts/render_syn.py:71 of the reference renders (read where it lies; not copied, not needed on the GPU box)
+    # the model scripts/render_syn.py:71 of the reference renders (its data files, stored under tests/golden/spot/)
     from lasr_amd.soft_renderer.functional import obj_io
-    path = '/root/reference/database/misc/spot/spot_triangulated.obj'
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'spot', 'spot_triangulated.obj')
     v, f = obj_io.load_obj(path, device='cpu')
     uv, mats, colors, files = obj_io.parse_obj_materials(path)
     assert v.shape == (2930, 3) and f.shape == (5856, 3) and uv.shape == (5856, 3, 2)
