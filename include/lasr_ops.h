@@ -348,6 +348,35 @@ int lasr_load_textures(const float* image, const float* faces_uv, const int* is_
                        int W, void* hip_stream);
 
 /*
+ * Per-face surface textures -> texture atlas, replaces `soft_renderer.cuda.create_texture_image`
+ * (third_party/softras/soft_renderer/cuda/create_texture_image_cuda.cpp, kernel create_texture_image_cuda_kernel.cu:10-70; called
+ * from functional/save_obj.py:9-37).  textures [F,R_in*R_in,3]; faces_uv [F,3,2] each face's triangle in pixel units of the atlas;
+ * image [tile_height*R_out, tile_width*R_out, 3] with tile_width = floor(sqrt(F-1)) + 1, tile_height = (F-1) / tile_width + 1.
+ * Pixel (x, y) belongs to face x / R_out + (y / R_out) * tile_width and copies the texel its barycentric coordinates pick (the
+ * reference's arithmetic in its order, eps as the reference's float argument); every pixel is written, 1 past the last face.
+ */
+int lasr_create_texture_image(const float* faces_uv, const float* textures, float* image, int F, int R_in, int R_out, float eps,
+                              void* hip_stream);
+int lasr_create_texture_image_f64(const double* faces_uv, const double* textures, double* image, int F, int R_in, int R_out,
+                                  float eps, void* hip_stream);
+
+/*
+ * Mesh voxelisation, replaces functional/voxelization.py:41-57 (`srf.voxelization(faces, size, normalize)` over the
+ * `soft_renderer.cuda.voxelization` kernels, cuda/voxelization_cuda_kernel.cu:30-190).  faces [B,F,3,3] already scaled to voxel
+ * units; voxels [B,S,S,S] int32 (overwritten), indexed by the face-vertex coordinates 0, 1, 2: 1 = surface or enclosed.  The
+ * surface is the reference's column scans along the three axes and the vertex voxels (one launch, bit-packed); the fill marks
+ * every empty voxel not 6-connected through empty voxels to the grid's boundary (one launch, one workgroup per mesh, no host
+ * synchronisation).  sweeps [B] (may be NULL) receives the number of fill sweeps of each mesh.
+ * S is limited to LASR_VOXEL_MAX_SIZE (64 MB of output per mesh; the reference has no limit).
+ */
+#define LASR_VOXEL_MAX_SIZE 256
+size_t lasr_voxelize_workspace_bytes(int B, int S);     /* 0 for invalid sizes */
+int lasr_voxelize(const float* faces, int* voxels, int* sweeps, void* workspace, size_t workspace_bytes, int B, int F, int S,
+                  void* hip_stream);
+int lasr_voxelize_f64(const double* faces, int* voxels, int* sweeps, void* workspace, size_t workspace_bytes, int B, int F, int S,
+                      void* hip_stream);
+
+/*
  * ---- small-tensor glue of LASR.forward as single kernels (lasr_amd/csrc/glue.hip) -----------------------------------
  *
  * Rotation distance, third_party/ext_utils/util_rot.py:27-37 (called at nnutils/mesh_net.py:508 / :516): m1, m2 [n,3,3]

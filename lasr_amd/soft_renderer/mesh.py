@@ -130,3 +130,9 @@ class Mesh(object):
         srf.save_obj(filename_obj, self.vertices[0], self.faces[0],
                      textures=self.textures[0] if save_texture else None,
                      texture_res=texture_res_out, texture_type=self.texture_type)
+
+    def voxelize(self, voxel_size=32):
+        """mesh.py:177-179: the face vertices of every mesh scaled by S/(S-1) and shifted by 0.5 -> voxelization(..., S, False),
+        [B,S,S,S] int32."""
+        face_vertices_norm = self.face_vertices * voxel_size / (voxel_size - 1) + 0.5
+        return srf.voxelization(face_vertices_norm, voxel_size, False)
