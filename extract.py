@@ -8,8 +8,9 @@ which also renders visualisations with pyrender / matplotlib -- not reproduced).
 For frame i of the sequence it writes <checkpoint_dir>/<name>/pred<i>.obj (articulated shape in camera space, the frame
 the reference's scripts/eval_mesh.py evaluates: eval_mesh.py:106-109) and cam<i>.txt in the layout of the reference's
 extract.py:123-130: np.savetxt of the 4x4 array [[R | T] (3x4, root body-to-camera transform); [fx, fy, ppx, ppy]] with
-the intrinsics expressed in the uncropped image (nnutils/predictor.py:188-189).  The reference additionally writes bone /
-skinning-Gaussian .ply files and novel-view renders for its visualisation scripts; those are not produced.  The flags are optimize.py's; the model is rebuilt as that stage built it and the checkpoint
+the intrinsics expressed in the uncropped image (nnutils/predictor.py:188-189).  For render_vis.py it also writes pred<i>.ply (the
+same mesh with its per-vertex colours, fusion.meshwrite's layout) and, with n_bones > 1, gauss<i>.ply (the bones' Gaussian
+ellipsoids in camera space, reference extract.py:113-121); the reference's novel-view renders are not reproduced.  The flags are optimize.py's; the model is rebuilt as that stage built it and the checkpoint
 is loaded as is (no re-meshing, no hypothesis selection beyond picking the best one for the export).
 """
 import os
@@ -21,6 +22,8 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 import optimize                                             # noqa: E402
+from lasr_amd import vis                                     # noqa: E402
+from lasr_amd.ext_utils.ply import write_ply                 # noqa: E402
 from lasr_amd.nnutils import train_utils                    # noqa: E402
 from lasr_amd.soft_renderer.functional import save_obj       # noqa: E402
 
@@ -43,6 +46,12 @@ def export(tr, out_dir):
             ids = bi['frameid'].view(-1, 2).t().reshape(-1)  # undo the pair interleave
             verts = m.verts_cam.view(len(ids), H, -1, 3)[:, best]
             cam = {k: v.view(len(ids), H, *v.shape[1:])[:, best].cpu().numpy() for k, v in m.cam_export.items()}
+            tex = m.get_mean_shape(len(ids) // 2)[1].view(len(ids), H, -1, 3)[0, best]   # the vertex colours the forward renders with
+            K = tr.opts.n_bones
+            if K > 1:
+                Rmat, Tmat = m._cam_src[0], m._cam_src[1]
+                Rmat, Tmat = Rmat.view(len(ids), H, K, 3, 3)[:, best], Tmat.view(len(ids), H, K, 3)[:, best]
+                ctl = [p.view(H, K - 1, -1)[best] for p in (m.ctl_ts, m.ctl_rs, m.log_ctl)]
             for k, fid in enumerate(int(v) for v in ids.tolist()):
                 if fid in done:
                     continue
@@ -51,6 +60,11 @@ def export(tr, out_dir):
                 rtk = np.concatenate([np.concatenate([cam['R'][k], cam['T'][k][:, None]], 1),
                                       np.concatenate([cam['focal'][k], cam['pp'][k]])[None]], 0)
                 np.savetxt(os.path.join(out_dir, 'cam%d.txt' % fid), rtk)
+                write_ply(os.path.join(out_dir, 'pred%d.ply' % fid), verts[k].cpu().numpy(), m.faces.cpu().numpy(),
+                          colors=255 * tex.cpu().numpy())
+                if K > 1:
+                    gv, gf, gc = vis.gaussian_spheres(*ctl, Rmat[k], Tmat[k])
+                    write_ply(os.path.join(out_dir, 'gauss%d.ply' % fid), gv.cpu().numpy(), gf, colors=gc)
                 done[fid] = path
             if len(done) >= n_frames:
                 break

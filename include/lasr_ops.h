@@ -377,6 +377,42 @@ int lasr_voxelize_f64(const double* faces, int* voxels, int* sweeps, void* works
                       void* hip_stream);
 
 /*
+ * Shading and compositing pass of render_vis.py (lasr_amd/csrc/vis.hip; the reference renders with pyrender / OpenGL,
+ * render_vis.py:226-289).  N frames share one face list of F faces over V vertices per frame, all in camera space (OpenCV axes:
+ * x right, y down, z forward).  Faces [0, F0) form the opaque layer, faces [F0, F) the translucent surface layer.
+ *   vert_rec  [N,V,12]  position x y z, NDC x | normal x y z, NDC y | colour r g b (0-1), 0  (the NDC of the camera raster)
+ *   faces     [F,4]     vertex indices, 4th unused; an index outside [0, V) leaves its pixels uncovered
+ *   face_rec  [N,F,8]   unit face normal, 0 | light-space plane a b c, 0: depth w = a u + b v + c along light_d at (u, v)
+ *   raster0   [N,2,IS,IS]  hard-mode aggrs_info of the opaque layer (lasr_sr_forward_bg, func_id_rgb = func_id_alpha = 0):
+ *                          plane 1 holds a face index in [0, F0) or -1
+ *   raster1   [N,2,IS,IS]  the same for the surface layer (index + F0 is the face), or NULL for one layer (then F0 == F)
+ *   shadow    [N,2,S,S]    hard-mode raster of all F faces from the light, orthographic: NDC = ((u, v) - (cu, cv)) / half
+ *   shadow_xf [N,4]        cu, cv, 1 / half, 0 per frame
+ *   frames    [N,H,W]      packed RGBA8 input frames (r in the low byte), read when params->overlay, else may be NULL
+ *   out       [N,H,W]      packed RGBA8 (alpha 255): the top-left H x W of the square IS x IS render
+ * Per pixel: barycentrics of the pixel centre against the face's NDC vertices (the rasteriser's convention), perspective-correct
+ * position / normal / colour, two-sided normal (flipped toward the camera), c = clamp(0.6 colour (k_ambient + k_diffuse
+ * max(0, n.L) s), 0, 1) with L = -light_d and s the 3x3-PCF shadow fraction (per tap, at the centre of its texel: the stored
+ * face's plane depth against the receiver's face plane extended there); the surface layer, where it is nearer than the
+ * opaque one, is blended over it with surface_alpha; background where no face; overlay: round(0.5 render + 0.5 frame).
+ * Checked on the host before any launch: sizes, layer split and pointers (LASR_E_BADARG).  The contents of device buffers are
+ * not read on the host: the kernel treats a map entry outside the layer's [0, F) (-1, too large, NaN) and a face with a vertex
+ * index outside [0, V) as no face, so no gather leaves its buffer (lasr_amd/vis.py also validates `faces` before the call).
+ */
+typedef struct lasr_vis_params {
+    float light_u[3], light_v[3], light_d[3];   /* orthonormal light frame, light_d = direction the light travels */
+    float k_ambient, k_diffuse, surface_alpha;
+    float shadow_bias;                          /* light-space depth margin of the shadow test */
+    float background[3];                        /* 0-1 */
+    int smooth;                                 /* 1: interpolated vertex normals, 0: face normals */
+    int overlay;                                /* 1: blend with `frames` */
+} lasr_vis_params;
+#define LASR_VIS_MAX_SIZE 16384
+int lasr_vis_shade(const float* vert_rec, const int* faces, const float* face_rec, const float* raster0, const float* raster1,
+                   const float* shadow, const float* shadow_xf, const unsigned* frames, unsigned* out, int N, int V, int F, int F0,
+                   int IS, int S, int H, int W, const lasr_vis_params* params, void* hip_stream);
+
+/*
  * ---- small-tensor glue of LASR.forward as single kernels (lasr_amd/csrc/glue.hip) -----------------------------------
  *
  * Rotation distance, third_party/ext_utils/util_rot.py:27-37 (called at nnutils/mesh_net.py:508 / :516): m1, m2 [n,3,3]

@@ -79,6 +79,8 @@ SIGNATURES = {
     'lasr_voxelize_workspace_bytes': (_sz, [_i, _i]),
     'lasr_voxelize': (_i, [_p, _p, _p, _p, _sz, _i, _i, _i, _p]),
     'lasr_voxelize_f64': (_i, [_p, _p, _p, _p, _sz, _i, _i, _i, _p]),
+    # lasr_amd/csrc/vis.hip
+    'lasr_vis_shade': (_i, [_p] * 9 + [_i] * 8 + [_p, _p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -128,7 +130,7 @@ SIGNATURES = {
     'lasr_prof_collect': (_i, [_p, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong)]),
 }
 
-ABI_VERSION = 5                                     # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
+ABI_VERSION = 6                                     # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
 # flags of the *_ex entry points (include/lasr_sr.h)
 SR_DEFAULT_FLAGS, SR_RELAXED_MATH, SR_SEGMENTED, SR_RECORDS_VALID, SR_GRADS_OVERWRITE = -1, 1, 2, 4, 8
 SR_PAIR_ONE_TEAM, SR_PAIR_TWO_TEAMS = 16, 32          # forward: teams of four waves per tile of the pair-walk kernel (default: by launch size)
@@ -141,6 +143,12 @@ class SrOptions(ctypes.Structure):
     heaviest-first tile order; a negative field = default."""
     _fields_ = [('coop8_max_tiles', ctypes.c_longlong), ('coop_max_tiles', ctypes.c_longlong), ('choose_max_tiles', ctypes.c_longlong),
                 ('order_max_tiles', ctypes.c_longlong), ('pair_min_tiles', ctypes.c_longlong)]
+
+
+class VisParams(ctypes.Structure):
+    """lasr_vis_params (include/lasr_ops.h): light frame, shading constants and output options of lasr_vis_shade."""
+    _fields_ = [('light_u', _f * 3), ('light_v', _f * 3), ('light_d', _f * 3), ('k_ambient', _f), ('k_diffuse', _f),
+                ('surface_alpha', _f), ('shadow_bias', _f), ('background', _f * 3), ('smooth', _i), ('overlay', _i)]
 
 
 _lib = None
