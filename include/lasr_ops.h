@@ -413,6 +413,26 @@ int lasr_vis_shade(const float* vert_rec, const int* faces, const float* face_re
                    int IS, int S, int H, int W, const lasr_vis_params* params, void* hip_stream);
 
 /*
+ * Keypoint transfer of scripts/eval_badja.py (lasr_amd/csrc/keypoints.hip; reference: scripts/eval_badja.py:225-242), for B
+ * pairs (reference frame, target frame):
+ *   colors [B,4,S,S]  the hard-mode raster of the reference frame's geometry with the target's projected vertices as vertex
+ *                     colours (render_flow_soft_3), read in place; NULL: the zero flow (every pixel invalid, pred = kp)
+ *   kp     [B,J,2]    keypoints (row, col) in pixels of the H x W crop (the top-left H x W of the S x S raster)
+ *   idx    [B,J]      int64 out: flat index r * W + c of the chosen pixel (also the call's scratch: packed search keys)
+ *   pred   [B,J,2]    fp32 out: (row + flow_y * H / 2, col + flow_x * W / 2), the reference's scaling
+ * Per pixel, in fp32 and the reference's operation order: flow = 0 where colour channel 2 < 1e-9, else colour.xy - grid with
+ * grid = (p * 2) * (1 / (S - 1)) - 1 (p = column for x, row for y); invalid where sqrt(fx * fx + fy * fy) < 1e-6; per keypoint
+ * idx = argmin over the crop of (invalid * 1e6 + (row - r)^2) + (col - c)^2, the first index on ties (torch's argmin).  Exact
+ * for integer keypoints in crops up to 1920 x 1080 (every key below 2^24).  A NaN keypoint gets idx = -1 and a NaN prediction.
+ * Checked on the host before any launch: sizes (2 <= S <= LASR_KP_MAX_SIZE, H, W <= S, 1 <= J <= LASR_KP_MAX_JOINTS) and
+ * pointers (LASR_E_BADARG).  One memset and two launches on hip_stream; no host synchronisation.
+ */
+#define LASR_KP_MAX_JOINTS 64
+#define LASR_KP_MAX_SIZE 16384
+int lasr_kp_transfer(const float* colors, const float* kp, long long* idx, float* pred, int B, int J, int S, int H, int W,
+                     void* hip_stream);
+
+/*
  * ---- small-tensor glue of LASR.forward as single kernels (lasr_amd/csrc/glue.hip) -----------------------------------
  *
  * Rotation distance, third_party/ext_utils/util_rot.py:27-37 (called at nnutils/mesh_net.py:508 / :516): m1, m2 [n,3,3]

@@ -55,8 +55,9 @@ extern "C" {
  *      launches from that many 8x8 tiles up take the pair-walk forward kernel.  New (no existing signature changes): lasr_pose_chain_*,
  *      lasr_render_tables_forward_imgs; forward flag bits LASR_SR_PAIR_ONE_TEAM / LASR_SR_PAIR_TWO_TEAMS (formerly rejected).
  *   5  export side (no existing signature changes): lasr_create_texture_image*, lasr_voxelize*, lasr_voxelize_workspace_bytes.
- *   6  visualisation (no existing signature changes): lasr_vis_shade and its parameter block lasr_vis_params. */
-#define LASR_ABI_VERSION 6
+ *   6  visualisation (no existing signature changes): lasr_vis_shade and its parameter block lasr_vis_params.
+ *   7  evaluation (no existing signature changes): lasr_kp_transfer, the keypoint transfer of scripts/eval_badja.py. */
+#define LASR_ABI_VERSION 7
 int         lasr_abi_version(void);
 const char* lasr_strerror(int code);
 int         lasr_last_hip_error(void);      /* hipError_t of the most recent LASR_E_LAUNCH on this thread */

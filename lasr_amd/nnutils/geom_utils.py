@@ -185,3 +185,36 @@ def orthographic_cam(verts, pp, fl):
     x = pp[:, 0:1] + verts[:, :, 0] * fl
     y = pp[:, 1:2] + verts[:, :, 1] * fl
     return torch.cat([x[..., None], y[..., None], verts[:, :, 2:]], -1)
+
+
+def render_flow_colors(renderer_soft, verts, verts_target, faces):
+    """The raster under render_flow_soft_3: verts [B,V,3+] (NDC x, y, depth) moved by the renderer's eye and flipped in y as
+    geom_utils.py:77-78 does, rendered with verts_target[..., :3] as vertex colours -> [B,4,S,S] (x, y, depth of the target
+    vertices interpolated, alpha).  scripts/eval_badja.py hands it to nnutils.keypoints.kp_transfer without the background fill."""
+    _lib.need_cuda(verts, verts_target, faces)
+    from .. import soft_renderer as sr
+    offset = torch.tensor(renderer_soft.transform.transformer._eye, dtype=torch.float32, device=verts.device)[None, None]
+    verts_pre = verts[:, :, :3] + offset
+    verts_pre[:, :, 1] = -1 * verts_pre[:, :, 1]
+    return renderer_soft.render_mesh(sr.Mesh(verts_pre, faces, textures=verts_target[:, :, :3], texture_type='vertex'))
+
+
+def render_flow_soft_3(renderer_soft, verts, verts_target, faces):
+    """Flow of frame `verts` towards `verts_target` (same topology) in NDC units of the S x S render (geom_utils.py:73-95):
+    -> (flow_fw [B,S,S,2], bgmask [B,S,S] bool, fgmask [B,S,S]).  Background is where the interpolated depth (channel 2) is
+    below 1e-9; there the colour is set to 10 before the pixel grid p * 2 / (S - 1) - 1 is subtracted, as the reference does.
+    fgmask is the alpha plane as a view of the same colours, so, as in the reference, the background fill leaves 10 in it there
+    (1 on covered pixels).  Device tensors only (TypeError for CPU tensors)."""
+    import numpy as np
+    px = render_flow_colors(renderer_soft, verts, verts_target, faces).clone()
+    fgmask = px[:, -1]
+    px = px.permute(0, 2, 3, 1)
+    bgmask = px[:, :, :, 2] < 1e-9
+    px[bgmask] = 10
+    grid = torch.tensor(np.stack(np.meshgrid(range(bgmask.shape[2]), range(bgmask.shape[1]))), dtype=torch.float32,
+                        device=px.device)
+    grid[0] = grid[0] * 2 / (bgmask.shape[2] - 1) - 1
+    grid[1] = grid[1] * 2 / (bgmask.shape[1] - 1) - 1
+    grid = grid.permute(1, 2, 0)[None]
+    flow_fw = px[:, :, :, :2] - grid
+    return flow_fw, bgmask, fgmask
