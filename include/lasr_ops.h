@@ -433,6 +433,45 @@ int lasr_kp_transfer(const float* colors, const float* kp, long long* idx, float
                      void* hip_stream);
 
 /*
+ * Watertight re-meshing (lasr_amd/csrc/manifold.hip), in place of the external Manifold binary the reference runs as
+ * `manifold in.obj out.obj 10000` (scripts/eval_mesh.py:100-105, render_vis.py:98, nnutils/train_utils.py:422).  The caller
+ * voxelises the input with lasr_voxelize into voxels [S,S,S] int32 (index c0, c1, c2; voxel i covers [i, i+1)), then:
+ *   repair   makes the solid well-composed: a Jacobi sweep turns every empty voxel of a critical configuration solid -- a 2x2
+ *            square of an axis plane whose diagonals hold opposite values, or a 2x2x2 block whose only voxels of one value are an
+ *            antipodal pair, in either colour -- until a sweep changes nothing; then export.hip's fill sweep fills the pockets the
+ *            repair closed.  voxels is rewritten in place (1 = solid).  info[0] = sweeps of the repair (the last one changes
+ *            nothing); info[1] = sweeps of the fill.  A solid voxel on the grid's outer layer is refused without a host
+ *            synchronisation: info[0] = -1 (LASR_E_BADARG of the caller, which reads info with the counts) and the solid is only
+ *            refilled.
+ *   count    counts[0] = solid voxels with an empty 6-neighbour, counts[1] = V vertices, counts[2] = F triangles of the boundary.
+ *            The per-row vertex masks and offsets stay in the workspace for extract (same voxels, same workspace, no call between).
+ *   extract  verts [V,3] fp32 lattice coordinates, faces [F,3] int64.  One quad per solid voxel face whose 6-neighbour is empty,
+ *            counter-clockwise seen from the empty side, split along its (0,0)-(1,1) diagonal of the in-plane axes
+ *            (a+1, a+2) mod 3; one vertex per lattice point whose eight voxels are not all equal.  Orders (deterministic, no
+ *            atomics): vertices by lattice linear index (p0 * (S+1) + p1) * (S+1) + p2; triangles by voxel linear index
+ *            (c0 * S + c1) * S + c2, then direction -c0, +c0, -c1, +c1, -c2, +c2, then the two triangles of the quad.
+ *            V and F are the counts read back from count: writes past them are dropped.
+ *   project  verts[v] = the closest point to lattice[v] on input face arg_face[v] (lasr_point_mesh_forward's arg_point; the
+ *            closest point as point_mesh's point_triangle computes it).  An out-of-range face leaves the lattice point.
+ *   guard    rounds of: flag every face whose normal has a non-positive dot product with its lattice normal, or whose area is
+ *            below min_area; move every vertex of a flagged face back to lattice[]; until no face is flagged.  rounds[0] = the
+ *            rounds that moved vertices back.  flags [V] int32 scratch.  One workgroup; no host synchronisation.
+ * Sizes and pointers are checked on the host before any launch: LASR_MANIFOLD_MIN_SIZE <= S <= LASR_MANIFOLD_MAX_SIZE
+ * (LASR_E_BADARG), workspace >= lasr_manifold_workspace_bytes(S) (LASR_E_WORKSPACE).  No call synchronises the host.
+ */
+#define LASR_MANIFOLD_MIN_SIZE 4
+#define LASR_MANIFOLD_MAX_SIZE 256
+size_t lasr_manifold_workspace_bytes(int S);      /* 0 for invalid sizes */
+int lasr_manifold_repair(int* voxels, int* info, void* workspace, size_t workspace_bytes, int S, void* hip_stream);
+int lasr_manifold_count(const int* voxels, int* counts, void* workspace, size_t workspace_bytes, int S, void* hip_stream);
+int lasr_manifold_extract(const int* voxels, float* verts, long long* faces, int V, int F, void* workspace, size_t workspace_bytes,
+                          int S, void* hip_stream);
+int lasr_manifold_project(const float* lattice, const float* in_verts, const long long* in_faces, const int* arg_face, float* verts,
+                          int V, int Vin, int Fin, void* hip_stream);
+int lasr_manifold_guard(const float* lattice, float* verts, const long long* faces, int* flags, int* rounds, int V, int F,
+                        float min_area, void* hip_stream);
+
+/*
  * ---- small-tensor glue of LASR.forward as single kernels (lasr_amd/csrc/glue.hip) -----------------------------------
  *
  * Rotation distance, third_party/ext_utils/util_rot.py:27-37 (called at nnutils/mesh_net.py:508 / :516): m1, m2 [n,3,3]

@@ -28,7 +28,8 @@ const char* const kKernelNames[K_NUM_KERNELS] = {
     "geodesic_forward_kernel", "geodesic_backward_kernel", "weighted_means_kernel", "intrinsics_kernel", "bone_fixup_kernel", "chamfer_kernel", "mean_shape_kernel", "obs_pair_kernel", "tail_kernel", "fill_planes_kernel", "gather_rows_kernel", "render_tables_forward_kernel", "render_tables_backward_kernel", "raster_inputs_kernel", "sr_order_kernel",
     "render_tables_flow_kernel", "raster_faces_kernel", "mesh_reg_kernel", "render_tables_fold_kernel", "lbs_backward_fold_kernel", "project_points_kernel", "pose_chain_kernel",
     "texture_atlas_kernel", "voxel_surface_kernel", "voxel_fill_kernel", "vis_shade_kernel", "kp_transfer_kernel",
-    "kp_sample_kernel"};
+    "kp_sample_kernel", "mf_pack_kernel", "mf_repair_kernel", "mf_count_kernel", "mf_scan_kernel", "mf_extract_kernel",
+    "mf_project_kernel", "mf_guard_kernel"};
 }  // namespace
 
 int lasr_launch_ok()

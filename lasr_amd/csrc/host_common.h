@@ -16,6 +16,7 @@ enum LasrKernelId {
     K_LOAD_TEXTURES, K_GEODESIC_FORWARD, K_GEODESIC_BACKWARD, K_WEIGHTED_MEANS, K_INTRINSICS, K_BONE_FIXUP, K_CHAMFER, K_MEAN_SHAPE, K_OBS_PAIR, K_TAIL, K_FILL_PLANES, K_GATHER_ROWS, K_RENDER_TABLES_FORWARD, K_RENDER_TABLES_BACKWARD, K_RASTER_INPUTS, K_SR_ORDER,
     K_RENDER_TABLES_FLOW, K_RASTER_FACES, K_MESH_REG, K_RENDER_TABLES_FOLD, K_LBS_BACKWARD_FOLD, K_PROJECT_POINTS, K_POSE_CHAIN,
     K_TEXTURE_ATLAS, K_VOXEL_SURFACE, K_VOXEL_FILL, K_VIS_SHADE, K_KP_TRANSFER, K_KP_SAMPLE,
+    K_MF_PACK, K_MF_REPAIR, K_MF_COUNT, K_MF_SCAN, K_MF_EXTRACT, K_MF_PROJECT, K_MF_GUARD,
     K_NUM_KERNELS
 };
 

@@ -11,7 +11,9 @@ pytorch3d.loss.chamfer_distance) of two fresh samples is reported, together with
 mean_x(1 - |cos(n_x, n_nn(x))|) + mean_y(1 - |cos(n_y, n_nn(y))|) over the sampled faces' normals; the script prints 1 minus
 it as the normal consistency).  pytorch3d / trimesh are not available here: area sampling with face normals, Kabsch ICP,
 the Chamfer sum and the normal term are written out; the nearest-neighbour searches run on lasr_nearest_point.
-(The reference also re-meshes the prediction with the external Manifold binary and renders error images: not done.)
+--remesh RESOLUTION > 0 re-meshes every prediction watertight first, as the reference does with the external Manifold binary
+for LASR's predictions (:100-105, `manifold in.obj out.obj 10000`): lasr_amd/nnutils/manifold.py:watertight on the GPU.  The
+default 0 scores the predictions as they are.  (The reference's error images are not rendered.)
 """
 import argparse
 import glob
@@ -23,6 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lasr_amd.nnutils import fused_ops                     # noqa: E402
+from lasr_amd.nnutils.manifold import watertight           # noqa: E402
 from lasr_amd.soft_renderer.functional import load_obj      # noqa: E402
 
 
@@ -107,7 +110,11 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description='mesh evaluation')
     ap.add_argument('--testdir', required=True)
     ap.add_argument('--gtdir', required=True)
+    ap.add_argument('--remesh', type=int, default=0, metavar='RESOLUTION',
+                    help='re-mesh each prediction watertight at this resolution first (the reference: 10000); 0: as it is')
     args = ap.parse_args(argv)
+    if args.remesh < 0:
+        ap.error('--remesh takes a non-negative resolution')
     dev = torch.device('cuda', 0)
     gts = sorted(glob.glob('%s/*.obj' % args.gtdir))
     preds = sorted(glob.glob('%s/pred*.obj' % args.testdir)) or sorted(glob.glob('%s/*.obj' % args.testdir))
@@ -115,7 +122,10 @@ def main(argv=None):
     cds, ncs = [], []
     for i, (p, g) in enumerate(zip(preds, gts)):
         pm, gm = load_obj(p, device=dev), load_obj(g, device=dev)
-        cd, nc = evaluate_pair((pm[0].float(), pm[1].long()), (gm[0].float(), gm[1].long()), with_normals=True)
+        pm = (pm[0].float(), pm[1].long())
+        if args.remesh > 0:
+            pm = watertight(pm[0], pm[1], args.remesh)
+        cd, nc = evaluate_pair(pm, (gm[0].float(), gm[1].long()), with_normals=True)
         cds.append(cd); ncs.append(nc)
         print('%04d: %.2f, %.2f' % (i, cd, nc))                       # the reference's line (:197): Chamfer, normal consistency
     print('ALL: %.2f, %.2f' % (np.mean(cds), np.mean(ncs)))
