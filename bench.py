@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- soft-rasteriser forward+backward throughput on MI355X (BASELINE.json metric #1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B]      # N > 1: re-launches itself, one process per GPU
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--full]   # N > 1: re-launches itself, one process per GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W          # the same thing, launched explicitly
 (the reference launches one process per GPU from its script line as well: scripts/template.sh:26, optimize.py:42-47)
@@ -18,9 +18,13 @@ frames; for N > 1 the [2,V,3] mesh
 gradient is then all-reduced over RCCL (frames are sharded data-parallel, weak scaling).
 Nothing inside the timed region touches the CPU oracle.
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed inside the
-library on the launch stream) and, at N=1, `cpu_baseline` (the oracle, OpenMP over host cores,
-on a bounded sample of the same workload).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs
+and prints the headline (`value`, `ms_per_step`, the configuration) -- nothing else.  With --full
+the line also carries `roofline` (dominant kernel, HIP-event timed inside the library on the launch
+stream, a pass of its own) and, at N=1, the relaxed-math forward, the launch-size sweep and other
+workload points, `cpu_baseline` (the oracle, OpenMP over host cores, on a bounded sample of the same
+workload), the LBS block, optimize.py-style it/s and the in-scope kernel time of that step; for
+N > 1, `optimize_py_dp`.  The --no-* / --lasr-iters options below trim what --full runs.
 """
 import argparse
 import ctypes
@@ -53,6 +57,9 @@ def parse():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--frames', type=int, default=256, help='frames per GPU per step (SURVEY 8d batches: 1/16/64/256)')
     ap.add_argument('--image-size', type=int, default=256, help='256 = the headline metric; 512 = BASELINE configs[2] (camel)')
+    ap.add_argument('--full', action='store_true', help='after the headline, also run every other leg of the line: roofline pass, '
+                    'relaxed-math forward, sweep and other workload points, CPU baseline, LBS, optimize.py iterations, step '
+                    'profile; N > 1: the data-parallel optimisation legs (off: the headline alone)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--rebuild-records', type=int, default=-1, help='1: the backward rebuilds the per-face records, 0: it reuses the '
                     'forward\'s (LASR_SR_RECORDS_VALID), -1 (default): as the autograd operator does -- reuse')
@@ -906,6 +913,82 @@ def sweep_leg(dev, points, steps_budget_ms=150.0):
     return out
 
 
+def roofline_pass(job, steps):
+    """The roofline leg's own pass after the timed region: min(steps, 10) steps with the library's per-kernel HIP events on the
+    launch stream -> {kernel: (mean ms, launches)}."""
+    h = job.h
+    h.lasr_prof_enable(job.stream, 1)
+    for _ in range(min(steps, 10)):
+        job.step()
+    torch.cuda.synchronize()
+    h.lasr_prof_enable(job.stream, 0)
+    return collect_kernel_times(h, job.stream)
+
+
+def roofline_block(job, ktimes):
+    """`roofline` of the line: the dominant raster kernel of roofline_pass against HBM, with the committed counter files' traffic and
+    VALU figures where they apply to this launch."""
+    B, F, P = job.B, job.F, job.IS * job.IS
+    alg = {'sr_forward_kernel': (72 * F + 24 * P) * B, 'sr_backward_kernel': (144 * F + 40 * P) * B,
+           'sr_setup_kernel': (36 + 192 + 8) * F * B}
+    dom = max((k for k in ktimes if k in ('sr_forward_kernel', 'sr_backward_kernel')), key=lambda k: ktimes[k][0])
+    achieved = alg[dom] / (ktimes[dom][0] * 1e-3) / 1e9
+    traffic, traffic_src, traffic_stale = measured_traffic(dom, B) if job.IS == 256 else (None, None, 'PMC passes are taken at 256x256')
+    vi = valu_issue(dom, B, ktimes[dom][0]) if job.IS == 256 else None
+    # achieved / peak / frac are the HBM figures SURVEY 8(d) defines (algorithmic bytes / kernel time); `bound` is what
+    # the counters say binds the kernel: VALU issue (valu_frac is the fraction to track), HBM is two orders of magnitude away
+    return {'bound': 'valu' if vi and vi.get('valu_frac') else 'hbm', 'kernel': dom, 'achieved': achieved,
+            'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic, 'traffic_source': traffic_src,
+            'traffic_stale': traffic_stale,
+            'valu_frac': vi.get('valu_frac') if vi else None,
+            'algorithmic_bytes_per_launch': alg[dom], 'avg_launch_ms': ktimes[dom][0],
+            'all_kernels_avg_ms': {k: v[0] for k, v in ktimes.items()},
+            'raster_source_sha': raster_source_hash(),
+            'valu_issue': vi}
+
+
+def single_gpu_legs(a, job, dev, out):
+    """--full at N = 1: the informational legs after the timed region and the roofline pass, each adding its block to `out`."""
+    global IS
+    B = job.B
+    # informational: the opt-in relaxed forward arithmetic (per-call flag LASR_SR_RELAXED_MATH, image within ~1e-5 of
+    # the default path; `value` is the default, reference-faithful arithmetic)
+    job.forward_flags = _lib.SR_RELAXED_MATH
+    try:
+        job.step()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(min(a.steps, 10)):
+            job.step()
+        torch.cuda.synchronize()
+        out['relaxed_forward_math'] = {'value': B * min(a.steps, 10) / (time.perf_counter() - t1), 'unit': 'frames/s',
+                                       'note': 'opt-in; distance + threshold decision bit-faithful, the rest fp32 rcp/exp'}
+    finally:
+        job.forward_flags = 0
+
+    def optional(key, fn):
+        # the informational legs after the timed region: one that fails leaves {'error': ...} in its block, the line still goes out
+        try:
+            out[key] = fn()
+        except Exception as e:                           # noqa: BLE001
+            out[key] = {'error': repr(e)[:400]}
+    if not a.no_sweep:
+        optional('sweep', lambda: sweep_leg(dev, [(1, 256), (4, 256), (16, 256), (64, 256), (64, 512)]))
+        IS = a.image_size
+        optional('other_points', lambda: variants_leg(dev, B))
+    if not a.no_cpu_baseline:
+        optional('cpu_baseline', lambda: cpu_baseline(job.F))
+    if not a.no_lbs:
+        optional('lbs', lambda: lbs_leg(dev))
+    if a.lasr_iters > 0:
+        optional('optimize_py', lambda: optimize_leg(dev, a.lasr_iters))
+    if a.lasr_iters > 0 and not a.no_step_profile:
+        # after every timed leg: the child process shares this GPU while it runs
+        torch.cuda.synchronize()
+        out['in_scope_step'] = in_scope_step_leg()
+
+
 def main():
     global IS, REBUILD_RECORDS
     a = parse()
@@ -983,23 +1066,10 @@ def main():
     # before the legs below, which run the same buffers again (the relaxed-math pass among them)
     dumped = dump_outputs(job, a.dump_outputs) if a.dump_outputs and rank == 0 else None
 
-    # ---- roofline leg: per-kernel HIP-event timing inside the library (separate pass) ----
-    h = job.h
-    h.lasr_prof_enable(job.stream, 1)
-    for _ in range(min(a.steps, 10)):
-        job.step()
-    torch.cuda.synchronize()
-    h.lasr_prof_enable(job.stream, 0)
-    ktimes = collect_kernel_times(h, job.stream)
+    # ---- --full: the roofline leg, a pass of its own on every rank (per-kernel HIP-event timing inside the library) ----
+    ktimes = roofline_pass(job, a.steps) if a.full else None
 
     if rank == 0:
-        F, P = job.F, IS * IS
-        alg = {'sr_forward_kernel': (72 * F + 24 * P) * B, 'sr_backward_kernel': (144 * F + 40 * P) * B,
-               'sr_setup_kernel': (36 + 192 + 8) * F * B}
-        dom = max((k for k in ktimes if k in ('sr_forward_kernel', 'sr_backward_kernel')), key=lambda k: ktimes[k][0])
-        achieved = alg[dom] / (ktimes[dom][0] * 1e-3) / 1e9
-        traffic, traffic_src, traffic_stale = measured_traffic(dom, B) if IS == 256 else (None, None, 'PMC passes are taken at 256x256')
-        vi = valu_issue(dom, B, ktimes[dom][0]) if IS == 256 else None
         frames = world * B * a.steps
         out = {
             'metric': 'rasterizer fwd+bwd frames/sec at %dx%d, 2.3k faces' % (IS, IS),
@@ -1010,7 +1080,7 @@ def main():
             'rank_device_ids': device_ids,
             'config': {'workload': 'soft-rasteriser fwd+bwd, mesh M2 (V=1212,F=2420), %dx%d, LASR modes '
                                    '(euclidean/softmax/prod/vertex, sigma=1e-4, gamma=1e-2)' % (IS, IS),
-                       'frames_per_gpu_per_step': B, 'image_size': IS, 'faces': F, 'vertices': job.V,
+                       'frames_per_gpu_per_step': B, 'image_size': IS, 'faces': job.F, 'vertices': job.V,
                        'parallelism': 'dp%d (frames sharded, mesh-gradient all-reduce)' % world,
                        'step_definition': 'face setup + [5 frames and more: the launch\'s own tile order, sr_tile_weight_kernel + sr_order_kernel] + '
                                           'forward kernel (background colour passed as an argument: no pre-fill pass, '
@@ -1022,58 +1092,16 @@ def main():
                                           '(+ RCCL all-reduce of the [2,V,3] mesh gradient for N > 1); rounds 1 and early 2 '
                                           'also timed the two fill passes the reference caller needs (soft_rasterize.py:50-53, '
                                           ':88-89), which these entry points make unnecessary'},
-            # achieved / peak / frac are the HBM figures SURVEY 8(d) defines (algorithmic bytes / kernel time); `bound` is what
-            # the counters say binds the kernel: VALU issue (valu_frac is the fraction to track), HBM is two orders of magnitude away
-            'roofline': {'bound': 'valu' if vi and vi.get('valu_frac') else 'hbm', 'kernel': dom, 'achieved': achieved,
-                         'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic, 'traffic_source': traffic_src,
-                         'traffic_stale': traffic_stale,
-                         'valu_frac': vi.get('valu_frac') if vi else None,
-                         'algorithmic_bytes_per_launch': alg[dom], 'avg_launch_ms': ktimes[dom][0],
-                         'all_kernels_avg_ms': {k: v[0] for k, v in ktimes.items()},
-                         'raster_source_sha': raster_source_hash(),
-                         'valu_issue': vi},
         }
+        if a.full:
+            out['roofline'] = roofline_block(job, ktimes)
         if dumped is not None:
             out['dump_outputs'] = {'dir': os.path.abspath(a.dump_outputs), 'seed': DUMP_SEED, 'arrays': dumped}
-        if world == 1:
-            # informational: the opt-in relaxed forward arithmetic (per-call flag LASR_SR_RELAXED_MATH, image within ~1e-5 of
-            # the default path; `value` above is the default, reference-faithful arithmetic)
-            job.forward_flags = _lib.SR_RELAXED_MATH
-            try:
-                job.step()
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                for _ in range(min(a.steps, 10)):
-                    job.step()
-                torch.cuda.synchronize()
-                out['relaxed_forward_math'] = {'value': B * min(a.steps, 10) / (time.perf_counter() - t1), 'unit': 'frames/s',
-                                               'note': 'opt-in; distance + threshold decision bit-faithful, the rest fp32 rcp/exp'}
-            finally:
-                job.forward_flags = 0
-        def optional(key, fn):
-            # the informational legs after the timed region: one that fails leaves {'error': ...} in its block, the line still goes out
-            try:
-                out[key] = fn()
-            except Exception as e:                           # noqa: BLE001
-                out[key] = {'error': repr(e)[:400]}
-        if world == 1 and not a.no_sweep:
-            optional('sweep', lambda: sweep_leg(dev, [(1, 256), (4, 256), (16, 256), (64, 256), (64, 512)]))
-            IS = a.image_size
-            optional('other_points', lambda: variants_leg(dev, B))
-        if world == 1 and not a.no_cpu_baseline:
-            optional('cpu_baseline', lambda: cpu_baseline(F))
-        if world == 1 and not a.no_lbs:
-            optional('lbs', lambda: lbs_leg(dev))
-        if world == 1 and a.lasr_iters > 0:
-            optional('optimize_py', lambda: optimize_leg(dev, a.lasr_iters))
-        if world == 1 and a.lasr_iters > 0 and not a.no_step_profile:
-            # after every timed leg: the child process shares this GPU while it runs
-            torch.cuda.synchronize()
-            out['in_scope_step'] = in_scope_step_leg()
+        if a.full and world == 1:
+            single_gpu_legs(a, job, dev, out)
     emit = LineOnce()
     dp = None
-    if world > 1 and a.lasr_iters > 0:                       # every rank takes part
+    if a.full and world > 1 and a.lasr_iters > 0:            # every rank takes part
 
         def dp_legs():
             d = optimize_dp_leg(dev, a.lasr_iters, rank, world, dist)

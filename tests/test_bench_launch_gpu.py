@@ -29,7 +29,7 @@ def run_bench(args, env_extra=None, timeout=600):
 
 def test_bench_two_ranks_self_launch(cuda):
     backend = 'nccl' if torch.cuda.device_count() >= 2 else 'gloo'
-    out = run_bench(['--gpus', '2', '--steps', '3', '--warmup', '1', '--frames', '16', '--lasr-iters', '4'],
+    out = run_bench(['--gpus', '2', '--steps', '3', '--warmup', '1', '--frames', '16', '--lasr-iters', '4', '--full'],
                     {'LASR_BENCH_BACKEND': backend}, timeout=900)
     assert out['n_gpus'] == 2 and out['world_size'] == 2 and out['steps'] == 3 and out['scaling'] == 'weak'
     assert out['metric'].startswith('rasterizer fwd+bwd frames/sec at 256x256')
@@ -59,7 +59,7 @@ def test_bench_four_ranks_self_launch_on_one_gpu(cuda):
     # optimisation leg, rank 0's single JSON line) runs here with more than two ranks sharing GPU 0 over gloo, at tiny sizes.
     # Four ranks, not eight: with this test's own process that is five processes holding the one GPU open (the self-launching
     # parent does not open it); a shared GPU is not given more than six.
-    out = run_bench(['--gpus', '4', '--steps', '2', '--warmup', '1', '--frames', '4', '--lasr-iters', '2'],
+    out = run_bench(['--gpus', '4', '--steps', '2', '--warmup', '1', '--frames', '4', '--lasr-iters', '2', '--full'],
                     {'LASR_BENCH_BACKEND': 'gloo'}, timeout=1500)
     assert out['n_gpus'] == 4 and out['world_size'] == 4 and len(out['rank_device_ids']) == 4 and out['backend'] == 'gloo'
     assert abs(out['value'] - 4 * 4 * 2 / (out['ms_per_step'] * 2e-3)) <= 1e-6 * out['value']
@@ -72,7 +72,7 @@ def test_bench_four_ranks_self_launch_on_one_gpu(cuda):
 
 
 def test_bench_single_gpu_line_has_every_block(cuda):
-    out = run_bench(['--steps', '3', '--warmup', '1', '--frames', '32', '--lasr-iters', '0'])
+    out = run_bench(['--steps', '3', '--warmup', '1', '--frames', '32', '--lasr-iters', '0', '--full'])
     assert out['n_gpus'] == 1 and out['dtype'] == 'f32' and out['vs_baseline'] is None
     r, c, l = out['roofline'], out['cpu_baseline'], out['lbs']
     # (32 frames per launch: the committed counter files are for 256, so no VALU fraction / traffic is quoted from them)
@@ -98,6 +98,26 @@ def test_bench_dumps_the_same_outputs_from_run_to_run(cuda, tmp_path):
         np.testing.assert_array_equal(a, b, err_msg=name)
     img = np.load(str(tmp_path / 'a' / 'soft_colors.npy'))
     assert 0 <= img.min() < img.max() <= 1
+
+
+FULL_ONLY = {'roofline', 'relaxed_forward_math', 'sweep', 'other_points', 'cpu_baseline', 'lbs', 'optimize_py', 'in_scope_step',
+             'optimize_py_dp'}
+
+
+def test_a_plain_run_prints_the_headline_alone(cuda, tmp_path):
+    # without --full a run sets up, warms up, times its steps, writes --dump-outputs and prints the headline: none of the blocks
+    # that take runs of their own, at one rank or several
+    out = run_bench(['--steps', '3', '--warmup', '1', '--frames', '32', '--dump-outputs', str(tmp_path)])
+    assert out['metric'].startswith('rasterizer fwd+bwd frames/sec at 256x256') and out['unit'] == 'frames/s'
+    assert out['higher_is_better'] is True and out['dtype'] == 'f32' and out['n_gpus'] == 1 and out['warmup'] == 1
+    assert abs(out['value'] - 32 * 3 / (out['ms_per_step'] * 3e-3)) <= 1e-6 * out['value']
+    assert not FULL_ONLY & set(out), sorted(FULL_ONLY & set(out))
+    assert set(out['dump_outputs']['arrays']) == {'soft_colors', 'grad_faces', 'grad_textures', 'mesh_grad'}
+    assert all(os.path.exists(str(tmp_path / (n + '.npy'))) for n in out['dump_outputs']['arrays'])
+    out = run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--frames', '4'], {'LASR_BENCH_BACKEND': 'gloo'}, timeout=600)
+    assert out['n_gpus'] == 2 and out['world_size'] == 2 and len(out['rank_device_ids']) == 2
+    assert abs(out['value'] - 2 * 4 * 2 / (out['ms_per_step'] * 2e-3)) <= 1e-6 * out['value']
+    assert not FULL_ONLY & set(out), sorted(FULL_ONLY & set(out))
 
 
 def test_rccl_executes_on_this_box(cuda):
@@ -141,7 +161,7 @@ def test_bench_line_reports_the_in_scope_kernel_time_of_the_optimisation_step(cu
     import shutil
     if shutil.which('rocprofv3') is None:
         pytest.skip('no rocprofv3 on this box')
-    args = ['--steps', '2', '--warmup', '1', '--frames', '16', '--lasr-iters', '2', '--no-cpu-baseline', '--no-sweep']
+    args = ['--steps', '2', '--warmup', '1', '--frames', '16', '--lasr-iters', '2', '--no-cpu-baseline', '--no-sweep', '--full']
     out = run_bench(args, timeout=900)
     s = out['in_scope_step']
     for cfg in ('spot3_s0', 'camel_s4'):

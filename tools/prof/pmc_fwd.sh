@@ -1,10 +1,10 @@
 # usage: bash tools/prof/pmc_fwd.sh <tag> <forward-variant>     -> gpurun_out/<tag>_pmc.txt (+ <tag>_bench.json)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; TAG=$1; V=$2
 cd /tmp; export TMPDIR=/tmp
-python $R/bench.py --forward-variant $V --no-cpu-baseline --no-lbs --lasr-iters 0 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python $R/bench.py --full --forward-variant $V --no-cpu-baseline --no-lbs --lasr-iters 0 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 pmc() {
   tag=$1; shift
-  rocprofv3 --pmc "$@" -d $O/pmc_$tag -o p -- python $R/bench.py --forward-variant $V --no-cpu-baseline --no-lbs --lasr-iters 0 --steps 2 --warmup 1 > /dev/null 2>$O/pmc_$tag.err
+  rocprofv3 --pmc "$@" -d $O/pmc_$tag -o p -- python $R/bench.py --full --forward-variant $V --no-cpu-baseline --no-lbs --lasr-iters 0 --steps 2 --warmup 1 > /dev/null 2>$O/pmc_$tag.err
   python $R/tools/pmc_summary.py $(find $O/pmc_$tag -name "*.db" | head -1) 2>>$O/pmc_$tag.err | grep -v setup >> $O/${TAG}_pmc.txt; rm -rf $O/pmc_$tag
 }
 rm -f $O/${TAG}_pmc.txt

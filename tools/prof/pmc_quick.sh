@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; T=$1
 [ -n "$2" ] && export LASR_HIP_LIB=$R/$2
 cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0 --steps 3 --warmup 1"
+B="python $R/bench.py --full --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0 --steps 3 --warmup 1"
 rm -f $O/${T}_pmcq.txt
 pmc() {
   rocprofv3 --pmc "$@" -d $O/pmc_x -o p -- $B > /dev/null 2>&1

@@ -7,7 +7,7 @@ for rep in 1 2; do
 for v in nopf base; do
   lib=$R/lasr_amd/csrc/liblasr_hip.so; [ $v != base ] && lib=$R/lasr_amd/csrc/variants/liblasr_hip_$v.so
   for args in "--frames 256" "--frames 64" "--frames 16" "--frames 4" "--frames 64 --image-size 512"; do
-    LASR_HIP_LIB=$lib python bench.py $args --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0 --steps 20 --warmup 3 2>/dev/null | python -c "
+    LASR_HIP_LIB=$lib python bench.py --full $args --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0 --steps 20 --warmup 3 2>/dev/null | python -c "
 import json,sys; d=json.load(sys.stdin); k=d['roofline']['all_kernels_avg_ms']
 print('$v', '$args', 'forward %.4f' % k['sr_forward_kernel'], 'backward %.4f' % k['sr_backward_kernel'], 'step %.4f' % d['ms_per_step'])"
   done

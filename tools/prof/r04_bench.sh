@@ -2,11 +2,11 @@
 # (run tools/prof/r04_final.sh first and copy its counter files into profiles/: the line quotes traffic / valu_frac from them)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; T=${1:-r04}
 cd $R
-python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err
-python bench.py --image-size 512 --frames 64 --no-lbs --no-sweep --lasr-iters 0 > $O/${T}_bench_512.json 2>/dev/null
+python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err
+python bench.py --full --image-size 512 --frames 64 --no-lbs --no-sweep --lasr-iters 0 > $O/${T}_bench_512.json 2>/dev/null
 python tools/cosdist_bench.py > $O/${T}_cosdist.json 2>/dev/null
 (cd /tmp; export TMPDIR=/tmp
- rocprofv3 --kernel-trace -d $O/prof_k -o k -- python $R/bench.py --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0 --steps 30 --warmup 3 > /dev/null 2>&1
+ rocprofv3 --kernel-trace -d $O/prof_k -o k -- python $R/bench.py --full --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0 --steps 30 --warmup 3 > /dev/null 2>&1
  python $R/tools/rocpd_stats.py $(find $O/prof_k -name "*.db" | head -1) > $O/${T}_kernel_stats.txt; rm -rf $O/prof_k)
 head -6 $O/${T}_kernel_stats.txt | cut -c1-140
 python -c "

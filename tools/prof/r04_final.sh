@@ -2,8 +2,8 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; T=${1:-r04}
 cd $R
 cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0"
-rocprofv3 --kernel-trace -d $O/prof_o -o o -- python $R/bench.py --no-cpu-baseline --no-lbs --no-sweep --steps 1 --warmup 1 --frames 16 --lasr-iters 30 > /dev/null 2>&1
+B="python $R/bench.py --full --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0"
+rocprofv3 --kernel-trace -d $O/prof_o -o o -- python $R/bench.py --full --no-cpu-baseline --no-lbs --no-sweep --steps 1 --warmup 1 --frames 16 --lasr-iters 30 > /dev/null 2>&1
 python $R/tools/rocpd_stats.py $(find $O/prof_o -name "*.db" | head -1) 90 > $O/${T}_optimize_step_kernel_stats.txt
 python $R/tools/step_sequence.py $(find $O/prof_o -name "*.db" | head -1) > $O/${T}_step_sequence.txt; rm -rf $O/prof_o
 pmc() {  # $1 = output file, $2 = extra bench args, rest = counters
@@ -30,7 +30,7 @@ for n in 16 4; do
   pmc $O/${T}_pmc_sq_n$n.txt "--frames $n" SQ_WAVES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_ANY GRBM_GUI_ACTIVE
 done
 cd $R; python tools/op_census.py 2>&1 | grep -v -i warn > $O/${T}_op_census.txt
-python tools/traffic_json.py $O/${T}_pmc.txt 256 "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of bench.py --no-cpu-baseline --no-lbs --lasr-iters 0 --steps 3 --warmup 1 (256 frames per launch, mesh M2, 256x256); KiB per dispatch summed over all TCC instances; bytes = FETCH_SIZE x 1024 x read_factor + WRITE_SIZE x 1024 x write_factor with the factors of profiles/r04_traffic_calibration.json (tools/ubench/traffic.hip: vector reads are tallied at half their bytes, scalar-cache reads and stores in full)" $R/profiles/r04_traffic_calibration.json > $O/${T}_traffic.json
+python tools/traffic_json.py $O/${T}_pmc.txt 256 "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of bench.py --full --no-cpu-baseline --no-lbs --lasr-iters 0 --steps 3 --warmup 1 (256 frames per launch, mesh M2, 256x256); KiB per dispatch summed over all TCC instances; bytes = FETCH_SIZE x 1024 x read_factor + WRITE_SIZE x 1024 x write_factor with the factors of profiles/r04_traffic_calibration.json (tools/ubench/traffic.hip: vector reads are tallied at half their bytes, scalar-cache reads and stores in full)" $R/profiles/r04_traffic_calibration.json > $O/${T}_traffic.json
 cp $O/${T}_traffic.json $O/${T}_valu.json $R/profiles/
 # The bench lines and the kernel trace they must agree with are NOT taken here: a box that has just run the GPU test-suite and
 # these profiling passes measured every kernel ~6-8 % slower (62.4 k instead of 66 k frames/s; clocks, not code).  Copy

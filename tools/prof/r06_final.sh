@@ -2,7 +2,7 @@
 # from tools/prof/r06_bench.sh on a FRESH box afterwards -- a box that has just run these passes clocks 6-8 % lower)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; T=${1:-r06}
 cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0"
+B="python $R/bench.py --full --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0"
 # ---- one optimisation iteration, per kernel (the trace bench.py's in_scope_step block is built from) and in launch order
 for cfg in spot3_s0 camel_s4; do
   rocprofv3 --kernel-trace -d $O/prof_o -o o -- python $R/bench.py --step-worker $cfg > /dev/null 2>&1
@@ -33,7 +33,7 @@ rocprofv3 --pmc SQ_INSTS_VALU_MFMA_F32 SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_
 python $R/tools/pmc_summary.py $(find $O/pmc_x -name "*.db" | head -1) > $O/${T}_pmc_lbs.txt 2>/dev/null; rm -rf $O/pmc_x
 python $R/tools/valu_json.py $O/${T}_pmc_sq.txt 256 > $O/${T}_valu.json
 cd $R
-python tools/traffic_json.py $O/${T}_pmc.txt 256 "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of bench.py --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0 --steps 3 --warmup 1 (256 frames per launch, mesh M2, 256x256); KiB per dispatch summed over all TCC instances; bytes = FETCH_SIZE x 1024 x read_factor + WRITE_SIZE x 1024 x write_factor with the factors of profiles/r04_traffic_calibration.json (tools/ubench/traffic.hip: vector reads are tallied at half their bytes, scalar-cache reads and stores in full)" $R/profiles/r04_traffic_calibration.json > $O/${T}_traffic.json
+python tools/traffic_json.py $O/${T}_pmc.txt 256 "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of bench.py --full --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 0 --steps 3 --warmup 1 (256 frames per launch, mesh M2, 256x256); KiB per dispatch summed over all TCC instances; bytes = FETCH_SIZE x 1024 x read_factor + WRITE_SIZE x 1024 x write_factor with the factors of profiles/r04_traffic_calibration.json (tools/ubench/traffic.hip: vector reads are tallied at half their bytes, scalar-cache reads and stores in full)" $R/profiles/r04_traffic_calibration.json > $O/${T}_traffic.json
 # ---- issue- or latency-bound?  the one-wave forward kernel at 8 / 6 / 4 / 2 waves per SIMD
 # (needs the occ6 / occ4 / occ2 builds of tools/prof/occupancy_sweep.sh under lasr_amd/csrc/variants/; skipped when they are absent)
 [ -f lasr_amd/csrc/variants/liblasr_hip_occ4.so ] && bash tools/prof/occupancy_sweep.sh > $O/${T}_occupancy_sweep.txt 2>&1

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; cd $R
 for v in default 0 default 0; do
   if [ $v = default ]; then unset LASR_SR_PAIR_MIN_TILES; else export LASR_SR_PAIR_MIN_TILES=$v; fi
-  python bench.py --frames 16 --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 2 --steps 2 --warmup 1 2>/dev/null | python -c "
+  python bench.py --full --frames 16 --no-cpu-baseline --no-lbs --no-sweep --lasr-iters 2 --steps 2 --warmup 1 2>/dev/null | python -c "
 import json,sys; d=json.load(sys.stdin)
 for c in ('spot3_s0','camel_s4'):
     x=d['in_scope_step'][c]; r=x['raster']
