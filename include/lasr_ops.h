@@ -472,6 +472,38 @@ int lasr_manifold_guard(const float* lattice, float* verts, const long long* fac
                         float min_area, void* hip_stream);
 
 /*
+ * ---- VCN optical flow, matching stage of preprocess/auto_gen.py (lasr_amd/csrc/vcn.hip, lasr_amd/ext_nnutils/vcn.py) -------
+ * All tensors are contiguous fp32 device arrays; U = 2 md + 1 displacements along x, V = 2 mdv + 1 along y (mdv = md // fac).
+ *
+ * lasr_vcn_corr_proj replaces VCN.cost_matching's normalisation, warp and corrf (third_party/ext_nnutils/VCNplus.py:384-394,
+ *   129-148, 350-373) and butterfly4D.proj's projfeat4d 1x1 projection with its BatchNorm (conv4d.py:181, 226-235), eval mode:
+ *   c1n = c1 / (||c1|| + 1e-9), c2n likewise over the C channels of each pixel; t = c2n when flow is NULL (level 0), else
+ *   grid_sample(c2n, q + flow(q), align_corners=True) zeroed unless |vgrid| < 1 in both axes; then
+ *   out[b, f, u, v, y, x] = scale[f] * sum_c proj_w[f, c] * lrelu_0.1(c1n[b, c, y, x] * t[b, c, y + v - mdv, x + u - md]) + shift[f]
+ *   with t = 0 outside the image (those entries are exactly shift[f]).  scale = gamma / sqrt(running_var + eps) and
+ *   shift = beta - running_mean * scale are folded on the host.  The [b, C, U, V, h, w] cost volume is never formed.
+ *   c1, c2 [B, C, H, W]; flow [B, 2, H, W] (x, y) or NULL; proj_w [F, C]; scale, shift [F]; out [B, F, U, V, H, W];
+ *   workspace >= lasr_vcn_corr_proj_workspace_bytes(B, H, W) (per-pixel inverse norms).
+ * lasr_vcn_flow_reg replaces flow_reg.forward (VCNplus.py:68-112) and the up-flow addition of cost_matching (:401-406):
+ *   per hypothesis n = b * F + f and pixel, over cost[n, :, :, pixel] of [B, F, U, V, H, W]: first-index argmax, softmax over the
+ *   7 x 7 (u, v) window around it clipped to the grid, flow = expected (u - md, v - mdv) (+ up_flow[b] when not NULL), local
+ *   entropy / log 49 and global entropy (softmax over all U V) / log(U V), p clamped to [1e-9, 1 - 1e-9].
+ *   flow, ent [B, 2F, H, W]: channel 2f = x-flow / local entropy, 2f + 1 = y-flow / global entropy of hypothesis f.
+ * Checked on the host before any launch (LASR_E_BADARG): B >= 1, 1 <= md <= LASR_VCN_MAX_DISP, 0 <= mdv <= md, H, W >= 1,
+ *   corr_proj: 1 <= C <= LASR_VCN_MAX_CHANNELS, F in {12, 16}, B (2 mdv + 1) <= 65535; flow_reg: 1 <= F <= LASR_VCN_MAX_HYPOTHESES,
+ *   B F <= 65535; every pointer except flow / up_flow non-NULL; a short workspace is LASR_E_WORKSPACE.
+ */
+#define LASR_VCN_MAX_DISP 7
+#define LASR_VCN_MAX_CHANNELS 1024
+#define LASR_VCN_MAX_HYPOTHESES 1024
+size_t lasr_vcn_corr_proj_workspace_bytes(int B, int H, int W);     /* 0 for invalid sizes */
+int lasr_vcn_corr_proj(const float* c1, const float* c2, const float* flow, const float* proj_w, const float* scale,
+                       const float* shift, float* out, void* workspace, size_t workspace_bytes, int B, int C, int F, int H, int W,
+                       int md, int mdv, void* hip_stream);
+int lasr_vcn_flow_reg(const float* cost, const float* up_flow, float* flow, float* ent, int B, int F, int H, int W, int md, int mdv,
+                      void* hip_stream);
+
+/*
  * ---- small-tensor glue of LASR.forward as single kernels (lasr_amd/csrc/glue.hip) -----------------------------------
  *
  * Rotation distance, third_party/ext_utils/util_rot.py:27-37 (called at nnutils/mesh_net.py:508 / :516): m1, m2 [n,3,3]
