@@ -1,17 +1,23 @@
 #!/usr/bin/env python3
-"""Export the reconstructed shape of every frame of a sequence from a checkpoint (reference: /root/reference/extract.py,
-which also renders visualisations with pyrender / matplotlib -- not reproduced).
+"""Export the reconstructed shape of every frame of a sequence from a checkpoint (reference: /root/reference/extract.py).
 
     python extract.py --model_path log/spot3-1/pred_net_latest.pth --dataname spot3 --n_bones 26 --n_faces 1600 \
-                      --nosymmetric --checkpoint_dir log/ --name spot3-1
+                      --nosymmetric --checkpoint_dir log/ --name spot3-1 [--render]
 
 For frame i of the sequence it writes <checkpoint_dir>/<name>/pred<i>.obj (articulated shape in camera space, the frame
 the reference's scripts/eval_mesh.py evaluates: eval_mesh.py:106-109) and cam<i>.txt in the layout of the reference's
 extract.py:123-130: np.savetxt of the 4x4 array [[R | T] (3x4, root body-to-camera transform); [fx, fy, ppx, ppy]] with
 the intrinsics expressed in the uncropped image (nnutils/predictor.py:188-189).  For render_vis.py it also writes pred<i>.ply (the
 same mesh with its per-vertex colours, fusion.meshwrite's layout) and, with n_bones > 1, gauss<i>.ply (the bones' Gaussian
-ellipsoids in camera space, reference extract.py:113-121); the reference's novel-view renders are not reproduced.  The flags are optimize.py's; the model is rebuilt as that stage built it and the checkpoint
-is loaded as is (no re-meshing, no hypothesis selection beyond picking the best one for the export).
+ellipsoids in camera space, reference extract.py:113-121).  The flags are optimize.py's plus --render; the model is rebuilt as that
+stage built it and the checkpoint is loaded as is (no re-meshing, no hypothesis selection beyond picking the best one for the export).
+
+--render (off by default; without it every output is what it was) adds the reference's diagnostic renders of the same forward
+(extract.py:100-206, nnutils/predictor.py:296-353) for the exported hypothesis: render-%05d.png (the input with the predicted mask
+over it, and the front, right and top views of the shaded mesh: lasr_amd/phong.py), vp2pred<i>.ply,
+vp3pred<i>.ply, bone<i>.ply and, with n_bones > 1, renderskin-%05d.png (one soft-renderer render of every bone's skinning weight)
+and, at the sequence's canonical frame, clusters.obj, cpoints.ply and skin.npy.  Part colours come from this project's palette
+(lasr_amd/synth.py:label_palette), not the reference's Cityscapes table.
 """
 import os
 import sys
@@ -22,13 +28,183 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 import optimize                                             # noqa: E402
-from lasr_amd import vis                                     # noqa: E402
+from lasr_amd import phong, synth, vis                       # noqa: E402
+from lasr_amd.nnutils.geom_utils import obj_to_cam          # noqa: E402
+from lasr_amd.nnutils.mesh_net import quaternion_to_rotation_matrix  # noqa: E402
 from lasr_amd.ext_utils.ply import write_ply                 # noqa: E402
 from lasr_amd.nnutils import train_utils                    # noqa: E402
 from lasr_amd.soft_renderer.functional import save_obj       # noqa: E402
 
+# kornia 0.5.3 (x, y, z, w) quaternions the reference turns the root by for the right and top views (predictor.py:312, :324)
+VIEW_QUATS = {'right': (0., -0.707, 0., 0.707), 'top': (-0.707, 0., 0., 0.707)}
+VIEW_SHRINK = 1.2                                            # the two turned views are divided by 1.2 (predictor.py:318, :330)
+TEXEL_SCALE = 500.                                           # vertex colours as uint8 / 500 (predictor.py:309)
 
-def export(tr, out_dir):
+
+def mask_overlay(img, mask):
+    """extract.py:139-144 of the reference: img [3,S,S] in 0-1 (RGB), mask [S,S] the predicted alpha in 0-1 -> uint8 [S,S,3].
+    The reference's "red" image is (0, 0, 255) in an RGB array, i.e. blue, and stays so here.  redMask truncates to uint8, and
+    cv2.addWeighted(redMask, 0.5, uint8(255 img), 1, 0) rounds half to even and saturates."""
+    img = np.transpose(np.asarray(img, np.float64), (1, 2, 0))
+    mask_pred = np.asarray(mask, np.float64) * 255
+    red = np.zeros(img.shape, np.uint8)
+    red[:, :] = (0, 0, 255)
+    red_mask = (red * mask_pred[:, :, None] / 255).astype(np.uint8)
+    base = (255 * img).astype(np.uint8)
+    return np.clip(np.rint(0.5 * red_mask.astype(np.float64) + base.astype(np.float64)), 0, 255).astype(np.uint8)
+
+
+def view_verts(v, pp, fl, eye, shrink=1.):
+    """Camera-space verts [n,V,3] -> pytorch3d world for the front / turned views (predictor.py:300-307): pinhole_cam with the
+    forward's principal point pp [n,2] and focal length fl [n], minus the soft renderer's eye, x and y negated, divided by shrink."""
+    z = v[..., 2:]
+    xy = pp[:, None] + v[..., :2] * fl[:, None, None] / z
+    pre = torch.cat([xy, z], 2) - eye
+    return torch.stack([-pre[..., 0], -pre[..., 1], pre[..., 2]], 2) / shrink
+
+
+def texels(tex):
+    """The reference's trimesh float -> uint8 colour conversion (rounded to nearest, half to even), divided by 500."""
+    return torch.round(tex.clamp(0, 1) * 255) / TEXEL_SCALE
+
+
+def render_panels(views, faces, tex, imgs, masks, S):
+    """views: {'front' | 'right' | 'top': pytorch3d-world verts [n,V,3]}, faces [F,3], tex [V,3] (0-1), imgs [n,3,S,S] (0-1),
+    masks [n,S,S] -> dict of numpy arrays: 'overlay' uint8 [n,S,S,3], 'front' / 'right' / 'top' float [n,S,S,3] (the renders,
+    unclamped, on white) and 'alpha' [n,S,S] (the front view's alpha: the reference's mask_pred).  All frames and views go
+    through one phong.render call per winding: vis.fix_inversion stands in for trimesh's fix_normals, per frame."""
+    names = ('front', 'right', 'top')
+    n = views['front'].shape[0]
+    allv = torch.cat([views[k] for k in names], 0)                           # [3n,V,3]
+    faces = torch.as_tensor(faces, dtype=torch.long, device=allv.device)
+    flip = torch.tensor([vis.signed_volume(allv[i], faces) < 0 for i in range(allv.shape[0])], device=allv.device)
+    rgba = torch.empty(allv.shape[0], S, S, 4, device=allv.device)
+    col = texels(tex)
+    for f, sel in ((faces, ~flip), (faces[:, [0, 2, 1]].contiguous(), flip)):
+        idx = sel.nonzero()[:, 0]
+        if len(idx):
+            rgba[idx] = phong.render(allv[idx], f, col, S, background=(1., 1., 1.))
+    rgba = rgba.view(3, n, S, S, 4).cpu().numpy()
+    on_white = (imgs * masks[:, None] + (1 - masks[:, None])).cpu().numpy()   # the observed crop, object on white
+    out = {k: rgba[i, ..., :3] for i, k in enumerate(names)}
+    out['alpha'] = rgba[0, ..., 3]
+    out['overlay'] = np.stack([mask_overlay(on_white[j], out['alpha'][j]) for j in range(n)])
+    return out
+
+
+def save_panels(path, panels, j, fid):
+    """The reference's 16 x 4 figure (extract.py:146-180): overlay, front, right and top view."""
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    fig = plt.figure(figsize=(16, 4))
+    for k, (key, title) in enumerate((('overlay', 'input/rendered mask [frame %d]' % fid), ('front', 'front view'),
+                                      ('right', 'right view'), ('top', 'top view'))):
+        ax = fig.add_subplot(1, 4, k + 1)
+        ax.imshow(np.clip(panels[key][j], 0, 1) if key != 'overlay' else panels[key][j])   # imshow clips floats to [0, 1]
+        ax.set_title(title)
+        ax.axis('off')
+    fig.savefig(path)
+    plt.close(fig)
+
+
+def render_skin(verts_cam, faces, skin, joints, pp, fl, eye, S):
+    """renderskin (predictor.py:339-348, extract.py:182-191): one soft-renderer render per bone of the frame's camera-space mesh
+    (pinhole, minus eye, y negated) coloured (w, 0, 0) by that bone's skinning weight w, all J in one call, on white, with the
+    joint's projection drawn as a (0, 1, 1) dot of radius 2 px (cv2.circle(..., 1, ..., 3) in the reference).
+    verts_cam [V,3], skin [J,V], joints [J,2] (NDC) -> float [J,S,S,3]."""
+    from lasr_amd import soft_renderer as sr
+    z = verts_cam[:, 2:]
+    pre = torch.cat([pp + verts_cam[:, :2] * fl / z, z], 1) - eye
+    pre = torch.stack([pre[:, 0], -pre[:, 1], pre[:, 2]], 1)
+    J = skin.shape[0]
+    r = sr.SoftRenderer(image_size=S, background_color=[1, 1, 1], camera_mode='look_at', perspective=False, light_mode='vertex',
+                        light_intensity_ambient=1., light_intensity_directionals=0.)
+    red = torch.tensor([1., 0., 0.], device=skin.device)
+    mesh = sr.Mesh(pre[None].expand(J, -1, -1).contiguous(), faces[None].expand(J, -1, -1).contiguous(),
+                   textures=(skin[:, :, None] * red).contiguous(), texture_type='vertex')
+    img = r.render_mesh(mesh)[:, :3].permute(0, 2, 3, 1).cpu().numpy().copy()
+    rr, cc = np.mgrid[0:S, 0:S]
+    for i, (x, y) in enumerate(joints.cpu().numpy()):
+        cx, cy = int(round(S / 2 + S / 2 * x)), int(round(S / 2 + S / 2 * y))
+        img[i][(rr - cy) ** 2 + (cc - cx) ** 2 <= 4] = (0., 1., 1.)
+    return img
+
+
+def save_skin(path, img):
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    fig = plt.figure(figsize=(16, 16))
+    for i in range(len(img)):
+        ax = fig.add_subplot(6, 7, i + 1)
+        ax.imshow(np.clip(img[i], 0, 1))
+        ax.axis('off')
+    fig.savefig(path)
+    plt.close(fig)
+
+
+def canonical_frame(opts):
+    from lasr_amd.dataloader import vid
+    try:
+        return vid.read_config(opts.dataname, getattr(opts, 'data_root', '.'))['can_frame']
+    except (FileNotFoundError, KeyError, ValueError):
+        return None
+
+
+def render_batch(tr, n, best, verts, tex):
+    """Everything --render needs from one training-mode forward, for hypothesis `best` of the n images of the batch."""
+    m = tr.module
+    H, K, S = tr.opts.n_hypo, tr.opts.n_bones, tr.opts.img_size
+    Rmat, Tmat, scale, ppoint = m._cam_src[:4]
+    Rb = Rmat.view(n, H, K, 3, 3)[:, best]
+    Tb = Tmat.view(n, H, K, 3)[:, best]
+    fl = scale.reshape(n, H)[:, best]
+    pp = ppoint.view(n, 2)
+    eye = torch.as_tensor(m.renderer_softtex.transform.transformer._eye, dtype=torch.float32, device=verts.device).reshape(-1)[:3]
+    deform = m.deform_v.view(n, H, -1, 3)[:, best]                           # the skinned shape before the root transform
+    cam = {'front': verts}
+    for key, q in VIEW_QUATS.items():                                        # Rmat_tex[:1] = Rmat[:1] R(q): the root turned
+        Rq = quaternion_to_rotation_matrix(torch.tensor([q], device=verts.device))[0]
+        cam[key] = deform.matmul(Rb[:, 0].matmul(Rq)) + Tb[:, 0, None]
+    views = {k: view_verts(v, pp, fl, eye, 1. if k == 'front' else VIEW_SHRINK) for k, v in cam.items()}
+    out = dict(cam=cam, panels=render_panels(views, m.faces, tex, m.imgs, m.masks.reshape(n, S, S), S))
+    if K > 1:
+        mean_v = m.get_mean_shape(n // 2)[0]
+        skin = m._skinning(mean_v, n)[best, :, :, 0]                         # [J,V]
+        ctl_ts = m.ctl_ts.view(H, K - 1, 3)[best]
+        eyeJ = torch.eye(K - 1, device=verts.device)[None, :, :, None]
+        # bone<i>.ply: the control points through the part transforms only (tocam=False, as predictor.py:268 makes bones_3d)
+        out['bones'] = torch.stack([obj_to_cam(ctl_ts[None], Rb[j], Tb[j][:, None], K, 1, eyeJ, tocam=False)[0] for j in range(n)])
+        joints = m.ctl_proj.view(n, H, K - 1, -1)[:, best, :, :2]
+        out['skin_imgs'] = [render_skin(verts[j], m.faces, skin, joints[j], pp[j], fl[j], eye, S) for j in range(n)]
+        out.update(skin=skin, pred_v=mean_v.view(n, H, -1, 3)[0, best], ctl_ts=ctl_ts)
+    return out
+
+
+def write_renders(tr, out_dir, rv, k, fid, colors, panels):
+    """The --render files of image k of the batch, frame fid; colors: pred<i>.ply's vertex colours (0-255)."""
+    m = tr.module
+    faces = m.faces.cpu().numpy()
+    save_panels(os.path.join(out_dir, 'render-%05d.png' % fid), rv['panels'], k, fid)
+    write_ply(os.path.join(out_dir, 'vp2pred%d.ply' % fid), rv['cam']['right'][k].cpu().numpy(), faces, colors=colors)
+    write_ply(os.path.join(out_dir, 'vp3pred%d.ply' % fid), rv['cam']['top'][k].cpu().numpy(), faces, colors=colors)
+    if panels is not None:
+        panels[fid] = {key: v[k] for key, v in rv['panels'].items()}
+    K = tr.opts.n_bones
+    if K > 1:
+        cmap = synth.label_palette(K - 1)
+        write_ply(os.path.join(out_dir, 'bone%d.ply' % fid), rv['bones'][k].cpu().numpy(), np.zeros((0, 3)), colors=cmap)
+        save_skin(os.path.join(out_dir, 'renderskin-%05d.png' % fid), rv['skin_imgs'][k])
+        if fid == canonical_frame(tr.opts):                                 # extract.py:195-206
+            skin = rv['skin']
+            skin_colors = (skin.t()[:, :, None] * torch.tensor(cmap, device=skin.device)[None]).sum(1) / 256.
+            save_obj(os.path.join(out_dir, 'clusters.obj'), rv['pred_v'], m.faces, textures=255 * skin_colors, texture_type='vertex')
+            write_ply(os.path.join(out_dir, 'cpoints.ply'), rv['ctl_ts'].cpu().numpy(), np.zeros((0, 3)), colors=cmap)
+            np.save(os.path.join(out_dir, 'skin.npy'), skin.cpu().numpy())
+
+
+def export(tr, out_dir, render=False, panels=None):
     """-> {frame id: obj path}"""
     m = tr.module
     H = tr.opts.n_hypo
@@ -52,9 +228,12 @@ def export(tr, out_dir):
                 Rmat, Tmat = m._cam_src[0], m._cam_src[1]
                 Rmat, Tmat = Rmat.view(len(ids), H, K, 3, 3)[:, best], Tmat.view(len(ids), H, K, 3)[:, best]
                 ctl = [p.view(H, K - 1, -1)[best] for p in (m.ctl_ts, m.ctl_rs, m.log_ctl)]
+            rv = render_batch(tr, len(ids), best, verts, tex) if render else None
             for k, fid in enumerate(int(v) for v in ids.tolist()):
                 if fid in done:
                     continue
+                if render:
+                    write_renders(tr, out_dir, rv, k, fid, 255 * tex.cpu().numpy(), panels)
                 path = os.path.join(out_dir, 'pred%d.obj' % fid)
                 save_obj(path, verts[k].cpu(), m.faces.cpu())
                 rtk = np.concatenate([np.concatenate([cam['R'][k], cam['T'][k][:, None]], 1),
@@ -71,8 +250,13 @@ def export(tr, out_dir):
     return done
 
 
+def parse_flags(argv):
+    """optimize.py's flags plus --render (default off)."""
+    return optimize.parse_flags(argv, defaults=dict(optimize.DEFAULTS, render=False))
+
+
 def main(argv):
-    opts = optimize.parse_flags(argv)
+    opts = parse_flags(argv)
     if not opts.model_path:
         raise SystemExit('--model_path is required')
     ckpt, opts.model_path = opts.model_path, ''              # build the model plainly, then load the tensors verbatim
@@ -90,8 +274,10 @@ def main(argv):
                       strict=False)
     if states.get('epoch_nscore') is not None and len(states['epoch_nscore']) == opts.n_hypo:
         tr.epoch_nscore = states['epoch_nscore'].to(tr.device)
-    out = export(tr, os.path.join(opts.checkpoint_dir, opts.name))
+    panels = {} if opts.render else None
+    out = export(tr, os.path.join(opts.checkpoint_dir, opts.name), render=opts.render, panels=panels)
     print('wrote %d meshes to %s' % (len(out), os.path.join(opts.checkpoint_dir, opts.name)))
+    main.panels = panels                                      # --render: {frame id: the figure's panel arrays}
     return out
 
 

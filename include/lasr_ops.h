@@ -472,6 +472,33 @@ int lasr_manifold_guard(const float* lattice, float* verts, const long long* fac
                         float min_area, void* hip_stream);
 
 /*
+ * ---- Phong pass of extract.py --render and scripts/eval_mesh.py --render (lasr_amd/csrc/phong.hip, lasr_amd/phong.py) ------------
+ * Replaces pytorch3d 0.4.0's MeshRenderer(MeshRasterizer(OrthographicCameras(), RasterizationSettings(cull_backfaces=True)),
+ * SoftPhongShader(PointLights(ambient = diffuse = specular = white)), BlendParams()) of the reference (nnutils/predictor.py:296-335,
+ * scripts/eval_mesh.py:170-192) for K = 1 face per pixel and blur radius 0.  Visibility is NOT computed here: `raster` is the
+ * hard-mode aggrs_info of lasr_sr_forward_bg (func_id_rgb = func_id_alpha = 0) whose plane 1 names the nearest face per pixel.
+ * N frames share one face list of F faces over V vertices per frame, in pytorch3d world (= view) coordinates.
+ *   vert_rec [N,V,12]   position x y z, 0 | unit vertex normal x y z, 0 | colour (texel) r g b, 0
+ *   faces    [F,4]      vertex indices, 4th unused; an index outside [0, V) leaves its pixels uncovered
+ *   raster   [N,2,S,S]  plane 1: face index in [0, F) or -1 (row 0 is the top row, NDC y = +1)
+ *   background          3 host floats (0-1)
+ *   out      [N,S,S,4]  fp32 RGBA, unclamped
+ * Pixel (row r, column c) of frame n sits at pytorch3d NDC x = 1 - (2c + 1)/S, y = 1 - (2r + 1)/S (+X left, +Y up); with the
+ * default orthographic camera world x, y are NDC.  Covered by face f: 2-D barycentrics at the pixel centre (no perspective
+ * correction), linear position p, normal, texel and z; n = normalize(normal, 1e-6), l = normalize((0, 1, 0) - p),
+ * v = normalize(-p), colour = (1 + relu(n.l)) texel + [n.l > 0] relu(v.(2 (n.l) n - l))^64; softmax_rgb_blend with
+ * sigma = gamma = 1e-4, znear = 1, zfar = 100: prob = sigmoid(d2 / sigma) with d2 the squared distance to the face's nearest
+ * edge, z_inv = (zfar - z) / (zfar - znear), m = max(z_inv, 1e-10), w = prob exp((z_inv - m) / gamma),
+ * delta = max(exp((1e-10 - m) / gamma), 1e-10), rgb = (w colour + delta bg) / (w + delta), alpha = prob.  Uncovered: bg, 0.
+ * Checked on the host before any launch (LASR_E_BADARG): N >= 0, V, F >= 1, 1 <= S <= LASR_PHONG_MAX_SIZE, N <= 65535,
+ *   every pointer non-NULL when N > 0.  Device contents are not read on the host: a map entry outside [0, F) (-1, NaN) or a face
+ *   with a vertex index outside [0, V) shades as background, so no gather leaves its buffer.
+ */
+#define LASR_PHONG_MAX_SIZE 8192
+int lasr_phong_shade(const float* vert_rec, const int* faces, const float* raster, const float* background, float* out, int N, int V,
+                     int F, int S, void* hip_stream);
+
+/*
  * ---- VCN optical flow, matching stage of preprocess/auto_gen.py (lasr_amd/csrc/vcn.hip, lasr_amd/ext_nnutils/vcn.py) -------
  * All tensors are contiguous fp32 device arrays; U = 2 md + 1 displacements along x, V = 2 mdv + 1 along y (mdv = md // fac).
  *

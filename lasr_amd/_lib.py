@@ -94,6 +94,8 @@ SIGNATURES = {
     'lasr_vcn_corr_proj_workspace_bytes': (_sz, [_i, _i, _i]),
     'lasr_vcn_corr_proj': (_i, [_p] * 8 + [_sz] + [_i] * 7 + [_p]),
     'lasr_vcn_flow_reg': (_i, [_p] * 4 + [_i] * 6 + [_p]),
+    # lasr_amd/csrc/phong.hip
+    'lasr_phong_shade': (_i, [_p] * 5 + [_i] * 4 + [_p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -143,7 +145,7 @@ SIGNATURES = {
     'lasr_prof_collect': (_i, [_p, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong)]),
 }
 
-ABI_VERSION = 9                                     # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
+ABI_VERSION = 10                                    # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
 # flags of the *_ex entry points (include/lasr_sr.h)
 SR_DEFAULT_FLAGS, SR_RELAXED_MATH, SR_SEGMENTED, SR_RECORDS_VALID, SR_GRADS_OVERWRITE = -1, 1, 2, 4, 8
 SR_PAIR_ONE_TEAM, SR_PAIR_TWO_TEAMS = 16, 32          # forward: teams of four waves per tile of the pair-walk kernel (default: by launch size)

@@ -17,7 +17,7 @@ enum LasrKernelId {
     K_RENDER_TABLES_FLOW, K_RASTER_FACES, K_MESH_REG, K_RENDER_TABLES_FOLD, K_LBS_BACKWARD_FOLD, K_PROJECT_POINTS, K_POSE_CHAIN,
     K_TEXTURE_ATLAS, K_VOXEL_SURFACE, K_VOXEL_FILL, K_VIS_SHADE, K_KP_TRANSFER, K_KP_SAMPLE,
     K_MF_PACK, K_MF_REPAIR, K_MF_COUNT, K_MF_SCAN, K_MF_EXTRACT, K_MF_PROJECT, K_MF_GUARD,
-    K_VCN_NORM, K_VCN_CORR_PROJ, K_VCN_FLOW_REG,
+    K_VCN_NORM, K_VCN_CORR_PROJ, K_VCN_FLOW_REG, K_PHONG_SHADE,
     K_NUM_KERNELS
 };
 

@@ -13,7 +13,13 @@ it as the normal consistency).  pytorch3d / trimesh are not available here: area
 the Chamfer sum and the normal term are written out; the nearest-neighbour searches run on lasr_nearest_point.
 --remesh RESOLUTION > 0 re-meshes every prediction watertight first, as the reference does with the external Manifold binary
 for LASR's predictions (:100-105, `manifold in.obj out.obj 10000`): lasr_amd/nnutils/manifold.py:watertight on the GPU.  The
-default 0 scores the predictions as they are.  (The reference's error images are not rendered.)
+default 0 scores the predictions as they are.
+--render also writes the reference's images (:170-200) into --testdir: gt-/pd-/cd-%06d.png, 512 x 512 pytorch3d-style Phong
+renders (lasr_amd/phong.py) of the ground truth and the aligned prediction in grey and of the ground truth coloured by its error,
+and one GIF of the three side by side (--gif, 5 s in all).  The error colour is matplotlib's plasma of 2 x the squared distance
+from each ground-truth vertex to the nearest aligned prediction sample.  This departs from the reference, which indexes
+chamfer3D's first output (one entry per prediction sample) by ground-truth vertex (:168, :172) and so colours vertex k with
+sample k's error.  The printed scores do not depend on --render.
 """
 import argparse
 import glob
@@ -24,6 +30,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from lasr_amd import phong, vis                            # noqa: E402
 from lasr_amd.nnutils import fused_ops                     # noqa: E402
 from lasr_amd.nnutils.manifold import watertight           # noqa: E402
 from lasr_amd.soft_renderer.functional import load_obj      # noqa: E402
@@ -87,9 +94,10 @@ def chamfer_with_normals(x, nx, y, ny):
     return float(dx.mean() + dy.mean()), float((1 - cos_x).mean() + (1 - cos_y).mean())
 
 
-def evaluate_pair(pred, gt, n=10000, seed=0, with_normals=False):
+def evaluate_pair(pred, gt, n=10000, seed=0, with_normals=False, aligned=None):
     """pred, gt: (verts [V,3], faces [F,3]) on the GPU -> Chamfer distance after normalisation and ICP; with_normals: the pair
-    (Chamfer distance, normal consistency = 1 - normal term) the reference prints per frame (:197)."""
+    (Chamfer distance, normal consistency = 1 - normal term) the reference prints per frame (:197).  aligned: a dict that receives
+    the normalised ground truth 'gt', the aligned prediction 'pred' and its evaluation sample 'sample' (with_normals only)."""
     gen = torch.Generator(device=pred[0].device).manual_seed(seed)
     (xv, xf), (yv, yf) = pred, gt
     yv = yv - yv.mean(0, keepdim=True)
@@ -103,32 +111,95 @@ def evaluate_pair(pred, gt, n=10000, seed=0, with_normals=False):
     x, nx = sample_points(xv, xf, n, gen, True)
     y, ny = sample_points(yv, yf, n, gen, True)
     cd, norm = chamfer_with_normals(x, nx, y, ny)
+    if aligned is not None:
+        aligned.update(gt=yv, pred=xv, sample=x)
     return cd, 1. - norm
 
 
-def main(argv=None):
+RENDER_SIZE = 512
+
+
+def error_colors(d2):
+    """RGB of matplotlib's plasma at 2 x the squared error d2 (values above 0.5 saturate)."""
+    import matplotlib
+    return matplotlib.colormaps['plasma'](2 * np.asarray(d2, np.float64))[:, :3]
+
+
+def render_triplet(gt, pred, sample):
+    """The reference's gt / pd / cd images (:170-192): gt (verts, faces) normalised, pred aligned, sample its evaluation points.
+    Both meshes are divided by 1.05 max|gt|, x and z negated and z shifted to start at 1; grey 0.5, or the error colours.
+    -> uint8 [512, 3 * 512, 3] (np.clip(255 img, 0, 255) truncated)."""
+    (yv, yf), (xv, xf) = gt, pred
+    d2 = fused_ops.nearest_point(yv[None].contiguous(), sample[None].contiguous())[0][0]
+    err = torch.as_tensor(error_colors(d2.cpu().numpy()), dtype=torch.float32, device=yv.device)
+    s = 1.05 * yv.abs().max()
+
+    def place(v):
+        v = v / s
+        v = torch.stack([-v[:, 0], v[:, 1], -v[:, 2]], 1)
+        return torch.stack([v[:, 0], v[:, 1], v[:, 2] - (v[:, 2].min() - 1)], 1)
+    vy, vx = place(yv), place(xv)
+    fy, fx = vis.fix_inversion(vy, yf).to(yv.device), vis.fix_inversion(vx, xf).to(xv.device)
+    grey_y = torch.full_like(vy, 0.5)
+    gt_cd = phong.render(torch.stack([vy, vy]), fy, torch.stack([grey_y, err]), RENDER_SIZE)
+    pd = phong.render(vx[None], fx, torch.full_like(vx, 0.5), RENDER_SIZE)
+    img = torch.cat([gt_cd[0, ..., :3], pd[0, ..., :3], gt_cd[1, ..., :3]], 1)
+    return np.clip(255 * img.cpu().numpy(), 0, 255).astype(np.uint8)
+
+
+def write_renders(testdir, i, img):
+    from PIL import Image
+    S = RENDER_SIZE
+    for k, name in enumerate(('gt', 'pd', 'cd')):
+        Image.fromarray(np.ascontiguousarray(img[:, k * S:(k + 1) * S])).save(os.path.join(testdir, '%s-%06d.png' % (name, i)))
+
+
+def write_gif(path, frames):
+    """imageio.mimsave(path, frames, duration=5 / len(frames)): 5 s in all."""
+    from PIL import Image
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    ims = [Image.fromarray(f) for f in frames]
+    ims[0].save(path, save_all=True, append_images=ims[1:], duration=int(round(5000. / len(ims))), loop=0)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='mesh evaluation')
     ap.add_argument('--testdir', required=True)
     ap.add_argument('--gtdir', required=True)
     ap.add_argument('--remesh', type=int, default=0, metavar='RESOLUTION',
                     help='re-mesh each prediction watertight at this resolution first (the reference: 10000); 0: as it is')
+    ap.add_argument('--render', action='store_true', help='write gt-/pd-/cd-%%06d.png into --testdir and the --gif')
+    ap.add_argument('--gif', default=os.path.join('tmp', 'output.gif'), help='the GIF --render writes (default tmp/output.gif)')
     args = ap.parse_args(argv)
     if args.remesh < 0:
         ap.error('--remesh takes a non-negative resolution')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     dev = torch.device('cuda', 0)
     gts = sorted(glob.glob('%s/*.obj' % args.gtdir))
     preds = sorted(glob.glob('%s/pred*.obj' % args.testdir)) or sorted(glob.glob('%s/*.obj' % args.testdir))
     assert len(gts) == len(preds) and gts, 'need the same number of predicted and ground-truth meshes'
-    cds, ncs = [], []
+    cds, ncs, frames = [], [], []
     for i, (p, g) in enumerate(zip(preds, gts)):
         pm, gm = load_obj(p, device=dev), load_obj(g, device=dev)
         pm = (pm[0].float(), pm[1].long())
         if args.remesh > 0:
             pm = watertight(pm[0], pm[1], args.remesh)
-        cd, nc = evaluate_pair(pm, (gm[0].float(), gm[1].long()), with_normals=True)
+        al = {} if args.render else None
+        cd, nc = evaluate_pair(pm, (gm[0].float(), gm[1].long()), with_normals=True, aligned=al)
+        if args.render:
+            img = render_triplet((al['gt'], gm[1].long()), (al['pred'], pm[1]), al['sample'])
+            write_renders(args.testdir, i, img)
+            frames.append(img)
         cds.append(cd); ncs.append(nc)
         print('%04d: %.2f, %.2f' % (i, cd, nc))                       # the reference's line (:197): Chamfer, normal consistency
     print('ALL: %.2f, %.2f' % (np.mean(cds), np.mean(ncs)))
+    if args.render:
+        write_gif(args.gif, frames)
     main.normal_consistency = ncs
     return cds
 
