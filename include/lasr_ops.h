@@ -499,6 +499,66 @@ int lasr_phong_shade(const float* vert_rec, const int* faces, const float* raste
                      int F, int S, void* hip_stream);
 
 /*
+ * ---- Nearest neighbours at evaluation size, chamfer3D and ICP (lasr_amd/csrc/chamfer.hip, lasr_amd/chamfer3D, lasr_amd/nnutils/icp.py)
+ * All point sets are contiguous fp32 device arrays [N,points,3]; indices are int32.  lasr_nearest_point above is shaped for
+ * LASR's <= 1.3 k-point sets; these are shaped for the 10 000 x 10 000 of scripts/eval_mesh.py:116-168.
+ *
+ * lasr_nn_tiled: a [N,P,3], b [N,Q,3] -> d2 [N,P], idx [N,P]: squared distance to and index of the nearest b point, lowest index
+ *   on ties; a row with no finite distance (NaN) reports d2 = inf, idx = 0 (the idx1 / dist1 of NmDistanceKernel,
+ *   third_party/chamfer3D/chamfer3D.cu:12-134).  R [N,3,3], T [N,3]: both NULL, or a rigid transform per batch element read from
+ *   device memory and applied to every query as it is loaded, row-vector convention a R + T.  Without a transform d2 and idx
+ *   equal lasr_nearest_point's bit for bit.  The target set passes through LDS in tiles of LASR_NN_TILE points; `splits` runs of
+ *   whole tiles are searched by separate blocks and merged through 64-bit keys (distance bits high, index low) by atomicMin, which
+ *   keeps "lowest index wins" in any arrival order.  splits = 0: chosen from the sizes; splits > 0: that many (at most 65535).
+ *   workspace: lasr_chamfer3d_workspace_bytes(N, P, 0) bytes, needed when more than one split runs (may be NULL for splits = 1).
+ * lasr_chamfer3d_forward: both directions of chamfer_3DFunction.forward (third_party/chamfer3D/dist_chamfer_3D.py:28-47) in one
+ *   call: dist1, idx1 [N,P] of xyz1 against xyz2, dist2, idx2 [N,Q] of xyz2 against xyz1.
+ *   workspace: lasr_chamfer3d_workspace_bytes(N, P, Q).
+ * lasr_chamfer3d_backward: the gradient of sum grad_dist1 dist1 + sum grad_dist2 dist2 with the indices fixed
+ *   (NmDistanceGradKernel, chamfer3D.cu:155-180, dist_chamfer_3D.py:50-64):
+ *     grad_xyz1[i] = 2 g1[i] (x1_i - x2[idx1[i]]) + sum_{j: idx2[j] = i} 2 g2[j] (x1_i - x2_j), and symmetrically grad_xyz2.
+ *   The reference scatters with float atomics; here every point gathers its terms in a fixed order, so two calls give the same
+ *   bits.  The caller supplies the inverse of the index maps as CSR: row_ptr1 [N,P+1], col1 [N,Q] list, for every xyz1 point, the
+ *   xyz2 points j with idx2[j] = it, ascending in j; row_ptr2 [N,Q+1], col2 [N,P] the same from idx1 (a stable sort of the
+ *   indices: lasr_amd/chamfer3D/dist_chamfer_3D.py).  An index or column outside its set contributes nothing.
+ * ICP: pytorch3d.ops.iterative_closest_point(X, Y, estimate_scale=False) as called at scripts/eval_mesh.py:156 (pytorch3d is not
+ *   vendored: its published loop restated, parity unpinned).  Per iteration: nearest Y point of every X R + T; Kabsch alignment of
+ *   the original X onto those points (centred covariance X^T Y / P, SVD with descending singular values,
+ *   R = U diag(1, 1, det(U V^T)) V^T, T = mean(Y_nn) - mean(X) R); rmse = sqrt(mean |X R + T - Y_nn|^2) of the new transform over
+ *   the old correspondences; relative = (previous rmse - rmse) / previous rmse, 1 on the first iteration; the batch has converged
+ *   when relative <= relative_rmse_thr for every element.  The sums are taken in double over per-block partials in a fixed order
+ *   and the 3x3 is solved in double on the device; three launches per iteration, no host value inside one.
+ *   State, caller-owned device memory: R [N,3,3] and T [N,3] fp32, rmse [N,2] fp64 {this iteration's, the previous one's},
+ *   status int32 [2] {stop flag, iterations done}.  lasr_icp_init sets R = I, T = 0, status = {0, 0} and arms the workspace.
+ *   lasr_icp_iterate enqueues n_iters iterations without synchronising; every kernel reads the stop flag first and returns without
+ *   writing once it is set, so the state stays that of the converging iteration.  The caller reads status[0] between calls.
+ *   workspace: lasr_icp_workspace_bytes(N, P, Q), the same buffer for init and every iterate of a run.
+ * lasr_icp_kabsch_host: TEST / DIAGNOSTIC entry, not part of the evaluation path and launching nothing: the alignment step alone, on the host, from the fifteen sums over P pairs {sum x (3), sum y (3),
+ *   sum x_i y_j (9, row-major)}; the same code the device runs (tests compare it with a LAPACK SVD without a GPU).
+ * Checked on the host before any launch (LASR_E_BADARG): N >= 0 (ICP: 1 <= N <= LASR_ICP_MAX_BATCH), N <= 65535,
+ *   P >= 0 (chamfer3d, ICP: >= 1), Q >= 1, P, Q <= 2^27, 0 <= splits <= 65535, 0 <= n_iters <= LASR_ICP_MAX_CHUNK, R and T both
+ *   NULL or neither, every other pointer non-NULL when there is work; LASR_E_WORKSPACE for a workspace that is too small.
+ *   The *_workspace_bytes functions return 0 for sizes the calls refuse.
+ */
+#define LASR_NN_TILE 512
+#define LASR_ICP_MAX_BATCH 64
+#define LASR_ICP_MAX_CHUNK 4096
+size_t lasr_chamfer3d_workspace_bytes(int N, int P, int Q);
+int lasr_nn_tiled(const float* a, const float* b, const float* R, const float* T, float* d2, int* idx, void* workspace,
+                  size_t workspace_bytes, int N, int P, int Q, int splits, void* hip_stream);
+int lasr_chamfer3d_forward(const float* xyz1, const float* xyz2, float* dist1, float* dist2, int* idx1, int* idx2, void* workspace,
+                           size_t workspace_bytes, int N, int P, int Q, int splits, void* hip_stream);
+int lasr_chamfer3d_backward(const float* xyz1, const float* xyz2, const int* idx1, const int* idx2, const float* grad_dist1,
+                            const float* grad_dist2, const int* row_ptr1, const int* col1, const int* row_ptr2, const int* col2,
+                            float* grad_xyz1, float* grad_xyz2, int N, int P, int Q, void* hip_stream);
+size_t lasr_icp_workspace_bytes(int N, int P, int Q);
+int lasr_icp_init(float* R, float* T, double* rmse, int* status, void* workspace, size_t workspace_bytes, int N, int P, int Q,
+                  void* hip_stream);
+int lasr_icp_iterate(const float* X, const float* Y, float* R, float* T, double* rmse, int* status, void* workspace,
+                     size_t workspace_bytes, int N, int P, int Q, int n_iters, double relative_rmse_thr, int splits, void* hip_stream);
+int lasr_icp_kabsch_host(const double* moments, int P, float* R, float* T);   /* test / diagnostic hook, see above */
+
+/*
  * ---- VCN optical flow, matching stage of preprocess/auto_gen.py (lasr_amd/csrc/vcn.hip, lasr_amd/ext_nnutils/vcn.py) -------
  * All tensors are contiguous fp32 device arrays; U = 2 md + 1 displacements along x, V = 2 mdv + 1 along y (mdv = md // fac).
  *

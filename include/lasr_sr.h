@@ -59,8 +59,9 @@ extern "C" {
  *   7  evaluation (no existing signature changes): lasr_kp_transfer, the keypoint transfer of scripts/eval_badja.py.
  *   8  watertight re-meshing (no existing signature changes): lasr_manifold_* of scripts/manifold.py.
  *   9  optical-flow preprocessing (no existing signature changes): lasr_vcn_corr_proj*, lasr_vcn_flow_reg of preprocess/auto_gen.py.
- *   10 diagnostic renders (no existing signature changes): lasr_phong_shade of extract.py --render, scripts/eval_mesh.py --render. */
-#define LASR_ABI_VERSION 10
+ *   10 diagnostic renders (no existing signature changes): lasr_phong_shade of extract.py --render, scripts/eval_mesh.py --render.
+ *   11 mesh evaluation (no existing signature changes): lasr_nn_tiled, lasr_chamfer3d_*, lasr_icp_* of scripts/eval_mesh.py --icp reference. */
+#define LASR_ABI_VERSION 11
 int         lasr_abi_version(void);
 const char* lasr_strerror(int code);
 int         lasr_last_hip_error(void);      /* hipError_t of the most recent LASR_E_LAUNCH on this thread */

@@ -96,6 +96,15 @@ SIGNATURES = {
     'lasr_vcn_flow_reg': (_i, [_p] * 4 + [_i] * 6 + [_p]),
     # lasr_amd/csrc/phong.hip
     'lasr_phong_shade': (_i, [_p] * 5 + [_i] * 4 + [_p]),
+    # lasr_amd/csrc/chamfer.hip
+    'lasr_chamfer3d_workspace_bytes': (_sz, [_i, _i, _i]),
+    'lasr_nn_tiled': (_i, [_p] * 7 + [_sz] + [_i] * 4 + [_p]),
+    'lasr_chamfer3d_forward': (_i, [_p] * 7 + [_sz] + [_i] * 4 + [_p]),
+    'lasr_chamfer3d_backward': (_i, [_p] * 12 + [_i] * 3 + [_p]),
+    'lasr_icp_workspace_bytes': (_sz, [_i, _i, _i]),
+    'lasr_icp_init': (_i, [_p] * 5 + [_sz] + [_i] * 3 + [_p]),
+    'lasr_icp_iterate': (_i, [_p] * 7 + [_sz] + [_i] * 4 + [ctypes.c_double, _i, _p]),
+    'lasr_icp_kabsch_host': (_i, [_p, _i, _p, _p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -145,11 +154,12 @@ SIGNATURES = {
     'lasr_prof_collect': (_i, [_p, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong)]),
 }
 
-ABI_VERSION = 10                                    # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
+ABI_VERSION = 11                                    # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
 # flags of the *_ex entry points (include/lasr_sr.h)
 SR_DEFAULT_FLAGS, SR_RELAXED_MATH, SR_SEGMENTED, SR_RECORDS_VALID, SR_GRADS_OVERWRITE = -1, 1, 2, 4, 8
 SR_PAIR_ONE_TEAM, SR_PAIR_TWO_TEAMS = 16, 32          # forward: teams of four waves per tile of the pair-walk kernel (default: by launch size)
 MEANS_MAX_TERMS, TAIL_MAX_GROUPS = 24, 16          # LASR_MEANS_MAX_TERMS / LASR_TAIL_MAX_GROUPS of include/lasr_ops.h
+NN_TILE, ICP_MAX_BATCH, ICP_MAX_CHUNK = 512, 64, 4096   # LASR_NN_TILE / LASR_ICP_MAX_BATCH / LASR_ICP_MAX_CHUNK of include/lasr_ops.h
 
 
 

@@ -29,7 +29,9 @@ const char* const kKernelNames[K_NUM_KERNELS] = {
     "render_tables_flow_kernel", "raster_faces_kernel", "mesh_reg_kernel", "render_tables_fold_kernel", "lbs_backward_fold_kernel", "project_points_kernel", "pose_chain_kernel",
     "texture_atlas_kernel", "voxel_surface_kernel", "voxel_fill_kernel", "vis_shade_kernel", "kp_transfer_kernel",
     "kp_sample_kernel", "mf_pack_kernel", "mf_repair_kernel", "mf_count_kernel", "mf_scan_kernel", "mf_extract_kernel",
-    "mf_project_kernel", "mf_guard_kernel", "vcn_norm_kernel", "vcn_corr_proj_kernel", "vcn_flow_reg_kernel", "phong_shade_kernel"};
+    "mf_project_kernel", "mf_guard_kernel", "vcn_norm_kernel", "vcn_corr_proj_kernel", "vcn_flow_reg_kernel", "phong_shade_kernel",
+    "nn_tiled_kernel", "nn_fill_keys_kernel", "nn_unpack_kernel", "chamfer_backward_kernel", "icp_init_kernel", "icp_moments_kernel",
+    "icp_solve_kernel"};
 }  // namespace
 
 int lasr_launch_ok()

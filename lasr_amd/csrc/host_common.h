@@ -18,6 +18,7 @@ enum LasrKernelId {
     K_TEXTURE_ATLAS, K_VOXEL_SURFACE, K_VOXEL_FILL, K_VIS_SHADE, K_KP_TRANSFER, K_KP_SAMPLE,
     K_MF_PACK, K_MF_REPAIR, K_MF_COUNT, K_MF_SCAN, K_MF_EXTRACT, K_MF_PROJECT, K_MF_GUARD,
     K_VCN_NORM, K_VCN_CORR_PROJ, K_VCN_FLOW_REG, K_PHONG_SHADE,
+    K_NN_TILED, K_NN_FILL_KEYS, K_NN_UNPACK, K_CHAMFER_BACKWARD, K_ICP_INIT, K_ICP_MOMENTS, K_ICP_SOLVE,
     K_NUM_KERNELS
 };
 

@@ -32,6 +32,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lasr_amd import phong, vis                            # noqa: E402
 from lasr_amd.nnutils import fused_ops                     # noqa: E402
+from lasr_amd.nnutils.icp import iterative_closest_point  # noqa: E402
 from lasr_amd.nnutils.manifold import watertight           # noqa: E402
 from lasr_amd.soft_renderer.functional import load_obj      # noqa: E402
 
@@ -77,6 +78,9 @@ def icp(x, y, iters=100, tol=1e-7):
     return R, t
 
 
+_icp_fast = icp                                            # evaluate_pair's keyword `icp` hides the function's name there
+
+
 def chamfer(x, y):
     dx = fused_ops.nearest_point(x[None], y[None])[0].mean()
     dy = fused_ops.nearest_point(y[None], x[None])[0].mean()
@@ -94,17 +98,29 @@ def chamfer_with_normals(x, nx, y, ny):
     return float(dx.mean() + dy.mean()), float((1 - cos_x).mean() + (1 - cos_y).mean())
 
 
-def evaluate_pair(pred, gt, n=10000, seed=0, with_normals=False, aligned=None):
+def evaluate_pair(pred, gt, n=10000, seed=0, with_normals=False, aligned=None, icp='fast'):
     """pred, gt: (verts [V,3], faces [F,3]) on the GPU -> Chamfer distance after normalisation and ICP; with_normals: the pair
     (Chamfer distance, normal consistency = 1 - normal term) the reference prints per frame (:197).  aligned: a dict that receives
-    the normalised ground truth 'gt', the aligned prediction 'pred' and its evaluation sample 'sample' (with_normals only)."""
+    the normalised ground truth 'gt', the aligned prediction 'pred' and its evaluation sample 'sample' (with_normals only).
+    icp: 'fast', the 100-iteration icp() above, or 'reference', the reference's call (:156)
+    iterative_closest_point(X, Y, estimate_scale=False, max_iterations=10000) on the device-resident loop of lasr_amd/nnutils/icp.py;
+    aligned then also receives its 'icp_iterations' and 'icp_converged'."""
+    if icp not in ('fast', 'reference'):
+        raise ValueError("icp is 'fast' or 'reference', got %r" % (icp,))
     gen = torch.Generator(device=pred[0].device).manual_seed(seed)
     (xv, xf), (yv, yf) = pred, gt
     yv = yv - yv.mean(0, keepdim=True)
     yv = 10 * yv / diameter(sample_points(yv, yf, 4000, gen))
     xv = xv - xv.mean(0, keepdim=True)
     xv = 10 * xv / diameter(sample_points(xv, xf, 4000, gen))
-    R, t = icp(sample_points(xv, xf, n, gen), sample_points(yv, yf, n, gen))
+    xs, ys = sample_points(xv, xf, n, gen), sample_points(yv, yf, n, gen)
+    if icp == 'reference':
+        sol = iterative_closest_point(xs[None], ys[None], estimate_scale=False, max_iterations=10000)
+        R, t = sol.RTs.R[0], sol.RTs.T[0]
+        if aligned is not None:
+            aligned.update(icp_iterations=sol.iterations, icp_converged=sol.converged)
+    else:
+        R, t = _icp_fast(xs, ys)
     xv = xv @ R + t
     if not with_normals:
         return chamfer(sample_points(xv, xf, n, gen), sample_points(yv, yf, n, gen))
@@ -170,6 +186,9 @@ def parse_args(argv=None):
     ap.add_argument('--remesh', type=int, default=0, metavar='RESOLUTION',
                     help='re-mesh each prediction watertight at this resolution first (the reference: 10000); 0: as it is')
     ap.add_argument('--render', action='store_true', help='write gt-/pd-/cd-%%06d.png into --testdir and the --gif')
+    ap.add_argument('--icp', choices=('fast', 'reference'), default='fast',
+                    help="rigid alignment: 'fast', at most 100 iterations (default), or 'reference', the reference's "
+                         'iterative_closest_point(..., max_iterations=10000) with its RMSE stop test')
     ap.add_argument('--gif', default=os.path.join('tmp', 'output.gif'), help='the GIF --render writes (default tmp/output.gif)')
     args = ap.parse_args(argv)
     if args.remesh < 0:
@@ -183,24 +202,28 @@ def main(argv=None):
     gts = sorted(glob.glob('%s/*.obj' % args.gtdir))
     preds = sorted(glob.glob('%s/pred*.obj' % args.testdir)) or sorted(glob.glob('%s/*.obj' % args.testdir))
     assert len(gts) == len(preds) and gts, 'need the same number of predicted and ground-truth meshes'
-    cds, ncs, frames = [], [], []
+    cds, ncs, frames, its = [], [], [], []
     for i, (p, g) in enumerate(zip(preds, gts)):
         pm, gm = load_obj(p, device=dev), load_obj(g, device=dev)
         pm = (pm[0].float(), pm[1].long())
         if args.remesh > 0:
             pm = watertight(pm[0], pm[1], args.remesh)
-        al = {} if args.render else None
-        cd, nc = evaluate_pair(pm, (gm[0].float(), gm[1].long()), with_normals=True, aligned=al)
+        al = {} if args.render or args.icp == 'reference' else None
+        cd, nc = evaluate_pair(pm, (gm[0].float(), gm[1].long()), with_normals=True, aligned=al, icp=args.icp)
         if args.render:
             img = render_triplet((al['gt'], gm[1].long()), (al['pred'], pm[1]), al['sample'])
             write_renders(args.testdir, i, img)
             frames.append(img)
         cds.append(cd); ncs.append(nc)
+        if args.icp == 'reference':
+            its.append((al['icp_iterations'], al['icp_converged']))
         print('%04d: %.2f, %.2f' % (i, cd, nc))                       # the reference's line (:197): Chamfer, normal consistency
     print('ALL: %.2f, %.2f' % (np.mean(cds), np.mean(ncs)))
+    if args.icp == 'reference':
+        print('ICP iterations: %s%s' % (' '.join('%d' % k for k, _ in its), '' if all(c for _, c in its) else ' (not all converged)'))
     if args.render:
         write_gif(args.gif, frames)
-    main.normal_consistency = ncs
+    main.normal_consistency, main.icp_iterations = ncs, its
     return cds
 
 
