@@ -794,6 +794,67 @@ int lasr_tail_step(const void* table, const int* chunks, int n_chunks, double* p
 #define LASR_FILL_MAX_PLANES 16
 int lasr_fill_planes(float* dst, const float* values, int n_values, int N, long long plane_elems, void* hip_stream);
 
+/*
+ * ---- Training monitor: flow colour coding, epoch contact sheet, scalar ring (lasr_amd/csrc/flowvis.hip) --
+ * Statistics scratch: caller-owned device words that are ZERO before the first call; every call leaves them zero again (the last
+ * block of its second launch clears them), so one buffer serves any number of calls on one stream and no memset precedes a call.
+ *
+ * lasr_flow_to_image replaces flow_to_image / compute_color / make_color_wheel (third_party/ext_utils/flowlib.py:45-173), batched.
+ *   flow [B,H,W,C] fp32, C in {2, 3}, channels 0 and 1 read; mask NULL or [B,H,W] fp32: u = v = 0 where the mask is 0, before
+ *   anything else (gu[~mask] = 0 of nnutils/train_utils.py:307,311); out [B,H,W,3] uint8 RGB, 4-byte aligned;
+ *   stats_scratch: lasr_flow_to_image_scratch_bytes(B) bytes.
+ *   A sample with |u| or |v| > 1e7 counts as (0, 0) for the maximum and comes out black (flowlib.py:59-61, 77-78); so does a NaN
+ *   sample (the reference's maximum with a NaN is an accident of Python's max()).  Per image: maxrad = max sqrt(u^2+v^2);
+ *   (u, v) /= maxrad + 2.22e-16; rad = |(u, v)|; fk = (atan2(-v, -u)/pi + 1)/2 * 54 + 1; k0 = floor(fk), k1 = k0 + 1 (56 -> 1),
+ *   f = fk - k0; per channel col = (1 - f) wheel[k0-1]/255 + f wheel[k1-1]/255; rad <= 1: col = 1 - rad (1 - col), else
+ *   col *= 0.75; out = floor(255 col).  Two launches: per-image maximum (wave, LDS, one integer atomicMax per block on the
+ *   radius' bit pattern: order-independent), then the colours, four consecutive pixels per lane.
+ *   B == 0 or H * W == 0: LASR_OK, nothing launched.  LASR_E_BADARG: C not in {2, 3}, a negative size, B > 65535,
+ *   B H W > 2^29, flow / out / stats_scratch NULL, out not 4-byte aligned.
+ *
+ * lasr_monitor_sheet composes the images the reference logs once per epoch (nnutils/train_utils.py:303-329) as one
+ *   [3 IS, 3 IS, 3] uint8 sheet, tiles in row-major order: flowobs, flowrd (colour coded as above, masked by vis_mask),
+ *   flow_error (flow_err * vis_mask, min-max scaled to grey), mask (mask_pred, min-max), maskgt (mask_gt, min-max), part,
+ *   img1, img2, texture (floor(255 x) clipped to 0..255; part.ptr == NULL: a black tile).  Min-max scaling is
+ *   floor(255 (x - min) / (max - min)) clipped; a constant panel comes out 0, NaN samples take no part and come out 0.
+ *   Over the texture tile, for k < n_ctl in order: the pixels (row r, column c) with 1.5^2 <= (c - cx)^2 + (r - cy)^2 <= 4.5^2,
+ *   (cx, cy) = IS/2 + IS/2 * ctl[k * ctl_stride + {0, 1}], take floor(palette[3k + {0,1,2}]) (palette in 0..255); this stands in
+ *   for cv2.circle(centre, 3, colour, 3) of :328.  Every plane is described by (ptr, chan_stride, pix_stride) in floats: channel c
+ *   of pixel i = r * IS + c is ptr[c * chan_stride + i * pix_stride], so planar and interleaved tensors and views need no copy.
+ *   One statistics launch (two maximum radii, three min / max pairs) and one compose launch.
+ *   stats_scratch: lasr_monitor_sheet_scratch_bytes() bytes.  IS == 0: LASR_OK.  LASR_E_BADARG: IS < 0 or > LASR_SHEET_MAX_SIZE,
+ *   a NULL plane other than part, out not 4-byte aligned, n_ctl < 0, n_ctl > 0 with ctl or palette NULL or ctl_stride < 2.
+ *
+ * lasr_scalar_ring_push replaces the per-step log.add_scalar(x.mean()) calls of nnutils/train_utils.py:330-344 (each a host
+ *   synchronisation there).  table: K rows of two int64 on the device {address of fp32 values, count}; writes
+ *   ring[(*head % capacity) * K + k] = mean of row k's values (NaN for a NULL address or count <= 0), then *head += 1.
+ *   One launch of one block; lane l of a wave adds elements l, l + 64, ... in order and the 64 partial sums fold through a fixed
+ *   butterfly: no float atomics, the same bits every time.  The host reads nothing: it drains the ring with a plain device-to-host
+ *   copy of lasr_scalar_ring_bytes(capacity, K) bytes.  K == 0: LASR_OK.  LASR_E_BADARG: K < 0 or > LASR_RING_MAX_SCALARS,
+ *   capacity < 1, a NULL pointer.  lasr_scalar_ring_bytes returns 0 for sizes the push refuses.
+ */
+#define LASR_SHEET_MAX_SIZE 4096
+#define LASR_RING_MAX_SCALARS 256
+typedef struct lasr_sheet_plane {
+    const float* ptr;
+    long long chan_stride;
+    long long pix_stride;
+} lasr_sheet_plane;
+typedef struct lasr_sheet_inputs {
+    lasr_sheet_plane flow_obs, flow_rd, vis_mask, flow_err, mask_pred, mask_gt, part, img1, img2, texture;
+    const float* ctl;        /* [n_ctl, ctl_stride]: projected bone centres, x and y in NDC (-1 .. 1) */
+    const float* palette;    /* [n_ctl, 3] ring colours, 0..255 */
+    int n_ctl;
+    int ctl_stride;
+} lasr_sheet_inputs;
+size_t lasr_flow_to_image_scratch_bytes(int B);      /* 0 for B < 0 */
+int lasr_flow_to_image(const float* flow, const float* mask, unsigned char* out, void* stats_scratch, int B, int H, int W, int C,
+                       void* hip_stream);
+size_t lasr_monitor_sheet_scratch_bytes(void);
+int lasr_monitor_sheet(const lasr_sheet_inputs* in, unsigned char* out, void* stats_scratch, int IS, void* hip_stream);
+size_t lasr_scalar_ring_bytes(int capacity, int K);
+int lasr_scalar_ring_push(const void* table, int K, float* ring, unsigned* head, int capacity, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

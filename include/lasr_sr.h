@@ -60,8 +60,10 @@ extern "C" {
  *   8  watertight re-meshing (no existing signature changes): lasr_manifold_* of scripts/manifold.py.
  *   9  optical-flow preprocessing (no existing signature changes): lasr_vcn_corr_proj*, lasr_vcn_flow_reg of preprocess/auto_gen.py.
  *   10 diagnostic renders (no existing signature changes): lasr_phong_shade of extract.py --render, scripts/eval_mesh.py --render.
- *   11 mesh evaluation (no existing signature changes): lasr_nn_tiled, lasr_chamfer3d_*, lasr_icp_* of scripts/eval_mesh.py --icp reference. */
-#define LASR_ABI_VERSION 11
+ *   11 mesh evaluation (no existing signature changes): lasr_nn_tiled, lasr_chamfer3d_*, lasr_icp_* of scripts/eval_mesh.py --icp reference.
+ *   12 training monitor (no existing signature changes): lasr_flow_to_image, lasr_monitor_sheet, lasr_scalar_ring_push and their size
+ *      queries (optimize.py --monitor, scripts/render_syn.py --flowvis). */
+#define LASR_ABI_VERSION 12
 int         lasr_abi_version(void);
 const char* lasr_strerror(int code);
 int         lasr_last_hip_error(void);      /* hipError_t of the most recent LASR_E_LAUNCH on this thread */

@@ -105,6 +105,13 @@ SIGNATURES = {
     'lasr_icp_init': (_i, [_p] * 5 + [_sz] + [_i] * 3 + [_p]),
     'lasr_icp_iterate': (_i, [_p] * 7 + [_sz] + [_i] * 4 + [ctypes.c_double, _i, _p]),
     'lasr_icp_kabsch_host': (_i, [_p, _i, _p, _p]),
+    # lasr_amd/csrc/flowvis.hip
+    'lasr_flow_to_image_scratch_bytes': (_sz, [_i]),
+    'lasr_flow_to_image': (_i, [_p] * 4 + [_i] * 4 + [_p]),
+    'lasr_monitor_sheet_scratch_bytes': (_sz, []),
+    'lasr_monitor_sheet': (_i, [_p, _p, _p, _i, _p]),
+    'lasr_scalar_ring_bytes': (_sz, [_i, _i]),
+    'lasr_scalar_ring_push': (_i, [_p, _i, _p, _p, _i, _p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -154,12 +161,13 @@ SIGNATURES = {
     'lasr_prof_collect': (_i, [_p, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong)]),
 }
 
-ABI_VERSION = 11                                    # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
+ABI_VERSION = 12                                    # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
 # flags of the *_ex entry points (include/lasr_sr.h)
 SR_DEFAULT_FLAGS, SR_RELAXED_MATH, SR_SEGMENTED, SR_RECORDS_VALID, SR_GRADS_OVERWRITE = -1, 1, 2, 4, 8
 SR_PAIR_ONE_TEAM, SR_PAIR_TWO_TEAMS = 16, 32          # forward: teams of four waves per tile of the pair-walk kernel (default: by launch size)
 MEANS_MAX_TERMS, TAIL_MAX_GROUPS = 24, 16          # LASR_MEANS_MAX_TERMS / LASR_TAIL_MAX_GROUPS of include/lasr_ops.h
 NN_TILE, ICP_MAX_BATCH, ICP_MAX_CHUNK = 512, 64, 4096   # LASR_NN_TILE / LASR_ICP_MAX_BATCH / LASR_ICP_MAX_CHUNK of include/lasr_ops.h
+SHEET_MAX_SIZE, RING_MAX_SCALARS = 4096, 256            # LASR_SHEET_MAX_SIZE / LASR_RING_MAX_SCALARS of include/lasr_ops.h
 
 
 
@@ -174,6 +182,17 @@ class VisParams(ctypes.Structure):
     """lasr_vis_params (include/lasr_ops.h): light frame, shading constants and output options of lasr_vis_shade."""
     _fields_ = [('light_u', _f * 3), ('light_v', _f * 3), ('light_d', _f * 3), ('k_ambient', _f), ('k_diffuse', _f),
                 ('surface_alpha', _f), ('shadow_bias', _f), ('background', _f * 3), ('smooth', _i), ('overlay', _i)]
+
+
+class SheetPlane(ctypes.Structure):
+    """lasr_sheet_plane (include/lasr_ops.h): channel c of pixel i is ptr[c * chan_stride + i * pix_stride] (strides in floats)."""
+    _fields_ = [('ptr', _p), ('chan_stride', ctypes.c_longlong), ('pix_stride', ctypes.c_longlong)]
+
+
+class SheetInputs(ctypes.Structure):
+    """lasr_sheet_inputs (include/lasr_ops.h): the device tensors behind the nine panels of lasr_monitor_sheet."""
+    _fields_ = [(n, SheetPlane) for n in ('flow_obs', 'flow_rd', 'vis_mask', 'flow_err', 'mask_pred', 'mask_gt', 'part', 'img1',
+                                          'img2', 'texture')] + [('ctl', _p), ('palette', _p), ('n_ctl', _i), ('ctl_stride', _i)]
 
 
 _lib = None

@@ -31,7 +31,8 @@ const char* const kKernelNames[K_NUM_KERNELS] = {
     "kp_sample_kernel", "mf_pack_kernel", "mf_repair_kernel", "mf_count_kernel", "mf_scan_kernel", "mf_extract_kernel",
     "mf_project_kernel", "mf_guard_kernel", "vcn_norm_kernel", "vcn_corr_proj_kernel", "vcn_flow_reg_kernel", "phong_shade_kernel",
     "nn_tiled_kernel", "nn_fill_keys_kernel", "nn_unpack_kernel", "chamfer_backward_kernel", "icp_init_kernel", "icp_moments_kernel",
-    "icp_solve_kernel"};
+    "icp_solve_kernel", "flow_maxrad_kernel", "flow_colour_kernel", "sheet_stats_kernel", "sheet_compose_kernel",
+    "scalar_ring_push_kernel"};
 }  // namespace
 
 int lasr_launch_ok()

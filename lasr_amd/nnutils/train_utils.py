@@ -552,12 +552,22 @@ class LASRTrainer:
             for t in (m.ctl_ts, m.rest_ts, m.ctl_rs, m.log_ctl):
                 dist.broadcast(t.data, 0)
 
+    def _monitor(self):
+        """--monitor: the contact sheets and scalars.csv of lasr_amd/nnutils/monitor.py, on rank 0; None without the flag."""
+        opts = self.opts
+        if not getattr(opts, 'monitor', False) or self.rank != 0:
+            return None
+        from . import monitor
+        mdir = getattr(opts, 'monitor_dir', '') or os.path.join(self.save_dir, 'monitor')
+        return monitor.TrainMonitor(mdir, opts, self.device)
+
     def train(self):
         opts, m = self.opts, self.module
         total_steps = 0
         torch.manual_seed(8)
         self.epoch_nscore = torch.zeros(opts.n_hypo, device=self.device)
         self.model.train()
+        mon = self._monitor()
         for epoch in range(opts.num_epochs):
             m.epoch = epoch
             if epoch == 0:
@@ -573,6 +583,12 @@ class LASRTrainer:
                 if i > 100 or len(self.dataloader) <= 101:
                     self.epoch_nscore += aux['current_nscore'].detach()
                 total_steps += 1
+                if mon is not None:                           # nnutils/train_utils.py:301-344, without its host reads
+                    if i == 0:
+                        mon.images(epoch, m, aux, m.optim_idx)
+                    mon.push(aux, self, total_steps)
+            if mon is not None:
+                mon.flush()
             if self.distributed:                              # keep hypothesis selection identical on all ranks
                 dist.all_reduce(self.epoch_nscore)
             skipped = self.skipped_steps()                    # steps whose gradients held a NaN and were zeroed (:289-290)

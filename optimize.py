@@ -42,7 +42,11 @@ DEFAULTS = dict(
     # overlap_allreduce: under torch.distributed with --use_graph, cut the captured backward at the encoder's layer-3 output and
     # all-reduce the gradients that exist by then while the rest of the backward replays (--nooverlap_allreduce: one message
     # after the whole replay)
-    overlap_allreduce=True)
+    overlap_allreduce=True,
+    # monitor: once per epoch a 3 x 3 contact sheet of the reference's tensorboard images (monitor_dir/epoch-%04d.png), every step
+    # the loss and gradient-norm scalars into monitor_dir/scalars.csv, all composed on the device (lasr_amd/nnutils/monitor.py);
+    # monitor_dir '' = <checkpoint_dir>/<name>/monitor
+    monitor=False, monitor_dir='')
 
 
 def parse_flags(argv, defaults=DEFAULTS):

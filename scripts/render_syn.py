@@ -9,6 +9,7 @@ rendered with the hard rasteriser (lasr_sr_forward: hard distance / hard z-buffe
   .../Annotations/.../%05d.png        128 * silhouette
   .../Camera/.../%05d.txt             focal, tx, ty, quaternion (w, x, y, z), depth
   .../FlowFW|FlowBW/.../flo-%05d.pfm  flow to the next / previous frame in pixels + validity; occ-%05d.pfm = -1
+  .../FlowFW|FlowBW/.../col-%05d.jpg  with --flowvis: the flow in Middlebury colours (lasr_amd/ext_utils/flowlib.py)
   <root>/configs/<outdir>.config      the [data] section optimize.py --dataname <outdir> reads
 The reference renders database/misc/spot/spot_triangulated.obj with its surface texture (pass it with --obj ... --surface_tex
 where a copy of that model is at hand; it is not shipped here); the default object
@@ -27,7 +28,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lasr_amd import soft_renderer as sr          # noqa: E402
 from lasr_amd import synth                        # noqa: E402
-from lasr_amd.ext_utils import util_flow          # noqa: E402
+from lasr_amd.ext_utils import flowlib, util_flow  # noqa: E402
 
 
 def rotmat_to_quat(m):
@@ -82,6 +83,8 @@ def main(argv=None):
     ap.add_argument('--surface_tex', action='store_true',
                     help='texture the object from an atlas image through per-face 5x5 surface textures, the way the '
                          'reference renders its textured .obj (render_syn.py:71: texture_res=5, texture_type=surface)')
+    ap.add_argument('--flowvis', action='store_true',
+                    help='also write the Middlebury-coloured flow pictures FlowFW|FlowBW/.../col-%%05d.jpg (render_syn.py:217-218)')
     args = ap.parse_args(argv)
     dev = torch.device('cuda', 0)
     size, dframe, focal, depth = args.img_size, 1, 10.0, 10.0
@@ -167,6 +170,8 @@ def main(argv=None):
             px = np.concatenate([px, 1 - bg[0].float().cpu().numpy()[:, :, None]], -1).astype(np.float32)
             util_flow.write_pfm(os.path.join(sub[name], 'flo-%05d.pfm' % idx), px)
             util_flow.write_pfm(os.path.join(sub[name], 'occ-%05d.pfm' % idx), occ)
+            if args.flowvis:
+                Image.fromarray(flowlib.flow_to_image(px)).save(os.path.join(sub[name], 'col-%05d.jpg' % idx), quality=95)
 
     os.makedirs(os.path.join(args.root, 'configs'), exist_ok=True)
     with open(os.path.join(args.root, 'configs', '%s.config' % args.outdir), 'w') as fh:
