@@ -12,13 +12,17 @@
 //            projects to is ONE run-time offset, not three exec-masked code variants), the obtuse-corner test's operands
 //            precomputed -- at an odd quad stride, so that 16 lanes reading the same quad of 16 different entries hit 16
 //            different bank groups;
-//   classify (wave-uniform entry, lanes = the wave's 8x8 pixels, record by LDS broadcast): exact integer rect test, barycentrics,
-//            then one bit per (pixel, entry) in one of three per-lane 64-bit masks: INSIDE the face, OUTSIDE but not certainly
-//            beyond the distance threshold (the backward's conservative line-distance reject, sr_device.h: certainly_far), or
-//            SLOW (a record that is not tame: handled by the generic arithmetic, wave-uniform, at the end of the chunk);
-//   balance  the lanes are ranked by their pair count (six ballots) and lane of rank r is partnered with rank 63 - r: the lighter
-//            partner takes the upper half of the difference from the heavier one's outside mask and folds it into a private
-//            partial state;
+//   classify (lanes = four rows of the tile, 16 pixels each; entry PER LANE) the chunk's rect ballots give every lane its candidate
+//            mask -- the entries whose exact integer pixel rect holds its pixel -- and each lane pops its own candidates: record
+//            gathered from LDS, barycentrics, then one bit per (pixel, entry) in one of three per-lane 64-bit masks: INSIDE the
+//            face, OUTSIDE but not certainly beyond the distance threshold (the backward's conservative line-distance reject,
+//            sr_device.h: certainly_far), or SLOW (a record that is not tame: never popped, handled by the generic arithmetic,
+//            wave-uniform, at the end of the chunk).  The loop runs as long as its fullest lane, so the candidates are evened
+//            out first: lanes ranked by candidate count (six ballots), rank r partnered with rank 63 - r, the lighter partner
+//            classifies the upper half of the difference at the heavier one's pixel centre and hands the result masks back
+//            (the same instructions on the same operands: no mask bit changes);
+//   balance  the lanes are ranked again, by their pair count, and partnered the same way: the lighter partner takes the upper
+//            half of the difference from the heavier one's outside mask and folds it into a private partial state;
 //   walk     every lane pops its own masks, inside pairs first, gathers the entry's record from LDS with 16-byte reads and applies
 //            the pair with the arithmetic of forward_face.  Inside and outside pixels share ONE clamped edge projection: an inside
 //            pixel's nearest edge line follows from the three products w_k^2 hk2_k (sr_device.h: euclid_one); only where two
@@ -342,6 +346,35 @@ __device__ __forceinline__ void pair_apply(const RasterArgs& A, const UniRecip& 
     }
 }
 
+// The rank of this lane when the wave's lanes are sorted by k (0..63), heaviest first, ties by lane: six ballots.  A function of the
+// 64 counts alone.
+__device__ __forceinline__ int rank_of(int k)
+{
+    u64_t Gm = ~0ull;
+    int greater = 0;
+#pragma unroll
+    for (int b = 5; b >= 0; b--) {
+        const bool mine = (k >> b) & 1;
+        const u64_t B = wave_mask(mine);
+        const u64_t GB = Gm & B;
+        if (!mine) { greater += __popcll(GB); Gm ^= GB; }
+        else Gm = GB;
+    }
+    return greater + bits_below_lane(Gm);
+}
+
+// the bits of hm above the smallest position whose upper part holds at most `moved` bits (all of hm when it has no more than that)
+__device__ __forceinline__ u64_t upper_bits(u64_t hm, int moved)
+{
+    if (moved <= 0) return 0ull;
+    if (__popcll(hm) <= moved) return hm;
+    int p = 0;
+#pragma unroll
+    for (int sft = 32; sft >= 1; sft >>= 1)
+        if (p + sft <= 63 && __popcll(hm >> (p + sft)) > moved) p += sft;
+    return p >= 63 ? 0ull : (hm >> (p + 1)) << (p + 1);
+}
+
 template <int NCH, int SPLIT>
 __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict__ aggrs, float* __restrict__ colors, PairLds<NCH, SPLIT>& L)
 {
@@ -550,25 +583,74 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
             // beyond edge k's line; -inf for faces the conservative reject does not apply to)
             u64_t ms = cand & ~tame_mask, mi = 0, mo = 0;
             cand &= tame_mask;
-            // (no divergent region: a lane without candidates rides along on slot 63 with an empty bit)
-            if (wave_mask(cand != 0) != 0) do {
-                const int e = __builtin_ctzll(cand | (1ull << 63));
-                const u64_t rest = cand & (cand - 1), bit = cand ^ rest;
-                cand = rest;
-                const float* R = Lrec + e * RS;
-                const float4 q0 = ld4(R), q1 = ld4(R + 4);
-                const float inv8 = R[8];
-                const float4 q3 = ld4(R + PR_HK2);
-                // (unfused like the walk's: on an edge-on face the fused form moves the barycentrics by whole pixels, and which
-                // distance formula a pixel gets must be the reference's choice)
-                const float w0 = q0.x * xp + q0.y * yp + q0.z;                  // barycentric()
-                const float w1 = q0.w * xp + q1.x * yp + q1.y;
-                const float w2 = q1.z * xp + q1.w * yp + inv8;
-                const bool inside = (bool)((int)(fminf(fminf(w0, w1), w2) > 0) & (int)(fmaxf(fmaxf(w0, w1), w2) < 1));
-                const bool far = (bool)((int)(w0 < q3.x) | (int)(w1 < q3.y) | (int)(w2 < q3.z));
-                mi |= inside ? bit : 0ull;
-                mo |= (bool)((int)!inside & (int)!far) ? bit : 0ull;
-            } while (wave_mask(cand != 0) != 0);
+            if (wave_mask(cand != 0) != 0) {
+                // the loop below runs as long as the fullest lane, so the candidates are evened out first, like the walk's pairs:
+                // rank the lanes by their candidate count, partner rank r with rank 63 - r; the lighter partner takes the upper
+                // half of the difference out of the heavier one's mask, classifies those bits at the HEAVIER lane's pixel centre
+                // (same instructions on the same operands: every mask bit is what its own lane would have computed) and hands
+                // the two result masks back.  Lanes outside a ragged image have no candidates: they are light partners.
+                const int kmine = min((int)__popcll(cand), 63);
+                const int rank = rank_of(kmine);
+                const int id_at_rank = __builtin_amdgcn_ds_permute(rank << 2, lane);             // lane r: the lane of rank r
+                const int partner = __builtin_amdgcn_ds_bpermute((63 - rank) << 2, id_at_rank);
+                const int kpart = __builtin_amdgcn_ds_bpermute(partner << 2, kmine);
+                const unsigned pc_lo = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)cand);
+                const unsigned pc_hi = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)(cand >> 32));
+                const float xq = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(xp)));
+                const float yq = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(yp)));
+                const bool heavy = rank < 32;
+                const u64_t hm = heavy ? cand : ((u64_t)pc_hi << 32 | pc_lo);
+                const u64_t top = upper_bits(hm, (heavy ? kmine - kpart : kpart - kmine) >> 1);
+                u64_t st = 0;                           // light lane: the partner's candidates it classifies
+                if (heavy) cand ^= top;
+                else st = top;
+                const bool gave = (bool)((int)heavy & (int)(top != 0));
+                // ONE loop over a lane's own run and then the partner's share (a second loop would cost max(own) + max(stolen)
+                // iterations); results collect in ri / ro and are set aside where a lane changes over -- an own bit and a stolen
+                // bit may name the same entry.  No divergent region but the change-over: a lane without work rides along on
+                // slot 63 with an empty bit.
+                float cx = xp, cy = yp;
+                u64_t ri = 0, ro = 0, more_m = ~0ull;
+                bool in_stolen = false;
+                auto advance = [&]() {
+                    if ((wave_mask(cand == 0) & more_m) != 0) {
+                        if ((bool)((int)(cand == 0) & (int)(st != 0))) {
+                            mi = ri; mo = ro; ri = 0; ro = 0;
+                            cx = xq; cy = yq; cand = st; st = 0; in_stolen = true;
+                        }
+                        more_m = wave_mask(st != 0);
+                    }
+                };
+                advance();
+                do {
+                    const int e = __builtin_ctzll(cand | (1ull << 63));
+                    const u64_t rest = cand & (cand - 1), bit = cand ^ rest;
+                    cand = rest;
+                    const float* R = Lrec + e * RS;
+                    const float4 q0 = ld4(R), q1 = ld4(R + 4);
+                    const float inv8 = R[8];
+                    const float4 q3 = ld4(R + PR_HK2);
+                    // (unfused like the walk's: on an edge-on face the fused form moves the barycentrics by whole pixels, and which
+                    // distance formula a pixel gets must be the reference's choice)
+                    const float w0 = q0.x * cx + q0.y * cy + q0.z;                  // barycentric()
+                    const float w1 = q0.w * cx + q1.x * cy + q1.y;
+                    const float w2 = q1.z * cx + q1.w * cy + inv8;
+                    const bool inside = (bool)((int)(fminf(fminf(w0, w1), w2) > 0) & (int)(fmaxf(fmaxf(w0, w1), w2) < 1));
+                    const bool far = (bool)((int)(w0 < q3.x) | (int)(w1 < q3.y) | (int)(w2 < q3.z));
+                    ri |= inside ? bit : 0ull;
+                    ro |= (bool)((int)!inside & (int)!far) ? bit : 0ull;
+                    advance();
+                } while (wave_mask(cand != 0) != 0);
+                if (!in_stolen) { mi = ri; mo = ro; ri = 0; ro = 0; }
+                // the hand-back: the light lane's results for the taken subset go into the heavy lane's masks
+                if (wave_mask(gave) != 0) {
+                    const unsigned gi_lo = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)ri);
+                    const unsigned gi_hi = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)(ri >> 32));
+                    const unsigned go_lo = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)ro);
+                    const unsigned go_hi = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)(ro >> 32));
+                    if (gave) { mi |= (u64_t)gi_hi << 32 | gi_lo; mo |= (u64_t)go_hi << 32 | go_lo; }
+                }
+            }
 
 #if defined(LASR_PW_ABL) && LASR_PW_ABL == 1        // measurement build: no walk
             s.a += (float)(__popcll(mi) + 2 * __popcll(mo)); mi = mo = 0;
@@ -580,20 +662,7 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
 #endif
             // ---- balance: rank the lanes by their pair count (heaviest first), partner rank r with rank 63 - r
             const int kmine = min((int)__popcll(mi) + (int)__popcll(mo), 63);
-            int rank;
-            {
-                u64_t Gm = ~0ull;
-                int greater = 0;
-#pragma unroll
-                for (int b = 5; b >= 0; b--) {
-                    const bool mine = (kmine >> b) & 1;
-                    const u64_t B = wave_mask(mine);
-                    const u64_t GB = Gm & B;
-                    if (!mine) { greater += __popcll(GB); Gm ^= GB; }
-                    else Gm = GB;
-                }
-                rank = greater + bits_below_lane(Gm);
-            }
+            const int rank = rank_of(kmine);
             const int id_at_rank = __builtin_amdgcn_ds_permute(rank << 2, lane);                 // lane r: the lane of rank r
             const int partner = __builtin_amdgcn_ds_bpermute((63 - rank) << 2, id_at_rank);
             const int kpart = __builtin_amdgcn_ds_bpermute(partner << 2, kmine);
@@ -608,15 +677,7 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
             u64_t st = 0;                                                       // light lane: the pairs it takes over
             bool gave = false;
             if (moved > 0 && !no_steal) {
-                // smallest position whose upper part holds at most `moved` bits
-                int p = 0;
-                u64_t top = hm;
-                if (__popcll(hm) > moved) {
-#pragma unroll
-                    for (int sft = 32; sft >= 1; sft >>= 1)
-                        if (p + sft <= 63 && __popcll(hm >> (p + sft)) > moved) p += sft;
-                    top = p >= 63 ? 0ull : (hm >> (p + 1)) << (p + 1);
-                }
+                const u64_t top = upper_bits(hm, moved);
                 if (heavy) { mo ^= top; gave = top != 0; }
                 else st = top;
             }

@@ -1,8 +1,9 @@
 # Counts of (pixel, face) pairs on the bench workload (numpy model of the rect / inside / conservative-far tests): candidates, walked
-# pairs, and the wave iterations of the pair-walk kernel -- unbalanced, rank-paired (the kernel), synchronised over a tile, dense.
+# pairs, and the wave iterations of the pair-walk kernel's two per-lane loops (classification and walk) -- unbalanced, rank-paired
+# (the kernel), in quads, synchronised over a tile, dense.
 #   python tools/pair_stats.py
 import numpy as np, sys, math
-sys.path.insert(0,'/root/repo')
+import os; sys.path.insert(0,os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lasr_amd import synth
 import bench
 NU=bench.NU; IS=256
@@ -78,6 +79,10 @@ for fr in frames:
                 for w in range(4):
                     kk=(ci+co)[w::4].reshape(-1); cand=cc[w::4].reshape(-1)
                     srt=np.sort(kk)[::-1]
+                    # classification: candidates evened out between rank r and rank 63-r (the kernel), or over quads (r, 31-r, 32+r, 63-r)
+                    cs=np.sort(cand)[::-1]
+                    cbal=max(np.ceil((cs[i]+cs[63-i])/2) for i in range(32))
+                    cquad=max(np.ceil((cs[i]+cs[31-i]+cs[32+i]+cs[63-i])/4) for i in range(16))
                     bal=np.maximum.reduce([np.ceil((srt[i]+srt[63-i])/2) for i in range(32)])
                     # alternatives: a heavy lane shared by TWO light ones (21 triples + 1 leftover), quads (rank r, 31-r, 32+r, 63-r)
                     tri=max(max(np.ceil((srt[i]+srt[63-2*i]+srt[62-2*i])/3) for i in range(21)), srt[21])
@@ -93,7 +98,7 @@ for fr in frames:
                         dD=min(max(0,t-kD),pA); y=min(max(0,t-kC),pB); x=min(max(0,t-kB+y),pA-dD)
                         cur_quads=max(cur_quads, kA-dD-x, kD+dD, kB+x-y, kC+y)
                     ALT.append((tri, quad, np.ceil(kk.sum()/64), cur_pairs, cur_quads))
-                    row.append((kk.sum(),kk.max(),bal,cand.max(),cand.sum(),ci[w::4].max(),ci[w::4].sum()))
+                    row.append((kk.sum(),kk.max(),bal,cand.max(),cand.sum(),ci[w::4].max(),ci[w::4].sum(),cbal,cquad))
                 stats.append((len(ch),row))
 print(tot)
 st=stats
@@ -109,7 +114,7 @@ densew=sum(math.ceil(r[0]/64) for _,rows in st for r in rows)
 print('frames',len(frames),'chunks',nchunks,'entries',sum(n for n,_ in st))
 print('pairs',pairs,'wave-iters: unbalanced',M,'balanced',Mb,'tile-synced',Mt,'dense per wave',densew,'dense per tile',dense)
 print('walk iterations with triples', sum(a[0] for a in ALT), 'quads', sum(a[1] for a in ALT), 'dense', sum(a[2] for a in ALT), '| outside-only: pairs', sum(a[3] for a in ALT), 'quads', sum(a[4] for a in ALT))
-print('classify iters (max cand per wave)',Cm,'cand sum/64',Cs/64)
+print('classify iters (max cand per wave)',Cm,'balanced in pairs (the kernel)',int(sum(r[7] for _,rows in st for r in rows)),'in quads',int(sum(r[8] for _,rows in st for r in rows)),'cand sum/64',Cs/64)
 print('inside-mode iterations (max inside pairs per lane of a chunk-wave)',sum(r[5] for _,rows in st for r in rows),'inside pairs / 64',sum(r[6] for _,rows in st for r in rows)/64)
 import collections
 Ts=np.array([r[0] for _,rows in st for r in rows])
