@@ -855,6 +855,44 @@ int lasr_monitor_sheet(const lasr_sheet_inputs* in, unsigned char* out, void* st
 size_t lasr_scalar_ring_bytes(int capacity, int K);
 int lasr_scalar_ring_push(const void* table, int K, float* ring, unsigned* head, int capacity, void* hip_stream);
 
+/*
+ * ---- Texture baking of scripts/bake_texture.py (lasr_amd/csrc/bake.hip, lasr_amd/nnutils/bake.py) --------
+ * This project's own addition: the reference has no counterpart, nothing of it is restated here, and parity is to the float64
+ * restatement in tests/bake_restated.py only.  The pair fills the per-face surface textures [F, R*R, 3] the rasteriser samples
+ * (texture_type 'surface') from T video frames with one camera-space mesh each (shared faces); it stands in for the per-vertex
+ * colours that are otherwise the only appearance of a reconstruction.
+ *
+ * lasr_bake_accumulate stands in for a per-texel loop "project into every frame, test visibility, add the weighted colour":
+ *   verts  [T,V,3]      camera space, OpenCV axes (x right, y down, z forward)
+ *   faces  [F,3]        int32, shared by the frames; a face with an index outside [0, V) is left untouched
+ *   K      [T,4]        fx fy px py in pixels of the H x W frame (16-byte aligned)
+ *   raster [T,2,IS,IS]  hard-mode aggrs_info of lasr_sr_forward_bg (func_id_rgb = func_id_alpha = 0) under the NDC mapping
+ *                       sx = 2u/IS - 1, sy = 1 - 2v/IS: plane 1 names the nearest face of pixel (row floor(v), column floor(u)), or -1
+ *   frames [T,H,W,3]    uint8;  masks [T,H,W] uint8 or NULL
+ *   accum  [F,R*R,4]    fp32 (sum w r, sum w g, sum w b, sum w), 16-byte aligned; read, added to and written back, so the caller
+ *                       zeroes it once and may pass the frames of a sequence in any number of consecutive calls
+ *   Texel j = iy R + ix samples the centroid of the barycentric region surface_texel(c0, c1, R) maps to j:
+ *   ix + iy <= R-1: (c0, c1) = ((ix + 1/3)/R, (iy + 1/3)/R), else ((R-1-ix + 2/3)/R, (R-1-iy + 2/3)/R); c2 = 1 - c0 - c1, c_k weighs
+ *   corner k.  Per frame, in increasing order: P = c0 V0 + c1 V1 + c2 V2, skipped unless P.z > 0; u = fx P.x/P.z + px,
+ *   v = fy P.y/P.z + py (pixel (r, c) covers u in [c, c+1), v in [r, r+1)), skipped unless 0 <= u < W and 0 <= v < H; visible when
+ *   the raster names this face at (floor(v), floor(u)) and, with masks, the mask is > 0 at all four bilinear taps; colour = bilinear
+ *   sample of the frame at (u - 0.5, v - 0.5), taps clamped to the frame, / 255; w = |n . P/|P||^power with n the unit face normal
+ *   (power = 0: w = 1; a zero-area face: 0).  One thread per texel, no atomics: the same bits for any split of the frames.
+ * lasr_bake_resolve: textures [F,R*R,3] = accum.rgb / accum.w where accum.w > 0, else the fallback vertex colour [V,3] interpolated
+ *   at the texel's centroid (fallback NULL: 0.5 grey); weight [F,R*R] = accum.w.
+ * Checked on the host before any launch (LASR_E_BADARG): T >= 0, V >= 1, F >= 0, 1 <= R <= LASR_BAKE_MAX_RES,
+ *   1 <= H, W <= IS <= LASR_BAKE_MAX_SIZE, 0 <= power <= LASR_BAKE_MAX_POWER, 4 F R R <= INT_MAX; then T == 0 or F == 0 is LASR_OK
+ *   with nothing launched; then every pointer but masks / fallback non-NULL.  Device contents are not read on the host.
+ */
+#define LASR_BAKE_MAX_RES 32
+#define LASR_BAKE_MAX_SIZE 8192
+#define LASR_BAKE_MAX_POWER 16
+int lasr_bake_accumulate(const float* verts, const int* faces, const float* K, const float* raster, const unsigned char* frames,
+                         const unsigned char* masks, float* accum, int T, int V, int F, int R, int IS, int H, int W, int power,
+                         void* hip_stream);
+int lasr_bake_resolve(const float* accum, const int* faces, const float* fallback, float* textures, float* weight, int V, int F,
+                      int R, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,8 +62,9 @@ extern "C" {
  *   10 diagnostic renders (no existing signature changes): lasr_phong_shade of extract.py --render, scripts/eval_mesh.py --render.
  *   11 mesh evaluation (no existing signature changes): lasr_nn_tiled, lasr_chamfer3d_*, lasr_icp_* of scripts/eval_mesh.py --icp reference.
  *   12 training monitor (no existing signature changes): lasr_flow_to_image, lasr_monitor_sheet, lasr_scalar_ring_push and their size
- *      queries (optimize.py --monitor, scripts/render_syn.py --flowvis). */
-#define LASR_ABI_VERSION 12
+ *      queries (optimize.py --monitor, scripts/render_syn.py --flowvis).
+ *   13 texture baking (no existing signature changes): lasr_bake_accumulate, lasr_bake_resolve of scripts/bake_texture.py. */
+#define LASR_ABI_VERSION 13
 int         lasr_abi_version(void);
 const char* lasr_strerror(int code);
 int         lasr_last_hip_error(void);      /* hipError_t of the most recent LASR_E_LAUNCH on this thread */

@@ -112,6 +112,9 @@ SIGNATURES = {
     'lasr_monitor_sheet': (_i, [_p, _p, _p, _i, _p]),
     'lasr_scalar_ring_bytes': (_sz, [_i, _i]),
     'lasr_scalar_ring_push': (_i, [_p, _i, _p, _p, _i, _p]),
+    # lasr_amd/csrc/bake.hip
+    'lasr_bake_accumulate': (_i, [_p] * 7 + [_i] * 8 + [_p]),
+    'lasr_bake_resolve': (_i, [_p] * 5 + [_i] * 3 + [_p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -161,13 +164,14 @@ SIGNATURES = {
     'lasr_prof_collect': (_i, [_p, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_longlong)]),
 }
 
-ABI_VERSION = 12                                    # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
+ABI_VERSION = 13                                    # LASR_ABI_VERSION of include/lasr_sr.h (tests/test_abi.py compares them)
 # flags of the *_ex entry points (include/lasr_sr.h)
 SR_DEFAULT_FLAGS, SR_RELAXED_MATH, SR_SEGMENTED, SR_RECORDS_VALID, SR_GRADS_OVERWRITE = -1, 1, 2, 4, 8
 SR_PAIR_ONE_TEAM, SR_PAIR_TWO_TEAMS = 16, 32          # forward: teams of four waves per tile of the pair-walk kernel (default: by launch size)
 MEANS_MAX_TERMS, TAIL_MAX_GROUPS = 24, 16          # LASR_MEANS_MAX_TERMS / LASR_TAIL_MAX_GROUPS of include/lasr_ops.h
 NN_TILE, ICP_MAX_BATCH, ICP_MAX_CHUNK = 512, 64, 4096   # LASR_NN_TILE / LASR_ICP_MAX_BATCH / LASR_ICP_MAX_CHUNK of include/lasr_ops.h
 SHEET_MAX_SIZE, RING_MAX_SCALARS = 4096, 256            # LASR_SHEET_MAX_SIZE / LASR_RING_MAX_SCALARS of include/lasr_ops.h
+BAKE_MAX_RES, BAKE_MAX_SIZE, BAKE_MAX_POWER = 32, 8192, 16   # LASR_BAKE_MAX_RES / LASR_BAKE_MAX_SIZE / LASR_BAKE_MAX_POWER of include/lasr_ops.h
 
 
 

@@ -32,7 +32,7 @@ const char* const kKernelNames[K_NUM_KERNELS] = {
     "mf_project_kernel", "mf_guard_kernel", "vcn_norm_kernel", "vcn_corr_proj_kernel", "vcn_flow_reg_kernel", "phong_shade_kernel",
     "nn_tiled_kernel", "nn_fill_keys_kernel", "nn_unpack_kernel", "chamfer_backward_kernel", "icp_init_kernel", "icp_moments_kernel",
     "icp_solve_kernel", "flow_maxrad_kernel", "flow_colour_kernel", "sheet_stats_kernel", "sheet_compose_kernel",
-    "scalar_ring_push_kernel"};
+    "scalar_ring_push_kernel", "bake_accumulate_kernel", "bake_resolve_kernel"};
 }  // namespace
 
 int lasr_launch_ok()

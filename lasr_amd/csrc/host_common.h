@@ -20,6 +20,7 @@ enum LasrKernelId {
     K_VCN_NORM, K_VCN_CORR_PROJ, K_VCN_FLOW_REG, K_PHONG_SHADE,
     K_NN_TILED, K_NN_FILL_KEYS, K_NN_UNPACK, K_CHAMFER_BACKWARD, K_ICP_INIT, K_ICP_MOMENTS, K_ICP_SOLVE,
     K_FLOW_MAXRAD, K_FLOW_COLOUR, K_SHEET_STATS, K_SHEET_COMPOSE, K_SCALAR_RING_PUSH,
+    K_BAKE_ACCUMULATE, K_BAKE_RESOLVE,
     K_NUM_KERNELS
 };
 

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""Bake a texture atlas from the video frames onto the meshes extract.py wrote (this project's own addition; the reference has
+no counterpart -- DESIGN.md section 4.11).
+
+    python scripts/bake_texture.py --testdir log/camel-5/ --seqname camel \\
+        [--texture_res 8] [--power 2] [--pose_frame 0] [--no_mask] [--outpath DIR/baked] [--preview out.gif]
+
+Reads what render_vis.py reads: the frames of configs/<seqname>.config, per frame id i <testdir>/pred<i>.ply (or .obj) in camera
+space and the intrinsics row of cam<i>.txt, and the silhouettes of the matching Annotations folder.  Every texel of the per-face
+surface textures is averaged over the frames that see it (lasr_amd/nnutils/bake.py, csrc/bake.hip); texels no frame sees take
+the mesh's vertex colours.  Writes <outpath>.obj / .mtl / .png (the mesh of --pose_frame with the atlas) and <outpath>_weight.npy,
+and with --preview a GIF of the baked mesh rendered back into every frame's camera beside the video frame.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description='Bake the video frames onto the reconstructed meshes as a texture atlas.')
+    p.add_argument('--testdir', default='', help='directory holding pred<i>.ply / .obj and cam<i>.txt')
+    p.add_argument('--seqname', default='camel', help='sequence name: its frames are listed by configs/<seqname>.config')
+    p.add_argument('--texture_res', default=8, type=int, help='texels per face edge: each face gets R x R texels')
+    p.add_argument('--power', default=2, type=int, help='exponent of the view weight |n . d|^power (0: plain mean)')
+    p.add_argument('--pose_frame', default=0, type=int, help='position in the frame list of the mesh the .obj is written for')
+    p.add_argument('--no_mask', dest='mask', action='store_false', help='do not restrict the samples to the silhouettes')
+    p.add_argument('--outpath', default='', help='output path without extension (default: <testdir>/baked)')
+    p.add_argument('--preview', default='', help='GIF to write: the baked mesh in every frame\'s camera, beside the frame')
+    return p.parse_args(argv)
+
+
+def check_topology(faces_list, frame_ids):
+    """Every pred<i> must share the faces of the first, as scripts/eval_badja.py:load_meshes requires."""
+    first = np.asarray(faces_list[0])
+    for fr, f in zip(frame_ids[1:], faces_list[1:]):
+        f = np.asarray(f)
+        if f.shape != first.shape or (f != first).any():
+            raise ValueError('pred%d does not share the topology of pred%d' % (fr, frame_ids[0]))
+    return first
+
+
+def silhouette_path(frame_path):
+    """.../JPEGImages/<res>/<seq>/00000.jpg -> .../Annotations/<res>/<seq>/00000.png (the layout of lasr_amd/dataloader/vid.py)."""
+    return frame_path.replace('JPEGImages', 'Annotations').replace('.jpg', '.png')
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from PIL import Image
+    import render_vis
+    from lasr_amd.nnutils import bake
+    from lasr_amd.soft_renderer.functional import save_obj
+    dev = torch.device('cuda', 0)
+    names = render_vis.frame_list(args.seqname)
+    if not names:
+        raise SystemExit('bake_texture.py: no frames for sequence %s' % args.seqname)
+    if not 0 <= args.pose_frame < len(names):
+        raise SystemExit('bake_texture.py: --pose_frame %d is outside the %d frames' % (args.pose_frame, len(names)))
+    if args.texture_res < 2:
+        raise SystemExit('bake_texture.py: --texture_res must be at least 2 (the atlas writer needs it)')
+    imgs, sils, verts, faces, colors, cams, ids = [], [], [], [], [], [], []
+    for name in names:
+        fr = int(os.path.basename(name).split('.')[-2])
+        imgs.append(np.asarray(Image.open(name).convert('RGB')))
+        try:
+            v, f, c = render_vis.load_mesh(args.testdir, fr)
+            cams.append(np.loadtxt(os.path.join(args.testdir, 'cam%d.txt' % fr)))
+        except (OSError, ValueError) as e:
+            raise SystemExit('bake_texture.py: no mesh for frame %d in %s (%s)' % (fr, args.testdir, e))
+        verts.append(v), faces.append(f.numpy()), colors.append(c), ids.append(fr)
+        if args.mask:
+            try:
+                sils.append(np.asarray(Image.open(silhouette_path(name)).convert('L')))
+            except OSError as e:
+                raise SystemExit('bake_texture.py: no silhouette for %s (%s); pass --no_mask to bake without' % (name, e))
+    try:
+        face = check_topology(faces, ids)
+    except ValueError as e:
+        raise SystemExit('bake_texture.py: %s' % e)
+    H, W = imgs[0].shape[:2]
+    R = args.texture_res
+    tv = torch.stack(verts).to(dev)
+    tf = torch.from_numpy(face).to(dev)
+    tK = torch.tensor(np.stack([c[3] for c in cams]), dtype=torch.float32, device=dev)
+    frames = torch.from_numpy(np.stack(imgs)).to(dev)
+    masks = torch.from_numpy(np.stack(sils)).to(dev) if args.mask else None
+    fallback = colors[args.pose_frame].to(dev).float() / 255.
+    with torch.no_grad():
+        textures, weight = bake.bake_texture(tv, tf, tK, frames, masks, texture_res=R, power=args.power, fallback=fallback)
+    out = args.outpath or os.path.join(args.testdir, 'baked')
+    if os.path.dirname(out):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+    save_obj(out + '.obj', verts[args.pose_frame], torch.from_numpy(face), textures, R, 'surface')
+    w = weight.cpu().numpy()
+    np.save(out + '_weight.npy', w)
+    print('baked %d faces x %d texels, seen %.1f %%' % (face.shape[0], R * R, 100. * float((w > 0).mean())))
+
+    if args.preview:
+        pil = []                                       # native size, no resampling: the video frame left, the render right
+        with torch.no_grad():
+            for i in range(0, len(names), bake.CHUNK_FRAMES):
+                j = min(i + bake.CHUNK_FRAMES, len(names))
+                rgba = bake.render_baked(tv[i:j], tf, tK[i:j], textures, H, W)
+                rgb = (rgba[:, :3].clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1)
+                pair = torch.cat([frames[i:j], rgb], 2)
+                pil += [Image.fromarray(p) for p in pair.cpu().numpy()]
+        pil[0].save(args.preview, save_all=True, append_images=pil[1:], duration=5000. / len(pil), loop=0)
+        print('wrote %d frames to %s' % (len(pil), args.preview))
+    return textures, weight
+
+
+if __name__ == '__main__':
+    main()
