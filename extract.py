@@ -18,6 +18,10 @@ over it, and the front, right and top views of the shaded mesh: lasr_amd/phong.p
 vp3pred<i>.ply, bone<i>.ply and, with n_bones > 1, renderskin-%05d.png (one soft-renderer render of every bone's skinning weight)
 and, at the sequence's canonical frame, clusters.obj, cpoints.ply and skin.npy.  Part colours come from this project's palette
 (lasr_amd/synth.py:label_palette), not the reference's Cityscapes table.
+
+--rig (off by default; without it every output is what it was) adds rig.npz: the rest mesh, vertex colours, the dense skin and the
+per-frame transform of every bone of the exported hypothesis, from which scripts/export_gltf.py writes a skinned, animated .glb
+(this project's own addition).
 """
 import os
 import sys
@@ -204,8 +208,30 @@ def write_renders(tr, out_dir, rv, k, fid, colors, panels):
             np.save(os.path.join(out_dir, 'skin.npy'), skin.cpu().numpy())
 
 
-def export(tr, out_dir, render=False, panels=None):
-    """-> {frame id: obj path}"""
+def rig_batch(tr, n, best):
+    """What --rig keeps of one forward, for hypothesis `best` of the n images of the batch: the mean shape _skinning and
+    obj_to_cam receive [V,3], the skin [J,V] (J = 0 without part bones) and _cam_src's transforms R [n,K,3,3], T [n,K,3]
+    (row vectors: p_cam = (sum_k w_k (p R_k + T_k)) R_0 + T_0; bone 0 the body, the parts after the bone fix-up)."""
+    m = tr.module
+    H, K = tr.opts.n_hypo, tr.opts.n_bones
+    mean_v = m.get_mean_shape(n // 2)[0]
+    rest = mean_v.view(n, H, -1, 3)[0, best]
+    skin = m._skinning(mean_v, n)[best, :, :, 0] if K > 1 else rest.new_zeros(0, rest.shape[0])
+    Rmat, Tmat = m._cam_src[0], m._cam_src[1]
+    return rest, skin, Rmat.view(n, H, K, 3, 3)[:, best], Tmat.view(n, H, K, 3)[:, best]
+
+
+def write_rig(path, tr, rig, tex):
+    """rig.npz (the input of scripts/export_gltf.py): rig = dict(rest, skin, frames {frame id: (R [K,3,3], T [K,3], fx fy px py)})."""
+    ids = sorted(rig['frames'])
+    R, T, intr = (np.stack([rig['frames'][i][j] for i in ids]) for j in range(3))
+    np.savez(path, rest_verts=rig['rest'].cpu().numpy().astype(np.float32), faces=tr.module.faces.cpu().numpy().astype(np.int32),
+             colors=tex.cpu().numpy().astype(np.float32), skin=rig['skin'].cpu().numpy().astype(np.float32),
+             frame_ids=np.asarray(ids, np.int64), R=R.astype(np.float32), T=T.astype(np.float32), intrinsics=intr.astype(np.float32))
+
+
+def export(tr, out_dir, render=False, panels=None, rig=False):
+    """-> {frame id: obj path}.  rig=True also writes <out_dir>/rig.npz (rig_batch, write_rig); every other file is unchanged."""
     m = tr.module
     H = tr.opts.n_hypo
     score = getattr(tr, 'epoch_nscore', None)
@@ -213,6 +239,7 @@ def export(tr, out_dir, render=False, panels=None):
     os.makedirs(out_dir, exist_ok=True)
     n_frames = getattr(tr, 'n_frames_on_disk', None) or tr.opts.n_frames
     done = {}
+    rigged = dict(frames={}) if rig else None
     tr.model.train()                                         # the training-mode forward is the one that builds the geometry
     with torch.no_grad():
         for batch in tr.dataloader:
@@ -229,6 +256,12 @@ def export(tr, out_dir, render=False, panels=None):
                 Rmat, Tmat = Rmat.view(len(ids), H, K, 3, 3)[:, best], Tmat.view(len(ids), H, K, 3)[:, best]
                 ctl = [p.view(H, K - 1, -1)[best] for p in (m.ctl_ts, m.ctl_rs, m.log_ctl)]
             rv = render_batch(tr, len(ids), best, verts, tex) if render else None
+            if rig:
+                rest, skin, rigR, rigT = rig_batch(tr, len(ids), best)
+                if 'rest' not in rigged:
+                    rigged.update(rest=rest.clone(), skin=skin.clone())
+                elif not (torch.equal(rest, rigged['rest']) and torch.equal(skin, rigged['skin'])):
+                    raise ValueError('extract.py --rig: the rest shape or the skin differs between batches; one rig cannot hold both')
             for k, fid in enumerate(int(v) for v in ids.tolist()):
                 if fid in done:
                     continue
@@ -239,6 +272,8 @@ def export(tr, out_dir, render=False, panels=None):
                 rtk = np.concatenate([np.concatenate([cam['R'][k], cam['T'][k][:, None]], 1),
                                       np.concatenate([cam['focal'][k], cam['pp'][k]])[None]], 0)
                 np.savetxt(os.path.join(out_dir, 'cam%d.txt' % fid), rtk)
+                if rig:
+                    rigged['frames'][fid] = (rigR[k].cpu().numpy(), rigT[k].cpu().numpy(), rtk[3])
                 write_ply(os.path.join(out_dir, 'pred%d.ply' % fid), verts[k].cpu().numpy(), m.faces.cpu().numpy(),
                           colors=255 * tex.cpu().numpy())
                 if K > 1:
@@ -247,12 +282,14 @@ def export(tr, out_dir, render=False, panels=None):
                 done[fid] = path
             if len(done) >= n_frames:
                 break
+    if rig and done:
+        write_rig(os.path.join(out_dir, 'rig.npz'), tr, rigged, tex)
     return done
 
 
 def parse_flags(argv):
-    """optimize.py's flags plus --render (default off)."""
-    return optimize.parse_flags(argv, defaults=dict(optimize.DEFAULTS, render=False))
+    """optimize.py's flags plus --render and --rig (both off by default)."""
+    return optimize.parse_flags(argv, defaults=dict(optimize.DEFAULTS, render=False, rig=False))
 
 
 def main(argv):
@@ -275,7 +312,7 @@ def main(argv):
     if states.get('epoch_nscore') is not None and len(states['epoch_nscore']) == opts.n_hypo:
         tr.epoch_nscore = states['epoch_nscore'].to(tr.device)
     panels = {} if opts.render else None
-    out = export(tr, os.path.join(opts.checkpoint_dir, opts.name), render=opts.render, panels=panels)
+    out = export(tr, os.path.join(opts.checkpoint_dir, opts.name), render=opts.render, panels=panels, rig=opts.rig)
     print('wrote %d meshes to %s' % (len(out), os.path.join(opts.checkpoint_dir, opts.name)))
     main.panels = panels                                      # --render: {frame id: the figure's panel arrays}
     return out

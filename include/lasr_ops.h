@@ -893,6 +893,39 @@ int lasr_bake_accumulate(const float* verts, const int* faces, const float* K, c
 int lasr_bake_resolve(const float* accum, const int* faces, const float* fallback, float* textures, float* weight, int V, int F,
                       int R, void* hip_stream);
 
+/*
+ * ---- Rigged glTF export of scripts/export_gltf.py (lasr_amd/csrc/rig.hip, lasr_amd/nnutils/rig.py) --------
+ * This project's own addition: the reference has no exporter, nothing of it is restated here, and parity is to the float64
+ * restatement in tests/rig_restated.py and to the project's own linear-blend skinning (lasr_lbs_forward) only.  The four entry
+ * points turn what extract.py --rig writes (rest mesh, dense skin, one row-vector transform per frame and bone:
+ * p_cam = (sum_k w_k (p R_k + T_k)) R_0 + T_0) into the arrays of a glTF 2.0 skin and animation, and measure what the
+ * truncation to k influences costs.  All arrays are dense, row major, fp32 unless noted.
+ *
+ * lasr_rig_pack: skin [J,V] -> joints u8 [V,k], weights [V,k], dropped [V]; k is 4 or LASR_RIG_MAX_INFLUENCES.  Per vertex the k
+ *   largest weights, a larger weight first and the lower bone index first among equal ones; s = their sum in that order,
+ *   weights_i = w_i / s; a slot beyond J, or one whose weight is 0, holds joint 0 with weight 0; s == 0: joint 0 with weight 1.
+ *   dropped = the sum of the weights left out, in ascending bone order.  Weights are taken to be >= 0 and finite.
+ * lasr_rig_quats: R [T,K,3,3] -> quat [T,K,4]: the unit quaternion (x, y, z, w) of the column-convention rotation R^T, by
+ *   Shepperd's method (the largest of the trace and the three diagonal entries picks the branch), normalised, with
+ *   quat[0].w >= 0 and quat[t] . quat[t-1] >= 0 for every bone.
+ * lasr_rig_skin: glTF's skinning of exactly those arrays: M_b = the matrix of quat[t,b] (standard formula, as stored) with
+ *   translation trans[t,b]; out[t,v] = M_0 (sum_i weights[v,i] M_{joints[v,i] + 1} [rest[v]; 1]), i in stored order; a joint
+ *   index >= K - 1 contributes nothing.  K == 1: joints and weights NULL, k == 0, out = M_0 [rest; 1].  Otherwise k is 4 or 8.
+ * lasr_rig_stats: posed, ref [T,V,3] -> stats [T,8] = (max_v |posed - ref|, sum_v |posed - ref|^2, min x y z, max x y z of
+ *   posed).  One block per frame: thread i folds vertices i, i + 256, ... in order, then the 256 partial results fold across
+ *   halves; no atomics, two runs give the same bits.
+ * Checked on the host before any launch (LASR_E_BADARG): 0 <= J <= LASR_RIG_MAX_BONES, 1 <= K <= LASR_RIG_MAX_BONES + 1 (quats:
+ *   0 <= K), k as above, T, V >= 0, 3 T V <= INT_MAX; then zero work (V == 0; T == 0; quats: K == 0) is LASR_OK with nothing
+ *   launched; then every pointer non-NULL (skin may be NULL for J == 0).  Device contents are not read on the host.
+ */
+#define LASR_RIG_MAX_BONES 64
+#define LASR_RIG_MAX_INFLUENCES 8
+int lasr_rig_pack(const float* skin, int J, int V, int k, unsigned char* joints, float* weights, float* dropped, void* hip_stream);
+int lasr_rig_quats(const float* R, int T, int K, float* quat, void* hip_stream);
+int lasr_rig_skin(const float* rest, const unsigned char* joints, const float* weights, const float* quat, const float* trans, int T,
+                  int K, int V, int k, float* out, void* hip_stream);
+int lasr_rig_stats(const float* posed, const float* ref, int T, int V, float* stats, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

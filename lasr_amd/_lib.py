@@ -115,6 +115,11 @@ SIGNATURES = {
     # lasr_amd/csrc/bake.hip
     'lasr_bake_accumulate': (_i, [_p] * 7 + [_i] * 8 + [_p]),
     'lasr_bake_resolve': (_i, [_p] * 5 + [_i] * 3 + [_p]),
+    # lasr_amd/csrc/rig.hip
+    'lasr_rig_pack': (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    'lasr_rig_quats': (_i, [_p, _i, _i, _p, _p]),
+    'lasr_rig_skin': (_i, [_p] * 5 + [_i] * 4 + [_p, _p]),
+    'lasr_rig_stats': (_i, [_p, _p, _i, _i, _p, _p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -172,6 +177,7 @@ MEANS_MAX_TERMS, TAIL_MAX_GROUPS = 24, 16          # LASR_MEANS_MAX_TERMS / LASR
 NN_TILE, ICP_MAX_BATCH, ICP_MAX_CHUNK = 512, 64, 4096   # LASR_NN_TILE / LASR_ICP_MAX_BATCH / LASR_ICP_MAX_CHUNK of include/lasr_ops.h
 SHEET_MAX_SIZE, RING_MAX_SCALARS = 4096, 256            # LASR_SHEET_MAX_SIZE / LASR_RING_MAX_SCALARS of include/lasr_ops.h
 BAKE_MAX_RES, BAKE_MAX_SIZE, BAKE_MAX_POWER = 32, 8192, 16   # LASR_BAKE_MAX_RES / LASR_BAKE_MAX_SIZE / LASR_BAKE_MAX_POWER of include/lasr_ops.h
+RIG_MAX_BONES, RIG_MAX_INFLUENCES = 64, 8                    # LASR_RIG_MAX_BONES / LASR_RIG_MAX_INFLUENCES of include/lasr_ops.h
 
 
 
