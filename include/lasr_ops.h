@@ -926,6 +926,48 @@ int lasr_rig_skin(const float* rest, const unsigned char* joints, const float* w
                   int K, int V, int k, float* out, void* hip_stream);
 int lasr_rig_stats(const float* posed, const float* ref, int T, int V, float* stats, void* hip_stream);
 
+/*
+ * ---- Silhouette propagation of preprocess/propagate_mask.py (lasr_amd/csrc/maskprop.hip, lasr_amd/nnutils/maskprop.py, DESIGN.md
+ * section 4.13) -------------------------------------------------------------------------------------------------------------------
+ * This project's own addition: the reference fills Annotations/ with a detector (preprocess/mask.py), which stays out of scope;
+ * nothing of it is restated here, and parity is to the float64 restatement in tests/maskprop_restated.py and to closed forms only.
+ * The three entry points carry a soft mask P_s [H,W] of a source frame s to a target frame t = s +- 1 along the optical flow (the
+ * DAVIS semi-supervised protocol: the user paints one frame).  Images are uint8 [H,W,3], soft masks and fields fp32 [H,W], flows
+ * fp32 [H,W,2] = (x, y) in pixels; all arrays are dense and on the device.  A colour's bin is (r>>4)<<8 | (g>>4)<<4 | (b>>4).
+ *
+ * lasr_maskprop_hist: hist uint32 [2, LASR_MASKPROP_BINS] += the colour counts of the pixels of the window [x0,x1) x [y0,y1) of img:
+ *   row 1 (foreground) counts those with P >= hi, row 0 (background) those with P <= lo (compared in fp32; defaults 0.9 / 0.1).
+ *   The counts are ADDED to what hist holds (the caller zeroes it, and sums the key frames' histogram with the running one).
+ *   An LDS-private histogram per workgroup, merged with integer atomics: exact, and the same whatever the order.
+ * lasr_maskprop_unary: for the pixel p of t, f = flow_ts(p), q = p + f.  q outside [0,W-1] x [0,H-1] (or not a number):
+ *   prior = conf = 0; else prior = the bilinear sample of P_s at q (the upper taps clamped to the image), back = the bilinear sample of
+ *   flow_st at q, conf = exp(-|f + back|^2 / (2 tau^2)).  app = log((hf[b]/Nf + eps) / (hb[b]/Nb + eps)) with b the bin of img_t(p),
+ *   hf / hb rows 1 / 0 of hist and Nf / Nb their totals (0 counts as 1); app_table is scratch for the 4096 values of app.
+ *   u = clamp(w_p conf logit(clamp(prior, 1e-3, 1 - 1e-3)) + w_a app, -U, U), q0 = sigmoid(u).
+ *   Defaults tau 1, w_p 1, w_a 0.5, eps 1e-3, U 6.  Two launches: the table (one block), then one thread per pixel.
+ * lasr_maskprop_meanfield: ONE edge-aware mean-field iteration, q_out(p) = sigmoid(u(p) + w_s sum_n k(p,n) (2 q_in(n) - 1)) over the
+ *   (2R+1)^2 - 1 neighbours n inside the image, k = exp(-|I(p) - I(n)|^2 / (2 sigma_i^2) - |p - n|^2 / (2 sigma_s^2)) on the uint8
+ *   colours.  q_in and q_out must differ (ping-pong; the caller launches K iterations, default 5).  Defaults R 4, sigma_i 12,
+ *   sigma_s 3, w_s 0.3.  Tiles of 32 x 8 pixels, one per lane, q and the packed colours of tile + halo staged in
+ *   8 (32 + 2R)(8 + 2R) bytes of LDS; the weights are recomputed per launch.
+ * No entry point uses floating-point atomics: the same input gives the same bits on every run.
+ * Checked on the host before any launch (LASR_E_BADARG): 0 <= H, W <= LASR_MASKPROP_MAX_SIZE, 3 H W <= INT_MAX;
+ *   hist: 0 <= x0, y0, x1 <= W, y1 <= H, lo < hi; unary: tau, eps, U > 0, w_p, w_a >= 0, all finite; meanfield:
+ *   0 <= R <= LASR_MASKPROP_MAX_RADIUS, sigma_i, sigma_s > 0, w_s >= 0, finite; then empty work (H == 0 or W == 0; hist: an
+ *   empty window, x1 <= x0 or y1 <= y0) is LASR_OK with nothing launched; then every pointer non-NULL.  Device contents are
+ *   not read on the host.  These launches are not in the lasr_prof_* kernel table.
+ */
+#define LASR_MASKPROP_BINS 4096
+#define LASR_MASKPROP_MAX_SIZE 16384
+#define LASR_MASKPROP_MAX_RADIUS 8
+int lasr_maskprop_hist(const unsigned char* img, const float* P, unsigned* hist, int H, int W, int x0, int y0, int x1, int y1, float hi,
+                       float lo, void* hip_stream);
+int lasr_maskprop_unary(const unsigned char* img_t, const float* P_s, const float* flow_ts, const float* flow_st, const unsigned* hist,
+                        float* app_table, float* u, float* q0, int H, int W, float tau, float w_p, float w_a, float eps, float U,
+                        void* hip_stream);
+int lasr_maskprop_meanfield(const unsigned char* img, const float* u, const float* q_in, float* q_out, int H, int W, int R,
+                            float sigma_i, float sigma_s, float w_s, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

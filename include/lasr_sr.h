@@ -63,7 +63,9 @@ extern "C" {
  *   11 mesh evaluation (no existing signature changes): lasr_nn_tiled, lasr_chamfer3d_*, lasr_icp_* of scripts/eval_mesh.py --icp reference.
  *   12 training monitor (no existing signature changes): lasr_flow_to_image, lasr_monitor_sheet, lasr_scalar_ring_push and their size
  *      queries (optimize.py --monitor, scripts/render_syn.py --flowvis).
- *   13 texture baking (no existing signature changes): lasr_bake_accumulate, lasr_bake_resolve of scripts/bake_texture.py. */
+ *   13 texture baking (no existing signature changes): lasr_bake_accumulate, lasr_bake_resolve of scripts/bake_texture.py.
+ *      Still 13 (additions only; a binding written against 13 loads the library unchanged): lasr_rig_* of scripts/export_gltf.py,
+ *      lasr_maskprop_hist, lasr_maskprop_unary, lasr_maskprop_meanfield of preprocess/propagate_mask.py. */
 #define LASR_ABI_VERSION 13
 int         lasr_abi_version(void);
 const char* lasr_strerror(int code);

@@ -120,6 +120,10 @@ SIGNATURES = {
     'lasr_rig_quats': (_i, [_p, _i, _i, _p, _p]),
     'lasr_rig_skin': (_i, [_p] * 5 + [_i] * 4 + [_p, _p]),
     'lasr_rig_stats': (_i, [_p, _p, _i, _i, _p, _p]),
+    # lasr_amd/csrc/maskprop.hip
+    'lasr_maskprop_hist': (_i, [_p] * 3 + [_i] * 6 + [_f, _f, _p]),
+    'lasr_maskprop_unary': (_i, [_p] * 8 + [_i, _i] + [_f] * 5 + [_p]),
+    'lasr_maskprop_meanfield': (_i, [_p] * 4 + [_i] * 3 + [_f] * 3 + [_p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -178,6 +182,7 @@ NN_TILE, ICP_MAX_BATCH, ICP_MAX_CHUNK = 512, 64, 4096   # LASR_NN_TILE / LASR_IC
 SHEET_MAX_SIZE, RING_MAX_SCALARS = 4096, 256            # LASR_SHEET_MAX_SIZE / LASR_RING_MAX_SCALARS of include/lasr_ops.h
 BAKE_MAX_RES, BAKE_MAX_SIZE, BAKE_MAX_POWER = 32, 8192, 16   # LASR_BAKE_MAX_RES / LASR_BAKE_MAX_SIZE / LASR_BAKE_MAX_POWER of include/lasr_ops.h
 RIG_MAX_BONES, RIG_MAX_INFLUENCES = 64, 8                    # LASR_RIG_MAX_BONES / LASR_RIG_MAX_INFLUENCES of include/lasr_ops.h
+MASKPROP_BINS, MASKPROP_MAX_SIZE, MASKPROP_MAX_RADIUS = 4096, 16384, 8   # LASR_MASKPROP_* of include/lasr_ops.h
 
 
 

@@ -3,6 +3,8 @@
 #   bash preprocess/auto_gen.sh camel [vcn_rob.pth]
 # Pass 1 keeps the frames that move enough (--flow_threshold 0.05) and installs them as sequence r<seq>; pass 2 computes the
 # flow of every consecutive pair (--flow_threshold 0) for <seq> itself.  Without a checkpoint both passes are dry runs.
+# Silhouettes must exist under $davisdir/Annotations/$res/<seq>/ first; from one painted frame:
+#   python preprocess/propagate_mask.py --datapath $davisdir/JPEGImages/$res/<seq>/ --key 0:first.png --loadmodel vcn_rob.pth
 set -e
 davisdir=./database/DAVIS
 res=Full-Resolution

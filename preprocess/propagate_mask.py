@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""Silhouettes for a video from one annotated frame, or a few (lasr_amd/nnutils/maskprop.py).
+
+    python preprocess/propagate_mask.py --datapath database/DAVIS/JPEGImages/Full-Resolution/camel/ \\
+           --key 0:first.png [--key 40:mid.png] --loadmodel vcn_rob.pth [--roundtrip] [--min_area 1000]
+
+The reference fills Annotations/ with a detector (preprocess/mask.py); this script takes its place for a user who paints the
+object in one frame (the DAVIS semi-supervised protocol).  The mask is carried through the video along the VCN flow of
+preprocess/auto_gen.py and written as %05d.png, one per frame of --datapath in sorted order, into the matching Annotations folder
+(the JPEGImages -> Annotations substitution of auto_gen.py, which runs next unchanged), in the reference's encoding: 128 in the
+red channel (mask.py:71-76).  A key PNG of any non-zero encoding is accepted.  maskprop.json next to the masks records the
+parameters, the per-frame areas and the round-trip IoU.  Without --loadmodel the flow network keeps its seeded random weights: the
+same dry run as auto_gen.py.  Quality on real footage is unverified; --roundtrip is the available check.
+"""
+import argparse
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+import auto_gen   # noqa: E402
+
+TUNING = (('hi', float, 0.9, 'a source pixel with P >= hi counts as foreground in the histogram'),
+          ('lo', float, 0.1, 'a source pixel with P <= lo counts as background in the histogram'),
+          ('tau', float, 1., 'forward-backward flow disagreement (px) at which the warped prior loses 39 % of its weight'),
+          ('w_p', float, 1., 'weight of the warped prior'),
+          ('w_a', float, 0.5, 'weight of the appearance log ratio'),
+          ('eps', float, 1e-3, 'floor of the histogram frequencies'),
+          ('U', float, 6., 'clamp of the unary logit'),
+          ('R', int, 4, 'radius of the mean-field window'),
+          ('sigma_i', float, 12., 'colour bandwidth of the mean-field weights (grey levels)'),
+          ('sigma_s', float, 3., 'spatial bandwidth of the mean-field weights (px)'),
+          ('w_s', float, 0.3, 'weight of the mean-field message'),
+          ('K', int, 5, 'mean-field iterations'),
+          ('min_component', float, 0.05, 'components below this share of the largest are dropped'))
+
+
+class AnnotationsExist(FileExistsError):
+    pass
+
+
+def parse_key(text):
+    idx, sep, path = text.partition(':')
+    if not sep or not path or not idx.isdigit():
+        raise argparse.ArgumentTypeError('--key takes FRAME:PNG, e.g. 0:first.png (got %r)' % text)
+    return int(idx), path
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description='propagate an annotated silhouette through a video')
+    p.add_argument('--datapath', required=True, help='folder of the frames (.../JPEGImages/.../<seq>/)')
+    p.add_argument('--key', action='append', type=parse_key, required=True, metavar='FRAME:PNG',
+                   help='an annotated frame: its index in the sorted frame list and the mask image (non-zero = object); repeatable')
+    p.add_argument('--loadmodel', default=None, help='VCN checkpoint (vcn_rob.pth); none: dry run with random weights')
+    p.add_argument('--testres', type=float, default=1, help='resolution of the flow network')
+    p.add_argument('--maxdisp', type=int, default=256, help='maximum disparity of the flow network')
+    p.add_argument('--fac', type=float, default=1, help='squeezes the coarsest search window along y')
+    p.add_argument('--roundtrip', action='store_true', help='propagate from the first key to the last frame and back; print the IoU')
+    p.add_argument('--min_area', type=int, default=1000, help='masks smaller than this many pixels are reported, not written')
+    p.add_argument('--force', action='store_true', help='write into an Annotations folder that already holds files')
+    for name, kind, default, text in TUNING:
+        p.add_argument('--' + name, type=kind, default=default, help='%s (default %s)' % (text, default))
+    args = p.parse_args(argv)
+    seen = [k for k, _ in args.key]
+    if len(set(seen)) != len(seen):
+        p.error('--key names frame %d twice' % [k for k in seen if seen.count(k) > 1][0])
+    return args
+
+
+def annotations_dir(datapath):
+    """The folder auto_gen.run reads the silhouettes of --datapath from."""
+    out = os.path.normpath(datapath).replace('JPEGImages', 'Annotations')
+    if out == os.path.normpath(datapath):
+        raise ValueError('--datapath %s has no JPEGImages component: the Annotations folder cannot be derived' % datapath)
+    return out
+
+
+def tuning_of(args):
+    return {name: getattr(args, name) for name, _, _, _ in TUNING}
+
+
+def encode_mask(mask):
+    """bool [H,W] -> uint8 [H,W,3] with 128 in the red channel (mask.py:71-76 through cv2's BGR order)."""
+    out = np.zeros(mask.shape + (3,), np.uint8)
+    out[..., 0] = np.asarray(mask, bool) * np.uint8(128)
+    return out
+
+
+def read_key(path, shape):
+    from PIL import Image
+    m = np.asarray(Image.open(path).convert('RGB')).any(-1)
+    if m.shape != tuple(shape):
+        raise ValueError('%s is %d x %d, the frames are %d x %d' % ((path,) + m.shape + tuple(shape)))
+    if not m.any():
+        raise ValueError('%s: the annotation is empty' % path)
+    return m
+
+
+def prepare_output(datapath, force):
+    out = annotations_dir(datapath)
+    if os.path.isdir(out) and os.listdir(out) and not force:
+        raise AnnotationsExist('%s already holds %d files; pass --force to write into it' % (out, len(os.listdir(out))))
+    os.makedirs(out, exist_ok=True)
+    return out
+
+
+def write_outputs(out, masks, report, min_area):
+    """Writes %05d.png per frame and maskprop.json; a frame whose mask has fewer than min_area pixels is reported, not written.
+    -> the list of the frames left out."""
+    from PIL import Image
+    small = []
+    for t, m in enumerate(masks):
+        if int(m.sum()) < min_area:
+            small.append(t)
+            continue
+        Image.fromarray(encode_mask(m)).save(os.path.join(out, '%05d.png' % t))
+    report = dict(report, min_area=min_area, skipped=small)
+    with open(os.path.join(out, 'maskprop.json'), 'w') as f:
+        json.dump(report, f, indent=1)
+    if small:
+        print('propagate_mask.py: %d frames have masks below --min_area %d and were NOT written: %s' % (len(small), min_area, small))
+        print('  auto_gen.py pairs frames and masks by position: remove these frames from %s and renumber the rest, or annotate '
+              'them (--key), before running it.  Nothing was renumbered.' % out.replace('Annotations', 'JPEGImages'))
+    return small
+
+
+def run(args, flow_fn, propagate=None, roundtrip=None):
+    """The whole script with flow_fn(imgA, imgB) -> (flow [H,W,>=2], occ), as auto_gen.run takes it.  propagate / roundtrip default
+    to lasr_amd.nnutils.maskprop's (the device passes).  -> the report written to maskprop.json."""
+    if propagate is None or (args.roundtrip and roundtrip is None):
+        from lasr_amd.nnutils import maskprop
+        propagate, roundtrip = propagate or maskprop.propagate, roundtrip or maskprop.roundtrip
+    out = prepare_output(args.datapath, args.force)
+    paths = sorted(p for p in glob.glob('%s/*' % args.datapath))
+    if not paths:
+        raise FileNotFoundError('no frames under %s' % args.datapath)
+    frames = [auto_gen.read_rgb(p) for p in paths]
+    keys = {}
+    for k, path in args.key:
+        if k >= len(frames):
+            raise ValueError('--key %d:%s: the video has %d frames' % (k, path, len(frames)))
+        keys[k] = read_key(path, frames[0].shape[:2])
+    tuning = tuning_of(args)
+    masks, _, rep = propagate(frames, keys, flow_fn, **tuning)
+    report = dict(datapath=args.datapath, frames=[os.path.basename(p) for p in paths], keys=sorted(keys), params=tuning,
+                  areas=[int(m.sum()) for m in masks], roundtrip_iou=None)
+    if args.roundtrip:
+        k0 = min(keys)
+        report['roundtrip_iou'] = float(roundtrip(frames, k0, keys[k0], flow_fn, **tuning))
+        print('round trip from frame %d to frame %d and back: IoU %.4f' % (k0, len(frames) - 1, report['roundtrip_iou']))
+    write_outputs(out, masks, report, args.min_area)
+    # maskprop.json sorts after the %05d.png files, so auto_gen.py's sorted listing still pairs frame i with mask i
+    return report
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    model = auto_gen.build_model(args)
+    try:
+        from lasr_amd.nnutils.maskprop import EmptyPropagation
+        run(args, lambda a, b: auto_gen.flow_inference(model, a, b, args.testres))
+    except (EmptyPropagation, AnnotationsExist, ValueError) as e:
+        sys.exit('propagate_mask.py: %s' % e)
+
+
+if __name__ == '__main__':
+    main()
