@@ -56,7 +56,9 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
     // whole face costs 33 registers = half the resident waves: slower, profiles/experiments/README.md.)  Measured: backward
     // 1.139 -> 1.092 ms at 256 frames, 65 VGPRs (the distance code only: with the vertex attributes and 1 / z from LDS as well the
     // kernel needs 70 VGPRs and takes 1.105 ms).
-    __shared__ __attribute__((aligned(16))) float s_rec[BWD_THREADS / 64][REC];
+    // Behind the record the slot holds BX floats prepared once per face for the distance code (sr_device.h: euclid_one_ext): the three
+    // edge blocks one projection reads at a run-time offset, the t[] permutation's 0 / 1 factors and the obtuse corner's operands.
+    __shared__ __attribute__((aligned(16))) float s_rec[BWD_THREADS / 64][REC + (LASR_FAST ? BX : 0)];
 #endif
     constexpr bool FM = BWD_FM;
     const Modes m = LASR_FAST ? Modes{2, 1, 2, 1, 1} : A.m;
@@ -99,6 +101,9 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
     if (LASR_FAST && (flags & 16)) {
         float* dst = s_rec[threadIdx.x >> 6];
         if (lane < REC) dst[lane] = A.recs[(size_t)gw * REC + lane];
+#if LASR_BWD_ONE && (LASR_BWD_TBL || LASR_BWD_ONEPROJ)
+        dst[REC + lane] = bwd_ext_word(A.recs + (size_t)gw * REC, flags, lane);
+#endif
         __builtin_amdgcn_wave_barrier();
     }
     const lptr_t lrec = (lptr_t)s_rec[threadIdx.x >> 6];
@@ -159,7 +164,8 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
     }
     // (the ten pixel planes a face reads go through plain 64-bit addressed loads: buffer descriptors with the plane offset as a
     // scalar -- one 32-bit byte offset per pixel instead of an address computation per load -- were measured 1.5 % SLOWER,
-    // profiles/r04_opt_ab.txt)
+    // profiles/r04_opt_ab.txt; a scalar base pointer per plane with one 32-bit per-lane offset is a form the compiler takes for the
+    // two aggregate planes only and steps the other eight from a 64-bit per-lane address, profiles/experiments/README.md)
     auto ld_plane = [&](const float* base, int nplanes, int plane, int pn_) -> float {
 #if defined(LASR_BWD_ABL) && LASR_BWD_ABL == 3       // measurement build: everything but the pixel-plane loads
         return 0.25f + 1e-3f * (float)(pn_ & 255) + 0.01f * (float)plane;
@@ -231,7 +237,11 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
         // (wave-uniform choice: the face's flags)
         if (LASR_FAST && (flags & 16)) {
 #if LASR_BWD_LDSREC
+#if LASR_BWD_TBL || LASR_BWD_ONEPROJ
+            if (!fragment_one_ext(lrec, lrec + REC, flags, A.thr, A.sigma, xp, yp, w0, w1, w2, fr, tie_scale)) continue;
+#else
             if (!fragment_one(lrec, A.thr, A.sigma, xp, yp, w0, w1, w2, fr, tie_scale)) continue;
+#endif
 #else
             if (!fragment_one(rec, A.thr, A.sigma, xp, yp, w0, w1, w2, fr, tie_scale)) continue;
 #endif

@@ -472,6 +472,61 @@ __device__ __forceinline__ bool euclid(RP rec, float xp, float yp,
     return true;
 }
 
+// K.cu:113-125 as a table: the edge (0..2) an outside pixel projects to, for the sign pattern idx = n0 + 2 n1 + 4 n2 of its
+// barycentrics (n_k = "w_k <= 0") and `over` = "beyond the face's obtuse corner" (only ever true for the face's one obtuse
+// corner, flags bit0..2).  Same truth table as euclid<>'s and euclid_one's lane-mask algebra; idx 0 ("none <= 0", which the
+// reference leaves undefined) is pinned to edge 0 like there.  Two bits per case, `over` cases in the high half.
+__host__ __device__ constexpr unsigned edge_table(int obtuse_bits)
+{
+    unsigned t = 0;
+    for (int over = 0; over < 2; over++)
+        for (int idx = 0; idx < 8; idx++) {
+            const bool n0 = idx & 1, n1 = idx & 2, n2 = idx & 4;
+            const bool o0 = over && (obtuse_bits & 1), o1 = over && (obtuse_bits & 2), o2 = over && (obtuse_bits & 4);
+            const bool c12 = n1 && n2, c20 = n2 && n0 && !n1, c01 = n0 && n1 && !n2;
+            const bool e1 = (c20 && !o1) || (c01 && o2) || (n0 && !n1 && !n2);
+            const bool e2 = (c01 && !o2) || (c12 && o0) || (n1 && !n0 && !n2);
+            t |= (unsigned)((e1 ? 1 : 0) + (e2 ? 2 : 0)) << (2 * idx + 16 * over);
+        }
+    return t;
+}
+
+// the table against the two other statements of the same choice, for all 8 sign patterns x {over, not over} x {no obtuse corner, corner
+// 0, 1, 2}: euclid_one's lane-mask algebra (e0 / e1 / e2, exactly one of them set) and the reference's nested if chain (K.cu:113-125)
+__host__ __device__ constexpr bool edge_table_matches()
+{
+    for (int v = 0; v < 4; v++) {
+        const int ob = v == 0 ? 0 : 1 << (v - 1);
+        const unsigned tbl = edge_table(ob);
+        for (int over = 0; over < 2; over++)
+            for (int idx = 0; idx < 8; idx++) {
+                const int k = (int)((tbl >> (2 * idx + 16 * over)) & 3u);
+                const bool n0 = idx & 1, n1 = idx & 2, n2 = idx & 4;
+                const bool o0 = over && (ob & 1), o1 = over && (ob & 2), o2 = over && (ob & 4);
+                // euclid_one
+                const bool c12 = n1 & n2, c20 = n2 & n0 & !n1, c01 = n0 & n1 & !n2;
+                const bool e1 = (c20 & !o1) | (c01 & o2) | (n0 & !n1 & !n2);
+                const bool e2 = (c01 & !o2) | (c12 & o0) | (n1 & !n0 & !n2);
+                const bool e0 = !(e1 | e2);
+                if ((int)e0 + (int)e1 + (int)e2 != 1) return false;
+                if (k != (e1 ? 1 : e2 ? 2 : 0)) return false;
+                // K.cu:113-125
+                int a = -1;
+                if (n1 && n2) { a = 0; if (o0) a = 2; }
+                else if (n2 && n0) { a = 1; if (o1) a = 0; }
+                else if (n0 && n1) { a = 2; if (o2) a = 1; }
+                else if (n0) a = 1;
+                else if (n1) a = 2;
+                else if (n2) a = 0;
+                if (a < 0) a = 0;
+                if (k != a) return false;
+                if (idx == 0 && k != 0) return false;        // "none <= 0" stays pinned to edge 0
+            }
+    }
+    return true;
+}
+static_assert(edge_table_matches(), "edge_table disagrees with euclid_one's edge choice");
+
 // Well-conditioned faces (flags bit 4), euclidean distance: ONE edge projection per pixel, inside or outside, wherever the choice of
 // the edge is clear.  K.cu:61-110 projects an inside pixel on all three edge LINES (no clamp) and keeps the nearest: that is the
 // line with the smallest perpendicular distance d_k = w_k h_k (h_k = height of vertex k over its opposite edge, hk2 = h_k^2 in
@@ -574,6 +629,132 @@ __device__ __forceinline__ void euclid_one(RP rec, float xp, float yp, float w0,
     fr.t0 = u0; fr.t1 = u1; fr.t2 = u2; fr.sign = inside ? 1.f : -1.f;
 }
 
+// ---- euclid_one on the backward's extended LDS record (sr_backward.h: the wave's slot holds the record and, behind it, BX floats
+// written once per face).  Same operations on the same operands in the same order per pixel as euclid_one; what changes is how
+// the wave gets there:
+//   * which edge an outside pixel projects to comes from edge_table (the word is chosen per face on the scalar side);
+//   * the obtuse-corner test runs once, on operands prepared per face (x_c, y_c, x_o - x_c, y_o - y_c: the difference is the one
+//     fp32 subtraction of the inline form), and only when the face's SCALAR flags name an obtuse corner;
+//   * ONE projection body runs, on the block of the lane's edge read at a run-time offset, instead of three exec-masked ones.
+// Layout of the extension, floats, block k = 0..2 at 16 k:
+//   [0..3] e[k][0..2], e[k][(k+1)%3]   [4] 1 / den[k]   [5..7] (k == 0, k == 1, k == 2)   [8..10] ((k+1)%3 == 0, == 1, == 2) as 0 / 1
+//   [12..15] of block 0: the obtuse corner's operands
+#ifndef LASR_BWD_TBL
+#define LASR_BWD_TBL 1          // edge choice from edge_table, obtuse test on prepared operands
+#endif
+#ifndef LASR_BWD_ONEPROJ
+#define LASR_BWD_ONEPROJ 1      // one projection at a run-time offset
+#endif
+#ifndef LASR_BWD_TSEL
+#define LASR_BWD_TSEL 0         // the t[] permutation: 0 = exact 0 / 1 factors from the block, 1 = selects
+#endif
+constexpr int BX = 64, BX_STRIDE = 16, BX_OBT = 12;
+typedef float f4_t __attribute__((ext_vector_type(4)));
+typedef const float __attribute__((address_space(3)))* lds_cptr_t;
+typedef const f4_t __attribute__((address_space(3)))* lds_c4ptr_t;
+// the value lane L (0..63) of the wave stores at word L of the extension: two loads from the face's record `f` (global) per lane
+__device__ __forceinline__ float bwd_ext_word(const float* __restrict__ f, int flags, int L)
+{
+    const int k = L >> 4, i = L & 15;
+    const int c = (flags & 1) ? 0 : (flags & 2) ? 1 : 2, o = c == 0 ? 2 : c - 1;       // scalar: the obtuse corner and its far neighbour
+    const bool obt = L >= BX_OBT && L < BX_OBT + 4;
+    int ia = i < 3 ? R_E + 3 * k + i : i == 3 ? (k == 2 ? R_E + 6 : R_E + 4 * k + 1) : R_IDEN + k;
+    ia = obt ? R_FACE + 3 * ((L & 2) ? o : c) + (L & 1) : ia;
+    const int ib = R_FACE + 3 * c + (L & 1);
+    const float a = f[ia], b = f[ib];
+    float v = (obt && (L & 2)) ? a - b : a;
+    const int kb = k == 2 ? 0 : k + 1;
+    if (i >= 5 && i < 8) v = (i - 5 == k) ? 1.f : 0.f;
+    if (i >= 8 && i < 11) v = (i - 8 == kb) ? 1.f : 0.f;
+    return v;
+}
+__host__ __device__ constexpr unsigned edge_table_of_flags(int flags)
+{
+    return (flags & 1) ? edge_table(1) : (flags & 2) ? edge_table(2) : (flags & 4) ? edge_table(4) : edge_table(0);
+}
+// rec: the record's LDS copy, ext: the extension behind it; flags: the face's flags in SCALAR registers
+__device__ __forceinline__ void euclid_one_ext(lds_cptr_t rec, lds_cptr_t ext, int flags, float xp, float yp, float w0, float w1, float w2,
+                                               Frag& fr, float tie_scale)
+{
+#if !LASR_BWD_FMA
+#pragma clang fp contract(off)   // see edge_project
+#endif
+    const float x0 = rec[R_FACE + 0], y0 = rec[R_FACE + 1], x1 = rec[R_FACE + 3], y1 = rec[R_FACE + 4], x2 = rec[R_FACE + 6], y2 = rec[R_FACE + 7];
+    const bool inside = (bool)((int)(fminf(fminf(w0, w1), w2) > 0) & (int)(fmaxf(fmaxf(w0, w1), w2) < 1));
+    // inside: edge k (from vertex k to k + 1) is the one opposite vertex (k + 2) % 3, at distance w_{k+2} h_{k+2}
+    const float q0 = w2 * w2 * rec[R_HK2 + 2], q1 = w0 * w0 * rec[R_HK2 + 0], q2 = w1 * w1 * rec[R_HK2 + 1];   // edge 0, 1, 2
+    const float qlo = fminf(fminf(q0, q1), q2), qmid = __builtin_amdgcn_fmed3f(q0, q1, q2);
+    const bool tie = (bool)((int)inside & (int)near_tie(qlo, qmid, tie_scale));
+    float u0, u1, u2;
+    if (tie) {
+        float best = 100000000.f, bx = 0, by = 0, b0 = 0, b1 = 0, b2 = 0;
+#define LASR_TRY_EDGE(K)                                                          \
+        edge_project<K, false, true, false, lds_cptr_t, true>(rec, w0, w1, w2, u0, u1, u2);   \
+        {                                                                         \
+            const float px = u0 * x0 + u1 * x1 + u2 * x2;                         \
+            const float py = u0 * y0 + u1 * y1 + u2 * y2;                         \
+            const float d2 = px * px + py * py;                                   \
+            if (d2 < best) { best = d2; bx = px; by = py; b0 = u0; b1 = u1; b2 = u2; } \
+        }
+        LASR_TRY_EDGE(0) LASR_TRY_EDGE(1) LASR_TRY_EDGE(2)
+#undef LASR_TRY_EDGE
+        fr.dx = bx; fr.dy = by; u0 = b0; u1 = b1; u2 = b2;
+    } else {
+#if LASR_BWD_TBL
+        // an inside pixel (clear of a tie: exactly one of q0, q1, q2 is the smallest) has no barycentric <= 0, which the table pins to
+        // edge 0 whatever `over` says: its own edge is OR-ed in, no select between the two kinds of pixel
+        const bool i1 = (bool)((int)inside & (int)(q1 == qlo)), i2 = (bool)((int)inside & (int)(q2 == qlo));
+        bool over = false;
+        if (flags & 7) {                                // wave-uniform, decided on the scalar side
+            const f4_t ob = *(lds_c4ptr_t)(ext + BX_OBT);
+            over = (xp - ob.x) * ob.z + (yp - ob.y) * ob.w > 0;
+        }
+        const int sh = (w0 <= 0 ? 2 : 0) | (w1 <= 0 ? 4 : 0) | (w2 <= 0 ? 8 : 0) | (over ? 16 : 0);
+        const int k = (int)__builtin_amdgcn_ubfe(edge_table_of_flags(flags), (unsigned)sh, 2u) | (i1 ? 1 : 0) | (i2 ? 2 : 0);
+#else
+        const bool i1 = q1 == qlo, i2 = q2 == qlo;      // (clear of a tie: exactly one of q0, q1, q2)
+        const bool n0 = w0 <= 0, n1 = w1 <= 0, n2 = w2 <= 0;
+        bool o0 = false, o1 = false, o2 = false;
+        if (flags & 7) {
+            if (flags & 1) o0 = (xp - x0) * (x2 - x0) + (yp - y0) * (y2 - y0) > 0;
+            if (flags & 2) o1 = (xp - x1) * (x0 - x1) + (yp - y1) * (y0 - y1) > 0;
+            if (flags & 4) o2 = (xp - x2) * (x1 - x2) + (yp - y2) * (y1 - y2) > 0;
+        }
+        const bool c12 = n1 & n2, c20 = n2 & n0 & !n1, c01 = n0 & n1 & !n2;
+        bool e1 = (c20 & !o1) | (c01 & o2) | (n0 & !n1 & !n2);
+        bool e2 = (c01 & !o2) | (c12 & o0) | (n1 & !n0 & !n2);
+        e1 = inside ? i1 : e1;
+        e2 = inside ? i2 : e2;
+        const int k = e2 ? 2 : e1 ? 1 : 0;
+#endif
+#if LASR_BWD_ONEPROJ
+        // edge_project_one's body on the lane's own block
+        const lds_cptr_t E = ext + BX_STRIDE * k;
+        const f4_t ea = *(lds_c4ptr_t)E;
+        const float num = w0 * ea.x + w1 * ea.y + w2 * ea.z - ea.w;
+        float ta = num * E[4];
+        float tb = 1 - ta;
+        ta = fminf(fmaxf(ta, 0.f), 1.f);
+        tb = fminf(fmaxf(tb, 0.f), 1.f);
+#if LASR_BWD_TSEL
+        const float t0 = k == 0 ? ta : k == 2 ? tb : 0.f, t1 = k == 1 ? ta : k == 0 ? tb : 0.f, t2 = k == 2 ? ta : k == 1 ? tb : 0.f;
+#else
+        // t[k] = ta, t[(k + 1) % 3] = tb, the third 0, by exact 0 / 1 factors (ta, tb lie in [0, 1]: every product and sum is exact)
+        const f4_t fa = *(lds_c4ptr_t)(E + 4), fb = *(lds_c4ptr_t)(E + 8);
+        const float t0 = __builtin_fmaf(tb, fb.x, ta * fa.y), t1 = __builtin_fmaf(tb, fb.y, ta * fa.z), t2 = __builtin_fmaf(tb, fb.z, ta * fa.w);
+#endif
+        u0 = t0 - w0; u1 = t1 - w1; u2 = t2 - w2;
+#else
+        if (k == 0) edge_project_one<0>(rec, w0, w1, w2, u0, u1, u2);
+        if (k == 1) edge_project_one<1>(rec, w0, w1, w2, u0, u1, u2);
+        if (k == 2) edge_project_one<2>(rec, w0, w1, w2, u0, u1, u2);
+#endif
+        fr.dx = u0 * x0 + u1 * x1 + u2 * x2;
+        fr.dy = u0 * y0 + u1 * y1 + u2 * y2;
+    }
+    fr.t0 = u0; fr.t1 = u1; fr.t2 = u2; fr.sign = inside ? 1.f : -1.f;
+}
+
 // Fragment probability of the face in `rec` at (xp,yp): K.cu:387-404.  false = face skipped.
 template <typename RP>
 __device__ __forceinline__ void barycentric(RP rec, float xp, float yp, float& w0, float& w1, float& w2)
@@ -639,6 +820,25 @@ __device__ __forceinline__ bool fragment_one(RP rec, float thr, float sigma, flo
     barycentric(rec, xp, yp, w0, w1, w2);
 #endif
     euclid_one(rec, xp, yp, w0, w1, w2, fr, tie_scale);
+    fr.dis = fr.dx * fr.dx + fr.dy * fr.dy;
+    if (fr.sign < 0 && fr.dis >= thr) return false;
+    fr.D = sigmoid_neg_<true>(div_<true>(-fr.sign * fr.dis, sigma));
+    return true;
+}
+
+// fragment_one on the backward's extended LDS record (euclid_one_ext)
+__device__ __forceinline__ bool fragment_one_ext(lds_cptr_t rec, lds_cptr_t ext, int flags, float thr, float sigma, float xp, float yp,
+                                                 float& w0, float& w1, float& w2, Frag& fr, float tie_scale)
+{
+#if LASR_BWD_FMA
+    w0 = rec[R_INV + 0] * xp + rec[R_INV + 1] * yp + rec[R_INV + 2];   // K.cu:24-29, contractable
+    w1 = rec[R_INV + 3] * xp + rec[R_INV + 4] * yp + rec[R_INV + 5];
+    w2 = rec[R_INV + 6] * xp + rec[R_INV + 7] * yp + rec[R_INV + 8];
+#else
+#pragma clang fp contract(off)   // see edge_project
+    barycentric(rec, xp, yp, w0, w1, w2);
+#endif
+    euclid_one_ext(rec, ext, flags, xp, yp, w0, w1, w2, fr, tie_scale);
     fr.dis = fr.dx * fr.dx + fr.dy * fr.dy;
     if (fr.sign < 0 && fr.dis >= thr) return false;
     fr.D = sigmoid_neg_<true>(div_<true>(-fr.sign * fr.dis, sigma));

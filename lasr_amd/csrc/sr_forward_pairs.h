@@ -152,24 +152,7 @@ __device__ __forceinline__ void stage_quads(const float4* __restrict__ src, floa
     }
 }
 
-// K.cu:113-125 as a table: the edge (0..2) an outside pixel projects to, for the sign pattern idx = n0 + 2 n1 + 4 n2 of its
-// barycentrics (n_k = "w_k <= 0") and `over` = "beyond the face's obtuse corner" (only ever true for the face's one obtuse
-// corner, flags bit0..2).  Same truth table as euclid<>'s lane-mask algebra (sr_device.h); idx 0 ("none <= 0", which the
-// reference leaves undefined) is pinned to edge 0 like there.  Two bits per case, `over` cases in the high half.
-__host__ __device__ constexpr unsigned edge_table(int obtuse_bits)
-{
-    unsigned t = 0;
-    for (int over = 0; over < 2; over++)
-        for (int idx = 0; idx < 8; idx++) {
-            const bool n0 = idx & 1, n1 = idx & 2, n2 = idx & 4;
-            const bool o0 = over && (obtuse_bits & 1), o1 = over && (obtuse_bits & 2), o2 = over && (obtuse_bits & 4);
-            const bool c12 = n1 && n2, c20 = n2 && n0 && !n1, c01 = n0 && n1 && !n2;
-            const bool e1 = (c20 && !o1) || (c01 && o2) || (n0 && !n1 && !n2);
-            const bool e2 = (c01 && !o2) || (c12 && o0) || (n1 && !n0 && !n2);
-            t |= (unsigned)((e1 ? 1 : 0) + (e2 ? 2 : 0)) << (2 * idx + 16 * over);
-        }
-    return t;
-}
+// (edge_table, the 2-bit table of the edge an outside pixel projects to, lives in sr_device.h: the backward raster reads it too)
 
 // a / b from y = RN(1 / b) with ONE Newton-Markstein correction: the correctly rounded quotient unless a / b lies within 2^-48
 // (relative) of a rounding boundary -- about one quotient in 2^24 then differs from div_by_recip's by an ulp.  For the
