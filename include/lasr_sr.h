@@ -297,6 +297,10 @@ int lasr_selftest_div(const float* a, const float* b, int* mismatches, int n, vo
 /* Same for the shared-divisor division of the clip/normalise step: a [n,3] with 0 <= a <= 1, b [n] in [1e-5, 3];
  * adds the number of quotients (3 per row) that differ bitwise from a[i,k] / b[i]. */
 int lasr_selftest_div3(const float* a, const float* b, int* mismatches, int n, void* hip_stream);
+/* Test hook, host arrays and host arithmetic only (no device needed): out[i] = the image index of wave gw[i] in the backward pass,
+ * gw[i] / F, by the multiplication and shift the kernel uses instead of an integer division.  0 <= gw[i] <= (2^31 - 1) / 64 (the
+ * largest N x F the entry points accept), F >= 1; LASR_E_BADARG otherwise. */
+int lasr_selftest_face_div(int F, const int* gw, int n, int* out);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,16 @@ constexpr bool BWD_FM = true;
 #ifndef LASR_BWD_ONE
 #define LASR_BWD_ONE 1      // one edge projection per pixel for well-conditioned faces (sr_device.h: euclid_one)
 #endif
+// Per-face constants the wave no longer derives (measurement builds switch a part back to its earlier form: make variant DEFS=-D..=0)
+#ifndef LASR_FC_TIE
+#define LASR_FC_TIE 1       // the near-tie margin from the record (word R_TIE, written by set-up) instead of an IEEE division per wave
+#endif
+#ifndef LASR_FC_TBL
+#define LASR_FC_TBL 1       // the LDS extension's source words from k_bwd_ext_tbl instead of per-lane index arithmetic
+#endif
+#ifndef LASR_FC_DIV
+#define LASR_FC_DIV 1       // gw / F by the host's magic multiplier (sr_common.h: face_div) instead of the integer-division expansion
+#endif
 constexpr int QCAP = 128;   // ring entries per wave (power of two, >= 2 * 64)
 constexpr int BWD_THREADS = 64;   // one wave per workgroup (see backward_impl)
 
@@ -89,9 +99,16 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
         blk = (total & 7) == 0 ? (blockIdx.x & 7) * per + (per - 1 - (blockIdx.x >> 3)) : total - 1 - blockIdx.x;
     }
 #endif
+#if LASR_FC_TBL
+    const int ext_src = LASR_FAST ? (int)k_bwd_ext_tbl[lane] : 0;       // (one coalesced load, in flight while the record's flags arrive)
+#endif
     const int gw = __builtin_amdgcn_readfirstlane((int)((blk * blockDim.x + threadIdx.x) >> 6));
     if (gw >= A.N * A.F) return;
+#if LASR_FC_DIV
+    const int bn = face_div(gw, A.fdiv_m, A.fdiv_s), fn = gw - bn * A.F;
+#else
     const int bn = gw / A.F, fn = gw - bn * A.F;
+#endif
     const int IS = A.IS, P = IS * IS;
     const cptr_t rec = as_const(A.recs + (size_t)gw * REC);
     const cptr_t tex = as_const(A.textures + (size_t)gw * A.T * NCH);
@@ -102,7 +119,11 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
         float* dst = s_rec[threadIdx.x >> 6];
         if (lane < REC) dst[lane] = A.recs[(size_t)gw * REC + lane];
 #if LASR_BWD_ONE && (LASR_BWD_TBL || LASR_BWD_ONEPROJ)
+#if LASR_FC_TBL
+        dst[REC + lane] = bwd_ext_word_tbl(A.recs + (size_t)gw * REC, flags, lane, ext_src);
+#else
         dst[REC + lane] = bwd_ext_word(A.recs + (size_t)gw * REC, flags, lane);
+#endif
 #endif
         __builtin_amdgcn_wave_barrier();
     }
@@ -152,7 +173,11 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
             ld[3 * k] = rec[R_INV + 3 * k] * h; ld[3 * k + 1] = rec[R_INV + 3 * k + 1] * h; ld[3 * k + 2] = rec[R_INV + 3 * k + 2] * h;
         }
     }
+#if LASR_FC_TIE
+    const float tie_scale = rec[R_TIE];          // near_tie_scale(hk2), 0 unless flags bit 4: derived once per face by set-up (sr_device.h)
+#else
     const float tie_scale = (flags & 16) ? near_tie_scale(rec[R_HK2], rec[R_HK2 + 1], rec[R_HK2 + 2]) : 0.f;     // (sr_device.h: near_tie)
+#endif
     // K.cu:599: a fragment the forward pass depth-culled gets no gradient.  A well-conditioned face whose vertex depths lie
     // strictly inside (near, far) cannot be culled anywhere (its clipped barycentrics are >= 0 and sum to 1 within 1e-4, so the
     // interpolated depth stays within the vertex range up to rounding): one test per face instead of one per fragment

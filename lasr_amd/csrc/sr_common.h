@@ -27,7 +27,32 @@ struct RasterArgs {
     // expansions gave, without ~30 VALU instructions per face): 1 / IS, the pixel-centre fma coefficients 2 / IS, (1 - IS) / IS,
     // (IS - 1) / IS, and stage 1's reject distance -sqrt(1.05 thr)
     float inv_is, cx_a, cx_b, cy_b, far_t;
+    // ... and of a wave's (image, face) split: gw / F as a multiplication and a shift (face_div below)
+    unsigned fdiv_m;
+    int fdiv_s;
 };
+
+// n / F for 0 <= n < 2^25 -- the wave index of the backward pass; check_common admits N F <= (2^31 - 1) / 64 = 2^25 - 1 -- by an exact
+// magic multiplier instead of the integer-division expansion (v_rcp_iflag and a chain of s_mul_hi / s_cselect in every wave).
+// With l = ceil(log2 F), s = 25 + l and m = ceil(2^s / F) = (2^s + e) / F, 0 <= e < F:
+//     n m / 2^s = n / F + n e / (F 2^s),   and   n e < 2^25 2^l = 2^s,   so the excess is below 1 / F:
+// floor(n / F) leaves a fraction of at most (F - 1) / F, the sum stays below the next integer, and floor(n m / 2^s) = floor(n / F)
+// for every such n (Granlund & Montgomery 1994, theorem 4.2 with N = 25).  F > 2^(l - 1) gives m < 2^26: the product is below 2^51
+// and takes one 32 x 32 -> 64 bit multiplication.  (tests/test_face_constants_cases.py walks the boundaries through lasr_selftest_face_div.)
+struct FaceDiv { unsigned m; int s; };
+inline FaceDiv face_div_of(int F)
+{
+    int l = 0;
+    while ((1ll << l) < (long long)F) l++;
+    FaceDiv d;
+    d.s = 25 + l;
+    d.m = F > 0 ? (unsigned)(((1ull << d.s) + (unsigned long long)F - 1) / (unsigned long long)F) : 0u;
+    return d;
+}
+__host__ __device__ __forceinline__ int face_div(int n, unsigned m, int s)
+{
+    return (int)(((unsigned long long)(unsigned)n * (unsigned long long)m) >> s);
+}
 
 constexpr int CHOICE_ONE_WAVE = 0, CHOICE_COOP = 1;
 __device__ __forceinline__ int chosen_kernel(const RasterArgs& A)

@@ -37,7 +37,10 @@ namespace lasr {
 //         [28..30] iden : RN(1/den[k])   } correctly rounded reciprocals for the exact-division-by-reciprocal below;
 // line 2  [32..40] e    : e[k][j] = sym[3k+j] - sym[3((k+1)%3)+j]           (K.cu:81-83,132-134, hoisted)
 //         [41..43] iz   : RN(1/z_k)      } flags bit5 says they are usable (finite, denominators in a safe range)
-//         [15], [31], [44..47] padding
+//         [15]     the backward's lane -> (row, column) walk over the pixel rect (build_record)
+//         [31]     tie  : near_tie_scale(hk2), the face's absolute near-tie margin (0 unless flags bit4): a function of the face
+//                         alone, derived once here instead of by an IEEE division in every backward wave
+//         [44..47] padding
 constexpr int REC = 48;
 
 // Round-4 instruction-mix options (profiles/r04_opt_ab.txt has the A/B of each bit; every one leaves the forward's output
@@ -55,7 +58,7 @@ constexpr bool OPT_SOFTMAX = (LASR_OPT & 16) != 0;    // depth-softmax update wi
 constexpr bool OPT_BWD_S1 = (LASR_OPT & 64) != 0;     // backward stage 1: branch-free conservative reject, fused centres
 constexpr bool OPT_BWD_MATH = (LASR_OPT & 128) != 0;
 constexpr bool OPT_EDGESEL = (LASR_OPT & 256) != 0;   // which edge an outside pixel projects to: lane-mask algebra, not a nested if chain  // backward stage 2: record reciprocals, med3, per-face depth-range test
-constexpr int R_BB = 0, R_FLAGS = 2, R_INV = 3, R_HK2 = 12, R_FACE = 16, R_DEN = 25, R_IDEN = 28, R_E = 32, R_IZ = 41;
+constexpr int R_BB = 0, R_FLAGS = 2, R_INV = 3, R_HK2 = 12, R_FACE = 16, R_DEN = 25, R_IDEN = 28, R_TIE = 31, R_E = 32, R_IZ = 41;
 
 // Read-only buffers written by an EARLIER kernel are viewed through the constant address
 // space: with a wave-uniform index the compiler then emits s_load (scalar cache -> SGPRs)
@@ -170,6 +173,8 @@ __device__ __forceinline__ float pix_center_p2(int i, int is, float inv_is, bool
     return pow2 ? (float)(2 * i + 1 - is) * inv_is : pix_center(i, is);
 }
 
+__host__ __device__ __forceinline__ float near_tie_scale(float h2a, float h2b, float h2c);     // (below, with near_tie)
+
 __device__ __forceinline__ void build_record(const float* __restrict__ f, float* __restrict__ rec,
                                              short4* __restrict__ rect, float margin, int IS,
                                              float* __restrict__ info27)
@@ -264,9 +269,11 @@ __device__ __forceinline__ void build_record(const float* __restrict__ f, float*
             const int mdiv = bw < 64 ? 65536 / bw + 1 : 0, dr = 64 / bw;
             rec[15] = __int_as_float(mdiv | (dr << 17));
         }
-        rec[31] = 0.f;                                              // padding: defined bytes in the workspace
+        // the near-tie margin of the backward's distance code (sr_backward.h read it off hk2 with an IEEE division in every wave):
+        // the same expression, once per face
+        rec[R_TIE] = (__float_as_int(rec[R_FLAGS]) & 16) ? near_tie_scale(rec[R_HK2], rec[R_HK2 + 1], rec[R_HK2 + 2]) : 0.f;
 #pragma unroll
-        for (int k = 44; k < REC; k++) rec[k] = 0.f;
+        for (int k = 44; k < REC; k++) rec[k] = 0.f;                // padding: defined bytes in the workspace
     }
     if (info27) {   // reference layout, for callers that still want the tensor
 #pragma unroll
@@ -667,6 +674,57 @@ __device__ __forceinline__ float bwd_ext_word(const float* __restrict__ f, int f
     if (i >= 5 && i < 8) v = (i - 5 == k) ? 1.f : 0.f;
     if (i >= 8 && i < 11) v = (i - 8 == kb) ? 1.f : 0.f;
     return v;
+}
+// The same word by a TABLE: where lane L's value comes from does not depend on the face, except for the obtuse corner's operands
+// in lanes 12..15, so the index arithmetic above (~40 half-rate integer / compare / select instructions in every wave) becomes one
+// 2-byte load per lane that does not wait for the record.  Entry: bits 0..5 a record word; BXT_ONE / BXT_ZERO: the value is the
+// constant 1 / 0 (the word is not used); BXT_C: add the obtuse corner's base R_FACE + 3 c; BXT_O: add its far neighbour's base
+// R_FACE + 3 o, and the value is that word MINUS the corner's (word R_FACE + 3 c + (L & 1)): the one fp32 subtraction x_o - x_c.
+constexpr int BXT_ONE = 0x40, BXT_ZERO = 0x80, BXT_C = 0x100, BXT_O = 0x200;
+static __constant__ constexpr unsigned short k_bwd_ext_tbl[BX] = {
+    0x020, 0x021, 0x022, 0x021, 0x01c, 0x05c, 0x09c, 0x09c, 0x09c, 0x05c, 0x09c, 0x01c, 0x100, 0x101, 0x200, 0x201,
+    0x023, 0x024, 0x025, 0x025, 0x01d, 0x09d, 0x05d, 0x09d, 0x09d, 0x09d, 0x05d, 0x01d, 0x01d, 0x01d, 0x01d, 0x01d,
+    0x026, 0x027, 0x028, 0x026, 0x01e, 0x09e, 0x09e, 0x05e, 0x05e, 0x09e, 0x09e, 0x01e, 0x01e, 0x01e, 0x01e, 0x01e,
+    0x029, 0x02a, 0x02b, 0x02d, 0x01f, 0x09f, 0x09f, 0x09f, 0x09f, 0x09f, 0x09f, 0x01f, 0x01f, 0x01f, 0x01f, 0x01f
+};
+// bwd_ext_word's index arithmetic, restated: (record word, subtract the corner's word, constant: -1 none / 0 / 1) packed in an int
+__host__ __device__ constexpr int bwd_ext_formula(int L, int c)
+{
+    const int k = L >> 4, i = L & 15, o = c == 0 ? 2 : c - 1, kb = k == 2 ? 0 : k + 1;
+    const bool obt = L >= BX_OBT && L < BX_OBT + 4;
+    int ia = i < 3 ? R_E + 3 * k + i : i == 3 ? (k == 2 ? R_E + 6 : R_E + 4 * k + 1) : R_IDEN + k;
+    ia = obt ? R_FACE + 3 * ((L & 2) ? o : c) + (L & 1) : ia;
+    const int cst = (i >= 5 && i < 8) ? (i - 5 == k ? 1 : 0) : (i >= 8 && i < 11) ? (i - 8 == kb ? 1 : 0) : -1;
+    return ia | ((obt && (L & 2)) ? 0x100 : 0) | ((cst + 1) << 9);
+}
+__host__ __device__ constexpr int bwd_ext_decode(int t, int c)
+{
+    const int o = c == 0 ? 2 : c - 1;
+    const int ia = (t & 63) + ((t & BXT_O) ? R_FACE + 3 * o : (t & BXT_C) ? R_FACE + 3 * c : 0);
+    const int cst = (t & BXT_ONE) ? 1 : (t & BXT_ZERO) ? 0 : -1;
+    return ia | ((t & BXT_O) ? 0x100 : 0) | ((cst + 1) << 9);
+}
+__host__ __device__ constexpr bool bwd_ext_tbl_matches()
+{
+    for (int c = 0; c < 3; c++)
+        for (int L = 0; L < BX; L++) {
+            const int a = bwd_ext_formula(L, c), b = bwd_ext_decode(k_bwd_ext_tbl[L], c);
+            // (a lane that stores a constant never uses its record word: only the constant has to agree)
+            if ((a >> 9) != (b >> 9) || ((a >> 9) == 0 && a != b)) return false;
+        }
+    return true;
+}
+static_assert(bwd_ext_tbl_matches(), "k_bwd_ext_tbl disagrees with bwd_ext_word's index arithmetic");
+// t: the lane's table entry (k_bwd_ext_tbl[L], loaded by the caller before the record's flags arrive)
+__device__ __forceinline__ float bwd_ext_word_tbl(const float* __restrict__ f, int flags, int L, int t)
+{
+    const int c = (flags & 1) ? 0 : (flags & 2) ? 1 : 2, o = c == 0 ? 2 : c - 1;       // scalar: the obtuse corner and its far neighbour
+    const int cb = R_FACE + 3 * c, ob = R_FACE + 3 * o;
+    const int ia = (t & 63) + ((t & BXT_O) ? ob : (t & BXT_C) ? cb : 0);
+    const float a = f[ia], b = f[cb + (L & 1)];
+    float v = (t & BXT_O) ? a - b : a;
+    v = (t & BXT_ONE) ? 1.f : v;
+    return (t & BXT_ZERO) ? 0.f : v;
 }
 __host__ __device__ constexpr unsigned edge_table_of_flags(int flags)
 {

@@ -88,7 +88,8 @@ struct PairLds {
     float rec[SPLIT][PW_CAP * RS];
     unsigned short list[PW_LIST];
     int wcnt[2][4 * SPLIT];
-    float sel[24];                    // edge k: (k == 0, k == 1, k == 2 | k + 1 == 0, k + 1 == 1, k + 1 == 2 mod 3) as 0 / 1, 8 floats apart
+    float sel[32];                    // edge k: (k == 0, k == 1, k == 2 | k + 1 == 0, k + 1 == 1, k + 1 == 2 mod 3) as 0 / 1, 8 floats apart;
+                                      // [24..31]: zeros, the block a 2-bit edge index of 3 would name (see pairs_tile_body)
     unsigned long long ball[SPLIT][2][16];   // the chunk's rect ballots: [0][x] entries whose rect holds column x, [1][y] row y (of the tile)
     float merge[SPLIT > 1 ? (SPLIT - 1) * 256 * (3 + NCH) : 1];       // partial states of the teams >= 1, [team - 1][field][pixel lane]
 };
@@ -401,10 +402,15 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
         for (int k = 0; k < NCH; k++) s.c[k] = 0.f;
     }
 
-    if (tid < 24) {
+    if (tid < 32) {
         const int k = tid >> 3, j = tid & 7;          // edge k, slot j: [0..2] = (vertex == k), [3] = (k + 1) % 3 == 0, [4..5] = ... == 1, == 2
-        L.sel[tid] = j < 3 ? (j == k ? 1.f : 0.f) : (j >= 3 && j < 6 && (j - 3) == (k + 1) % 3) ? 1.f : 0.f;
+        L.sel[tid] = tid >= 24 ? 0.f : j < 3 ? (j == k ? 1.f : 0.f) : (j >= 3 && j < 6 && (j - 3) == (k + 1) % 3) ? 1.f : 0.f;
     }
+    // A lane without work rides along the walk on slot 63 (pair_apply: !has) and reads its edge index from that slot's table word.
+    // A chunk of fewer than 64 entries leaves the slot as it was: a valid table from an earlier chunk (indices 0..2), or, before the
+    // first full chunk, whatever the LDS held -- then the index could be 3 and the 0 / 1 factors were read past sel[23].  The word
+    // starts as an empty table (every index 0), and sel is padded, so the rider's reads stay in its own blocks.  Its result is discarded.
+    if (tid < SPLIT) L.rec[tid][63 * RS + PR_ETBL] = 0.f;
     // level 0: the groups of 64 consecutive faces whose union rect meets the 16x16 tile (every wave evaluates the same test)
     const int G = groups_of(A.F);
     const short4* __restrict__ grects = A.grects + (size_t)bn * G;

@@ -750,6 +750,7 @@ static RasterArgs make_args(void* ws, const float* textures, int N, int F, int T
     A.inv_is = 1.f / (float)IS;
     A.cx_a = 2.f * A.inv_is; A.cx_b = (float)(1 - IS) * A.inv_is; A.cy_b = (float)(IS - 1) * A.inv_is;
     { const float thr_pad = A.thr * 1.05f; A.far_t = -sqrtf(thr_pad); }
+    { const FaceDiv d = face_div_of(F); A.fdiv_m = d.m; A.fdiv_s = d.s; }
     A.m = Modes{dist, rgb, alpha, tex, double_side ? 1 : 0};
     A.overwrite_grads = 0;
     A.use_bg = 0;
@@ -1183,6 +1184,18 @@ extern "C" int lasr_selftest_div(const float* a, const float* b, int* mismatches
     if (n == 0) return LASR_OK;
     hipLaunchKernelGGL(selftest_div_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, a, b, mismatches, n);
     return launch_ok();
+}
+
+// gw[i] / F as the backward kernel computes it (sr_common.h: face_div with make_args' multiplier); host arrays, host arithmetic, no launch
+extern "C" int lasr_selftest_face_div(int F, const int* gw, int n, int* out)
+{
+    if (F < 1 || n < 0 || (n > 0 && (!gw || !out))) return LASR_E_BADARG;
+    const FaceDiv d = face_div_of(F);
+    for (int i = 0; i < n; i++) {
+        if (gw[i] < 0 || gw[i] > 0x7fffffff / 64) return LASR_E_BADARG;
+        out[i] = face_div(gw[i], d.m, d.s);
+    }
+    return LASR_OK;
 }
 
 extern "C" int lasr_selftest_div3(const float* a, const float* b, int* mismatches, int n, void* hip_stream)
