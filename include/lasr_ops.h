@@ -968,6 +968,78 @@ int lasr_maskprop_unary(const unsigned char* img_t, const float* P_s, const floa
 int lasr_maskprop_meanfield(const unsigned char* img, const float* u, const float* q_in, float* q_out, int H, int W, int R,
                             float sigma_i, float sigma_s, float w_s, void* hip_stream);
 
+/*
+ * ---- Dense point tracks of scripts/export_tracks.py (lasr_amd/csrc/tracks.hip, lasr_amd/nnutils/tracks.py)
+ * This project's own addition: the reference only transfers annotated keypoints between frame pairs (scripts/eval_badja.py);
+ * nothing of it is restated here, and parity is to the float64 restatement in tests/tracks_restated.py and to closed forms only.
+ * Query pixels are anchored on the surface in the frame they name and carried through every frame with a visibility decision.
+ * Conventions are those of lasr_bake_accumulate:
+ *   verts  [n,V,3]      camera space, OpenCV axes (x right, y down, z forward); the n frames of the window passed
+ *   faces  [F,3]        int32, shared by all frames; a face with an index outside [0, V) anchors nothing
+ *   K      [n,4]        fx fy px py in pixels of the H x W frame (16-byte aligned)
+ *   raster [n,2,IS,IS]  hard-mode aggrs_info of lasr_sr_forward_bg (func_id_rgb = func_id_alpha = 0) under the NDC mapping
+ *                       sx = 2u/IS - 1, sy = 1 - 2v/IS: plane 1 names the nearest face of pixel (row floor(v), column floor(u)), or -1
+ *   Pixel (r, c) covers u in [c, c+1), v in [r, r+1); its centre is (c + 0.5, r + 0.5).
+ *
+ * lasr_track_anchor: queries [Q,3] fp32 (t, v, u) = frame position, row coordinate, column coordinate (the TAP-Vid order), t a
+ *   whole number.  The call holds the frames [t0, t0 + n); a query with t outside [t0, t0 + n) is left untouched (its anchor and
+ *   snapped rows are neither read nor written), so the host may walk a video in windows.  Per query of the window it writes
+ *   anchors [Q] = 16-byte records (int32 face, fp32 c1, fp32 c2, fp32 facing), 16-byte aligned; face -1 = no anchor (then
+ *   c1 = c2 = facing = 0), and snapped [Q,2] fp32 = the (v, u) the anchor was computed at.
+ *   1. (v, u) outside 0 <= u < W, 0 <= v < H (or not a number): no anchor.  Else face = the face named at (floor v, floor u).
+ *   2. If that pixel is empty and snap_radius r > 0 (at most LASR_TRACK_MAX_SNAP): among the covered pixels of the (2r+1)^2 window
+ *      around it, clipped to the frame, the one whose centre is nearest to (u, v) (squared distance in fp32; ties go to the lowest
+ *      flat index row * IS + col) gives the face, and (u, v) moves to that pixel's centre.  None covered: no anchor, (v, u) unmoved.
+ *   3. Barycentrics by Moeller-Trumbore on the EDGE vectors e1 = V1 - V0, e2 = V2 - V0 of frame t, along the camera ray
+ *      d = ((u - px)/fx, (v - py)/fy, 1): p = d x e2, det = e1 . p, s = V0.z d - V0, b1 = (s . p)/det, q = s x e1,
+ *      b2 = (d . q)/det, b0 = 1 - b1 - b2.  s runs from V0 to the ray's point at V0's depth, not to the camera: the barycentrics
+ *      are the same for any origin on the ray, and this one keeps s as short as the face is wide.  (Origin-based products,
+ *      V1 x V2 or s = -V0, are avoided: their cancellation costs a factor |V|/|edge| of precision at LASR's depths.)
+ *      Each b_k is clamped to [0, 1] and the three are divided by their sum (a sub-pixel query may lie just outside the face that
+ *      owns the pixel centre); c1, c2 are stored, c0 = 1 - c1 - c2.  A zero-area face (e1 x e2 = 0), det = 0 or a b that is not
+ *      finite gives no anchor.
+ *   4. facing = +1 if n . P >= 0 else -1, with n = e1 x e2 (not normalised) and P = V0 + c1 e1 + c2 e2 (= c0 V0 + c1 V1 + c2 V2).
+ *
+ * lasr_track_project: one thread per (frame, query), the query index fastest; writes tracks [n,Q,2] fp32 (u, v) and state [n,Q]
+ *   uint8 for the n frames passed.  P = V0 + c1 e1 + c2 e2 of that frame; u = fx P.x/P.z + px, v = fy P.y/P.z + py.  States, tested
+ *   in this order: 0 no anchor (face outside [0, F) or naming a vertex outside [0, V); track = NaN); 4 not P.z > 0 (track = NaN);
+ *   3 outside 0 <= u < W, 0 <= v < H (track written); 2 hidden; 1 visible.  Visible means both
+ *   (a) the sign of n . P at this frame (as in step 4) equals the anchor's facing: a back-face test that needs no winding
+ *       convention, which the meshes do not guarantee; and
+ *   (b) some pixel of the (2w+1)^2 window around (floor v, floor u), clipped to the frame, names the anchor's face or a face that
+ *       shares at least one vertex index with it; w = window, 0 .. LASR_TRACK_MAX_WINDOW, default 1.
+ *   Rule (b) is deliberate.  Identity of the named face alone flickers for points near a face edge, and a depth comparison needs
+ *   a tolerance nobody can derive; the price is up to w pixels of slack at occlusion boundaries (a point up to w pixels behind an
+ *   occluder's outline still counts as visible, and one whose face neighbourhood shows through within w pixels likewise).
+ *   No atomics: the same bits for any split of the frames into windows.
+ *
+ * lasr_track_splat_keys / lasr_track_splat_resolve: the preview's two launches.  keys uint32 [n,H,W], zeroed by the caller.  Every
+ *   (frame, query) with state 1 and its track inside the frame does atomicMax(keys[frame, r, c], q + 1) on the pixels
+ *   (r, c) = (floor v + dy, floor u + dx) with dx^2 + dy^2 <= radius^2 in integers (radius at most LASR_TRACK_MAX_RADIUS), clipped to
+ *   the frame: the highest query index wins an overlap, whatever the order.  Resolve: out uint8 [n,H,W,3] = frames where key = 0,
+ *   else per channel (A colour + (255 - A) frame + 127) / 255 in unsigned integer arithmetic (the division truncates) with
+ *   colour = colors[key - 1] (uint8 [Q,3]) and A = LASR_TRACK_SPLAT_ALPHA.
+ *
+ * Checked on the host before any launch (LASR_E_BADARG): n, Q, F >= 0, V >= 1, 1 <= H, W <= IS <= LASR_TRACK_MAX_SIZE (the splat
+ *   pair: 1 <= H, W <= LASR_TRACK_MAX_SIZE), 3 V <= INT_MAX, F <= 2^24, t0 >= 0, t0 + n <= 2^24, 0 <= snap_radius <=
+ *   LASR_TRACK_MAX_SNAP, 0 <= window <= LASR_TRACK_MAX_WINDOW, 0 <= radius <= LASR_TRACK_MAX_RADIUS; then an empty problem (n == 0
+ *   or Q == 0; resolve: n == 0) is LASR_OK with nothing launched; then every pointer non-NULL (faces may be NULL for F == 0, colors
+ *   for Q == 0).  Device contents are not read on the host.  These launches are not in the lasr_prof_* kernel table.
+ */
+#define LASR_TRACK_MAX_SNAP 16
+#define LASR_TRACK_MAX_WINDOW 2
+#define LASR_TRACK_MAX_RADIUS 8
+#define LASR_TRACK_MAX_SIZE 8192
+#define LASR_TRACK_SPLAT_ALPHA 192u
+int lasr_track_anchor(const float* verts, const int* faces, const float* K, const float* raster, const float* queries, void* anchors,
+                      float* snapped, int t0, int n, int Q, int V, int F, int IS, int H, int W, int snap_radius, void* hip_stream);
+int lasr_track_project(const float* verts, const int* faces, const float* K, const float* raster, const void* anchors, float* tracks,
+                       unsigned char* state, int n, int Q, int V, int F, int IS, int H, int W, int window, void* hip_stream);
+int lasr_track_splat_keys(const float* tracks, const unsigned char* state, unsigned* keys, int n, int Q, int H, int W, int radius,
+                          void* hip_stream);
+int lasr_track_splat_resolve(const unsigned* keys, const unsigned char* colors, const unsigned char* frames, unsigned char* out, int n,
+                             int Q, int H, int W, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,7 +65,8 @@ extern "C" {
  *      queries (optimize.py --monitor, scripts/render_syn.py --flowvis).
  *   13 texture baking (no existing signature changes): lasr_bake_accumulate, lasr_bake_resolve of scripts/bake_texture.py.
  *      Still 13 (additions only; a binding written against 13 loads the library unchanged): lasr_rig_* of scripts/export_gltf.py,
- *      lasr_maskprop_hist, lasr_maskprop_unary, lasr_maskprop_meanfield of preprocess/propagate_mask.py. */
+ *      lasr_maskprop_hist, lasr_maskprop_unary, lasr_maskprop_meanfield of preprocess/propagate_mask.py,
+ *      lasr_track_anchor, lasr_track_project, lasr_track_splat_keys, lasr_track_splat_resolve of scripts/export_tracks.py. */
 #define LASR_ABI_VERSION 13
 int         lasr_abi_version(void);
 const char* lasr_strerror(int code);
