@@ -66,7 +66,8 @@ extern "C" {
  *   13 texture baking (no existing signature changes): lasr_bake_accumulate, lasr_bake_resolve of scripts/bake_texture.py.
  *      Still 13 (additions only; a binding written against 13 loads the library unchanged): lasr_rig_* of scripts/export_gltf.py,
  *      lasr_maskprop_hist, lasr_maskprop_unary, lasr_maskprop_meanfield of preprocess/propagate_mask.py,
- *      lasr_track_anchor, lasr_track_project, lasr_track_splat_keys, lasr_track_splat_resolve of scripts/export_tracks.py. */
+ *      lasr_track_anchor, lasr_track_project, lasr_track_splat_keys, lasr_track_splat_resolve of scripts/export_tracks.py,
+ *      lasr_sr_plan_forward (test hook beside lasr_sr_peek_choice and lasr_selftest_*: the forward plan of a call, host only). */
 #define LASR_ABI_VERSION 13
 int         lasr_abi_version(void);
 const char* lasr_strerror(int code);
@@ -288,6 +289,45 @@ int         lasr_prof_collect(void* hip_stream, int kernel_id, double* total_ms,
  * 3/8 of coop_max_tiles themselves.
  */
 int lasr_sr_peek_choice(const void* workspace, int N, int F, int* choice, void* hip_stream);
+
+/*
+ * lasr_sr_plan_forward (test hook; host arithmetic only: no launch, no device access, callable on a machine without a GPU): the
+ * plan a forward call with these sizes, modes, flags and options follows -- which kernel, in which tile order, with what launch
+ * geometry (lasr_sr_options has the rules, csrc/sr_raster.hip: plan_forward the arithmetic and its measurements).  The argument
+ * checks and return codes are lasr_sr_forward_opt's; an empty batch (N = 0 or IS = 0) returns LASR_OK and a zeroed plan.
+ */
+enum lasr_sr_form {                          /* the forward kernel of a launch */
+    LASR_SR_FORM_GENERIC = 0,                /* any mode combination but LASR's (three channels): four waves per 16x16 tile */
+    LASR_SR_FORM_ONE_WAVE = 1,               /* one wave per 8x8 tile */
+    LASR_SR_FORM_ONE_WAVE_RELAXED = 2,       /* ... with LASR_SR_RELAXED_MATH */
+    LASR_SR_FORM_FOUR_WAVES = 3,             /* four waves share an 8x8 tile */
+    LASR_SR_FORM_EIGHT_WAVES = 4,            /* eight waves share an 8x8 tile */
+    LASR_SR_FORM_SEG_FOUR = 5,               /* LASR_SR_SEGMENTED: four waves fold segments of an 8x8 tile's list */
+    LASR_SR_FORM_SEG_EIGHT = 6,              /* ... eight waves */
+    LASR_SR_FORM_PAIRS_ONE_TEAM = 7,         /* pair walk: one team of four waves per 16x16 tile */
+    LASR_SR_FORM_PAIRS_TWO_TEAMS = 8,        /* pair walk: two teams per 16x16 tile */
+    LASR_SR_FORM_COUNT = 9
+};
+enum lasr_sr_choice_source {                 /* what the device decides on when `both` kernels are launched */
+    LASR_SR_CHOICE_NONE = 0,                 /* the host decided */
+    LASR_SR_CHOICE_BBOX_ESTIMATE = 1,        /* sr_choose_kernel's estimate of the busy tiles from the meshes' pixel bounding boxes */
+    LASR_SR_CHOICE_NONEMPTY_TILES = 2        /* sr_order_kernel's count of non-empty tiles (launches in their own tile order) */
+};
+typedef struct lasr_sr_plan {
+    int form;                    /* lasr_sr_form */
+    int both;                    /* 1: `form` (four waves) AND LASR_SR_FORM_ONE_WAVE are launched, the device chooses; else 0 */
+    int choice_source;           /* lasr_sr_choice_source; LASR_SR_CHOICE_NONE unless `both` */
+    int choice_max;              /* LASR_SR_CHOICE_NONEMPTY_TILES: four waves iff the count is at most this; otherwise -1 */
+    int ordered;                 /* 1: the launch issues its tiles heaviest first (sr_tile_weight_kernel, sr_order_kernel) */
+    int order_groups;            /* image groups per XCD of that order (0: the launch cannot be grouped, so it is not ordered) */
+    int tile_shift;              /* log2 of the order table's tile side: 4 for the pair walk, else 3 */
+    int tso;                     /* tiles per image side of the order table */
+    int threads;                 /* block size of `form` */
+    long long choose_threshold;  /* LASR_SR_CHOICE_BBOX_ESTIMATE: four waves iff the estimate is at most this (8x8 tiles) */
+    long long grid;              /* blocks of the forward launch: one per tile of `form` (8x8, or 16x16: generic and pair walk) */
+} lasr_sr_plan;
+int lasr_sr_plan_forward(int N, int F, int T, int channels, int IS, int func_id_dist, int func_id_rgb, int func_id_alpha,
+                         int texture_sample_type, int double_side, int flags, const lasr_sr_options* options, lasr_sr_plan* out);
 
 
 /*

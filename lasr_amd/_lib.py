@@ -170,6 +170,7 @@ SIGNATURES = {
     'lasr_sr_forward_f64': (_i, [_p] * 6 + [_sz] + [_i] * 4 + [_f, _f, _f, _f, _i, _f, _f, _i, _i, _i, _i, _p]),
     'lasr_sr_backward_f64': (_i, [_p] * 9 + [_sz] + [_i] * 4 + [_f, _f, _f, _f, _i, _f, _f, _i, _i, _i, _i, _p]),
     'lasr_sr_peek_choice': (_i, [_p, _i, _i, ctypes.POINTER(ctypes.c_int), _p]),
+    'lasr_sr_plan_forward': (_i, [_i] * 11 + [_p, _p]),
     'lasr_selftest_div': (_i, [_p, _p, _p, _i, _p]),
     'lasr_selftest_div3': (_i, [_p, _p, _p, _i, _p]),
     'lasr_selftest_face_div': (_i, [_i, _p, _i, _p]),
@@ -198,6 +199,19 @@ class SrOptions(ctypes.Structure):
     heaviest-first tile order; a negative field = default."""
     _fields_ = [('coop8_max_tiles', ctypes.c_longlong), ('coop_max_tiles', ctypes.c_longlong), ('choose_max_tiles', ctypes.c_longlong),
                 ('order_max_tiles', ctypes.c_longlong), ('pair_min_tiles', ctypes.c_longlong)]
+
+
+class SrPlan(ctypes.Structure):
+    """lasr_sr_plan (include/lasr_sr.h): the forward plan lasr_sr_plan_forward reports -- kernel form, device-side choice, tile
+    order and launch geometry."""
+    _fields_ = [(n, _i) for n in ('form', 'both', 'choice_source', 'choice_max', 'ordered', 'order_groups', 'tile_shift', 'tso',
+                                  'threads')] + [('choose_threshold', ctypes.c_longlong), ('grid', ctypes.c_longlong)]
+
+
+# enum lasr_sr_form / enum lasr_sr_choice_source of include/lasr_sr.h
+(SR_FORM_GENERIC, SR_FORM_ONE_WAVE, SR_FORM_ONE_WAVE_RELAXED, SR_FORM_FOUR_WAVES, SR_FORM_EIGHT_WAVES, SR_FORM_SEG_FOUR,
+ SR_FORM_SEG_EIGHT, SR_FORM_PAIRS_ONE_TEAM, SR_FORM_PAIRS_TWO_TEAMS) = range(9)
+SR_CHOICE_NONE, SR_CHOICE_BBOX_ESTIMATE, SR_CHOICE_NONEMPTY_TILES = range(3)
 
 
 class VisParams(ctypes.Structure):

@@ -707,63 +707,111 @@ __global__ __launch_bounds__(256) void selftest_div3_kernel(const float* __restr
 // ===========================================================================
 using namespace lasr;
 
-
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int groups_of_host(int F) { return (F + GROUP - 1) / GROUP; }
 
-
-extern "C" size_t lasr_sr_workspace_bytes(int N, int F, int T, int IS)
+// The workspace, as byte offsets from its 256-aligned base -- the one place that knows them:
+//   per-face records | pixel rects | group rects | sr_choose_kernel's word (256 bytes) | sr_order_kernel's block -> tile table |
+//   sr_tile_weight_kernel's keys | 256 bytes of slack for the alignment of the base.
+// The table and the keys are sized for the launch's 8x8 tiles (IS = 0: none, the backward's records-only size).
+struct SrLayout {
+    size_t recs, rects, grects, choice, order, total;
+    // the keys follow the order table as the launch fills it (`tiles`: N x tso x tso of ITS tile size, ForwardPlan), not as it is allocated
+    size_t keys(long long tiles) const { return order + align_up((size_t)tiles * sizeof(int), 256); }
+};
+static SrLayout sr_layout(int N, int F, int IS)
 {
-    (void)T;
-    if (N < 0 || F < 0) return 0;
-    const size_t nf = (size_t)N * (size_t)F;
-    const size_t ng = (size_t)N * (size_t)((F + GROUP - 1) / GROUP);
-    const size_t t8 = IS > 0 ? (size_t)(IS + 7) / 8 : 0;
-    return align_up(nf * REC * sizeof(float), 256) + align_up(nf * sizeof(short4), 256) + align_up(ng * sizeof(short4), 256) + 256 /* sr_choose_kernel's word */
-           + align_up((size_t)N * t8 * t8 * sizeof(int), 256) /* sr_order_kernel's table */ + align_up((size_t)N * t8 * t8, 256) /* tile weights */ + 256;
+    const size_t nf = (size_t)N * (size_t)F, ng = (size_t)N * (size_t)groups_of_host(F);
+    const size_t t8 = IS > 0 ? (size_t)(IS + 7) / 8 : 0, tiles8 = (size_t)N * t8 * t8;
+    SrLayout L = {};
+    L.rects = L.recs + align_up(nf * REC * sizeof(float), 256);
+    L.grects = L.rects + align_up(nf * sizeof(short4), 256);
+    L.choice = L.grects + align_up(ng * sizeof(short4), 256);
+    L.order = L.choice + 256;
+    L.total = L.order + align_up(tiles8 * sizeof(int), 256) + align_up(tiles8, 256) + 256;
+    return L;
+}
+static char* workspace_base(const void* ws) { return (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255); }
+
+extern "C" size_t lasr_sr_workspace_bytes(int N, int F, int, int IS)
+{
+    return N < 0 || F < 0 ? 0 : sr_layout(N, F, IS).total;
 }
 
-static int check_common(int N, int F, int T, int IS, int dist, int rgb, int alpha, int tex)
+// The scalar arguments of one forward or backward call, filled by name in each entry point (nothing is threaded by position).
+struct SrCall {
+    int N, F, T, nch, IS;
+    float near, far;
+    const float* near_far_dev;           // optional {near, far} on the device
+    float eps, sigma, dist_eps, gamma;
+    Modes m;                             // as passed (double_side: any non-zero value)
+    int flags;
+    const float* background;             // forward, optional: HOST array of nch floats
+    const lasr_sr_options* options;      // forward, optional
+    hipStream_t stream;
+};
+constexpr int FORWARD_FLAGS = LASR_SR_RELAXED_MATH | LASR_SR_SEGMENTED | LASR_SR_PAIR_ONE_TEAM | LASR_SR_PAIR_TWO_TEAMS;
+constexpr int BACKWARD_FLAGS = LASR_SR_RECORDS_VALID | LASR_SR_GRADS_OVERWRITE;
+static int forward_flags(int flags) { return flags == LASR_SR_DEFAULT_FLAGS ? 0 : flags; }
+
+static bool is_lasr_fast(const Modes& m) { return m.dist == 2 && m.rgb == 1 && m.alpha == 2 && m.tex == 1 && m.double_side; }
+
+static int check_common(const SrCall& c)
 {
-    if (N < 0 || F < 0 || T < 1 || IS < 0) return LASR_E_BADARG;
-    if (dist < 0 || dist > 2 || rgb < 0 || rgb > 1 || alpha < 0 || alpha > 2 || tex < 0 || tex > 1) return LASR_E_BADMODE;
-    if ((long long)N * F > 0x7fffffffLL / 64 || (long long)N * IS * IS > 0x7fffffffLL) return LASR_E_BADARG;
-    if (IS > 32767) return LASR_E_BADARG;   // pixel rects are stored as int16
+    const Modes& m = c.m;
+    if (c.N < 0 || c.F < 0 || c.T < 1 || c.IS < 0) return LASR_E_BADARG;
+    if (m.dist < 0 || m.dist > 2 || m.rgb < 0 || m.rgb > 1 || m.alpha < 0 || m.alpha > 2 || m.tex < 0 || m.tex > 1) return LASR_E_BADMODE;
+    if ((long long)c.N * c.F > 0x7fffffffLL / 64 || (long long)c.N * c.IS * c.IS > 0x7fffffffLL) return LASR_E_BADARG;
+    if (c.IS > 32767) return LASR_E_BADARG;   // pixel rects are stored as int16
     return LASR_OK;
 }
 
-
-static RasterArgs make_args(void* ws, const float* textures, int N, int F, int T, int IS, float near, float far,
-                            float eps, float sigma, int dist, float dist_eps, float gamma, int rgb, int alpha,
-                            int tex, int double_side, float** recs, short4** rects, short4** grects)
+// the flag bits an entry point accepts, then its channel count
+static int check_flags_nch(const SrCall& c, int accepted_flags)
 {
-    const size_t nf = (size_t)N * (size_t)F;
-    char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    *recs = (float*)p;
-    *rects = (short4*)(p + align_up(nf * REC * sizeof(float), 256));
-    *grects = (short4*)((char*)*rects + align_up(nf * sizeof(short4), 256));
+    if (c.flags & ~accepted_flags) return LASR_E_BADARG;
+    if (c.nch == 3) return LASR_OK;
+    // the 6- and 9-channel passes exist for LASR's renders only (two flow attribute triples; + the texture colours when the
+    // three renders of a step share their geometry): euclidean / softmax / prod / vertex attributes, double sided
+    if ((c.nch != 6 && c.nch != 9) || c.T != 3 || !is_lasr_fast(c.m)) return LASR_E_BADMODE;
+    return LASR_OK;
+}
+
+static RasterArgs make_args(const SrCall& c, char* base, const SrLayout& L, const float* textures)
+{
     RasterArgs A;
-    A.recs = *recs; A.rects = *rects; A.grects = *grects; A.textures = textures;
-    A.N = N; A.F = F; A.T = T; A.res = (int)sqrt((double)T); A.IS = IS;   // K.cu:696
-    A.near = near; A.far = far; A.near_far_dev = nullptr; A.eps = eps; A.sigma = sigma; A.gamma = gamma;
-    A.thr = dist_eps * sigma;                                              // K.cu:352 (float product)
-    A.inv_is = 1.f / (float)IS;
-    A.cx_a = 2.f * A.inv_is; A.cx_b = (float)(1 - IS) * A.inv_is; A.cy_b = (float)(IS - 1) * A.inv_is;
+    A.recs = (const float*)(base + L.recs); A.rects = (const short4*)(base + L.rects); A.grects = (const short4*)(base + L.grects);
+    A.textures = textures;
+    A.N = c.N; A.F = c.F; A.T = c.T; A.res = (int)sqrt((double)c.T); A.IS = c.IS;   // K.cu:696
+    A.near = c.near; A.far = c.far; A.near_far_dev = c.near_far_dev; A.eps = c.eps; A.sigma = c.sigma; A.gamma = c.gamma;
+    A.thr = c.dist_eps * c.sigma;                                          // K.cu:352 (float product)
+    A.inv_is = 1.f / (float)c.IS;
+    A.cx_a = 2.f * A.inv_is; A.cx_b = (float)(1 - c.IS) * A.inv_is; A.cy_b = (float)(c.IS - 1) * A.inv_is;
     { const float thr_pad = A.thr * 1.05f; A.far_t = -sqrtf(thr_pad); }
-    { const FaceDiv d = face_div_of(F); A.fdiv_m = d.m; A.fdiv_s = d.s; }
-    A.m = Modes{dist, rgb, alpha, tex, double_side ? 1 : 0};
+    { const FaceDiv d = face_div_of(c.F); A.fdiv_m = d.m; A.fdiv_s = d.s; }
+    A.m = Modes{c.m.dist, c.m.rgb, c.m.alpha, c.m.tex, c.m.double_side ? 1 : 0};
     A.overwrite_grads = 0;
-    A.use_bg = 0;
-    A.choice = nullptr;
-    A.choice_max = -1;
-    A.order = nullptr;
+    A.use_bg = c.background != nullptr;
+    for (int k = 0; k < c.nch && c.background; k++) A.bg[k] = c.background[k];
+    A.choice = nullptr; A.choice_max = -1; A.order = nullptr;
     return A;
 }
 
+// records, pixel rects and group rects of the call's faces into the workspace (forward, and a backward without LASR_SR_RECORDS_VALID)
+static int launch_setup(const SrCall& c, char* base, const SrLayout& L, const float* faces, float* faces_info, float thr)
+{
+    {
+        ProfScope ps(K_SR_SETUP, c.stream);
+        const int bpi = (c.F + 255) / 256;
+        hipLaunchKernelGGL(sr_setup_kernel, dim3((unsigned)(c.N * bpi)), dim3(256), 0, c.stream, faces, (float*)(base + L.recs),
+                           (short4*)(base + L.rects), (short4*)(base + L.grects), faces_info, c.F, bpi, sqrtf(thr), c.IS);
+    }
+    return launch_ok();
+}
+
+// The forward plan (plan_forward below): which kernel a launch takes, in which tile order, with what geometry.
 // nothing in this file is mutable process state: the forward arithmetic is a per-call flag, the kernel-choice thresholds a per-call
 // lasr_sr_options (their built-in defaults below are constants read once at load time)
-static int default_flags() { return 0; }
-
 static long long env_blocks(const char* name, long long dflt)
 {
     const char* e = getenv(name);
@@ -776,7 +824,7 @@ static long long env_blocks(const char* name, long long dflt)
 //                                        bounding boxes -- at most g_coop_max_tiles: four waves per tile, else one wave per tile
 //   above                                one wave per tile (W1)
 // Six and nine channels hand more through LDS per entry (fewer tiles in flight per CU): their bounds are 5/8 of the numbers,
-// and they skip the device-side range (see forward_impl).  The device-side choice costs two launches of ~5 us (the chooser and
+// and they skip the device-side range (see plan_forward).  The device-side choice costs two launches of ~5 us (the chooser and
 // the kernel that returns at once).
 // Measured on an MI355X, forward kernel ms (profiles/r03_coop_ab.txt).  Mesh M2 (2420 faces, the object covers a third of the
 // tiles) at 256x256 (1024 tiles per frame), three channels, [four waves per 16x16 tile, the choice until then] -> four / eight waves:
@@ -797,6 +845,13 @@ static const long long k_coop_max_tiles = env_blocks("LASR_SR_COOP_MAX_TILES", 1
 static const long long k_choose_max_tiles = env_blocks("LASR_SR_CHOOSE_MAX_TILES", 49152);
 // launches of up to this many 8x8 tiles (five frames and more, tile total a multiple of 8) issue their tiles heaviest first
 static const long long k_order_max_tiles = env_blocks("LASR_SR_ORDER_MAX_TILES", 1ll << 40);
+// (below 5 frames the two order launches, 12 us, cost more than the order gains: 4 frames forward .089 -> .081 ms, step .153 -> .155)
+static const int k_order_min_frames = (int)env_blocks("LASR_SR_ORDER_MIN_FRAMES", 5);
+// (an XCD walks the crowded tiles of ALL its N / 8 images at once while their records fit about twice its 4 MB L2 -- 128 frames of
+// 2420 faces, 7.4 MB per XCD: forward -8 % -- beyond that the record fetch multiplies for nothing: 256 frames, 14.9 MB: FETCH_SIZE
+// 172 MB -> 1.18 GB per launch.  Larger launches sort and issue the XCD's images four at a time, the interleave of the fixed
+// order: 256 frames, forward 1.964 -> 1.915 ms + 15 us of order kernels; groups of 2 / 16: 1.924 / 1.925)
+static const int k_order_group_images = (int)env_blocks("LASR_SR_ORDER_GROUP_IMAGES", 4);
 // LASR's mode combination, launches of at least this many 8x8 tiles: the pair-walk kernel (sr_forward_pairs.h), whose lanes walk
 // their own pixel's (pixel, face) pairs; smaller launches keep the latency designs above.  Its output differs from theirs in the
 // rounding sequence only (image within ~1e-6).  LASR_SR_PAIR_MIN_TILES at load time, lasr_sr_options.pair_min_tiles per call.
@@ -814,71 +869,61 @@ static const long long k_pair_min_tiles = env_blocks("LASR_SR_PAIR_MIN_TILES", 3
 // counts and one team's smaller footprint wins.  LASR_SR_PAIR_ONE_TEAM / LASR_SR_PAIR_TWO_TEAMS force either per call.
 static const long long k_pair_teams_max_tiles = env_blocks("LASR_SR_PAIR_TEAMS_MAX_TILES", 3072);
 
-static bool is_lasr_fast(const Modes& m) { return m.dist == 2 && m.rgb == 1 && m.alpha == 2 && m.tex == 1 && m.double_side; }
+// The forward kernels by [form (LASR_SR_FORM_*)][channels 3, 6, 9] with their block sizes; a combination that does not exist is a
+// null entry, refused with LASR_E_BADMODE before anything is launched.
+typedef void (*ForwardKernel)(RasterArgs, float*, float*);
+struct ForwardEntry { ForwardKernel fn; int threads; };
+static int channel_index(int nch) { return nch == 9 ? 2 : nch == 6 ? 1 : 0; }
+static const ForwardEntry k_forward[LASR_SR_FORM_COUNT][3] = {
+    /* GENERIC          */ {{sr_forward_kernel<false, 3>, 256}, {nullptr, 0}, {nullptr, 0}},      // every other mode combination: 16x16 tiles
+    /* ONE_WAVE         */ {{sr_forward_kernel<true, 3, false, true>, 64}, {sr_forward_kernel<true, 6, false, true>, 64},
+                            {sr_forward_kernel<true, 9, false, true>, 64}},
+    /* ONE_WAVE_RELAXED */ {{sr_forward_kernel<true, 3, true, true>, 64}, {sr_forward_kernel<true, 6, true, true>, 64},
+                            {sr_forward_kernel<true, 9, true, true>, 64}},
+    /* FOUR_WAVES       */ {{sr_forward_coop_kernel<3, 4, 2, 1>, 256}, {sr_forward_coop_kernel<6, 4, 1, 0>, 256},
+                            {sr_forward_coop_kernel<9, 4, 1, 0>, 256}},
+    /* EIGHT_WAVES      */ {{sr_forward_coop_kernel<3, 8, 1, 0>, 512}, {sr_forward_coop_kernel<6, 8, 1, 0>, 512},
+                            {sr_forward_coop_kernel<9, 8, 1, 0>, 512}},
+    /* SEG_FOUR         */ {{sr_forward_seg_kernel<3, 4>, 256}, {sr_forward_seg_kernel<6, 4>, 256}, {sr_forward_seg_kernel<9, 4>, 256}},
+    /* SEG_EIGHT        */ {{sr_forward_seg_kernel<3, 8>, 512}, {sr_forward_seg_kernel<6, 8>, 512}, {sr_forward_seg_kernel<9, 8>, 512}},
+    /* PAIRS_ONE_TEAM   */ {{sr_forward_pairs3_kernel, 256}, {sr_forward_pairs_kernel<6>, 256}, {sr_forward_pairs_kernel<9>, 256}},
+    /* PAIRS_TWO_TEAMS  */ {{sr_forward_pairs_teams_kernel<3, 2>, 512}, {sr_forward_pairs_teams_kernel<6, 2>, 512},
+                            {sr_forward_pairs_teams_kernel<9, 2>, 512}},
+};
 
-static int forward_impl(const float* faces, const float* textures, float* faces_info, float* aggrs_info,
-                        float* soft_colors, void* workspace, size_t workspace_bytes, int N, int F, int T, int IS,
-                        float near, float far, float eps, float sigma_val, int func_id_dist, float dist_eps,
-                        float gamma_val, int func_id_rgb, int func_id_alpha, int texture_sample_type,
-                        int double_side, void* hip_stream, int nch, const float* near_far_dev, int flags,
-                        const float* background = nullptr, const lasr_sr_options* opt = nullptr)
+// A pure function of the call's sizes, modes, flags and options and of the constants above: no HIP call, no pointer arithmetic
+// (lasr_sr_plan_forward exposes it; include/lasr_sr.h documents the fields).
+typedef lasr_sr_plan ForwardPlan;
+static ForwardPlan plan_forward(const SrCall& c)
 {
+    const lasr_sr_options* opt = c.options;
+    const int N = c.N, F = c.F, IS = c.IS, nch = c.nch, flags = c.flags;
     const long long g_coop8_max_tiles = opt && opt->coop8_max_tiles >= 0 ? opt->coop8_max_tiles : k_coop8_max_tiles;
     const long long g_coop_max_tiles = opt && opt->coop_max_tiles >= 0 ? opt->coop_max_tiles : k_coop_max_tiles;
     const long long g_choose_max_tiles = opt && opt->choose_max_tiles >= 0 ? opt->choose_max_tiles : k_choose_max_tiles;
     const long long g_order_max_tiles = opt && opt->order_max_tiles >= 0 ? opt->order_max_tiles : k_order_max_tiles;
-    int rc = check_common(N, F, T, IS, func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type);
-    if (rc) return rc;
-    if (N == 0 || IS == 0) return LASR_OK;
-    if (!aggrs_info || !soft_colors || (F > 0 && (!faces || !textures))) return LASR_E_BADARG;
-    if (!workspace || workspace_bytes < lasr_sr_workspace_bytes(N, F, T, IS)) return LASR_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)hip_stream;
-    float* recs; short4* rects; short4* grects;
-    RasterArgs A = make_args(workspace, textures, N, F, T, IS, near, far, eps, sigma_val, func_id_dist, dist_eps,
-                             gamma_val, func_id_rgb, func_id_alpha, texture_sample_type, double_side, &recs, &rects, &grects);
-    A.near_far_dev = near_far_dev;
-    if (background) {
-        A.use_bg = 1;
-        for (int k = 0; k < nch; k++) A.bg[k] = background[k];
-    }
-    const int total = N * F;
-    // the 8x8-tile kernels, five frames and more: this launch's own tile order (sr_order_kernel)
-    const int t8o = (IS + 7) / 8;
-    const long long tiles8o = (long long)N * t8o * t8o;
     const long long g_pair_min_tiles = opt && opt->pair_min_tiles >= 0 ? opt->pair_min_tiles : k_pair_min_tiles;
-    // the pair-walk kernel: LASR's modes, default arithmetic, launches from pair_min_tiles up; its tiles are 16x16 pixels
-    const bool pairs = total > 0 && (nch > 3 || is_lasr_fast(A.m)) && !(flags & (LASR_SR_RELAXED_MATH | LASR_SR_SEGMENTED)) &&
-                       tiles8o >= g_pair_min_tiles;
-    const int tile_shift = pairs ? 4 : 3;
-    const int tso = (IS + (1 << tile_shift) - 1) >> tile_shift;              // tiles per side of the order table
-    const long long tileso = (long long)N * tso * tso;
-    // (an XCD walks the crowded tiles of ALL its N / 8 images at once while their records fit about twice its 4 MB L2 -- 128 frames of
-    // 2420 faces, 7.4 MB per XCD: forward -8 % -- beyond that the record fetch multiplies for nothing: 256 frames, 14.9 MB: FETCH_SIZE
-    // 172 MB -> 1.18 GB per launch.  Larger launches sort and issue the XCD's images four at a time, the interleave of the fixed
-    // order: 256 frames, forward 1.964 -> 1.915 ms + 15 us of order kernels; groups of 2 / 16: 1.924 / 1.925)
-    // (below 5 frames the two order launches, 12 us, cost more than the order gains: 4 frames forward .089 -> .081 ms, step .153 -> .155)
-    static const int order_min_frames = (int)env_blocks("LASR_SR_ORDER_MIN_FRAMES", 5);
-    static const int order_group_images = (int)env_blocks("LASR_SR_ORDER_GROUP_IMAGES", 4);
-    int order_groups = 1;
+    const int total = N * F;
+    const bool tile_kernels = nch > 3 || is_lasr_fast(c.m);      // the 8x8-tile kernels and the pair walk: LASR's mode combination; six / nine channels
+    const int t8o = (IS + 7) / 8;
+    const long long tiles8o = (long long)N * t8o * t8o;          // the launch's size, in which every threshold is expressed
+    ForwardPlan P = {};
+    // the pair-walk kernel: LASR's modes, default arithmetic, launches from pair_min_tiles up (the r06 table above); its tiles are 16x16 pixels
+    const bool pairs = total > 0 && tile_kernels && !(flags & (LASR_SR_RELAXED_MATH | LASR_SR_SEGMENTED)) && tiles8o >= g_pair_min_tiles;
+    // the launch's own tile order (sr_order_kernel): five frames and more (k_order_min_frames), the table in tiles of the kernel that reads it
+    P.tile_shift = pairs ? 4 : 3;
+    P.tso = (IS + (1 << P.tile_shift) - 1) >> P.tile_shift;      // tiles per side of the order table
+    const long long tileso = (long long)N * P.tso * P.tso;
+    // groups of k_order_group_images images per XCD once an XCD's records pass 8 MB (the measurement at k_order_group_images) or its keys the LDS
+    P.order_groups = 1;
     if ((long long)((N + 7) >> 3) * F * REC * (long long)sizeof(float) > (8ll << 20) || tileso > 8ll * ORDER_MAX_ENTRIES)
-        order_groups = (N & 7) == 0 && order_group_images > 0 && (N >> 3) % order_group_images == 0 ? (N >> 3) / order_group_images : 0;
-    const bool use_order = total > 0 && (nch > 3 || is_lasr_fast(A.m)) && N >= order_min_frames && (tileso & 7) == 0 &&
-                           tiles8o <= g_order_max_tiles && tso <= ORDER_MAX_SIDE && order_groups > 0 &&
-                           tileso <= 8ll * order_groups * ORDER_MAX_ENTRIES && N < 32768;
-    char* const slot = (char*)grects + align_up((size_t)N * groups_of_host(F) * sizeof(short4), 256);   // [0] sr_choose_kernel's word
-    if (total > 0) {
-        {
-            ProfScope ps(K_SR_SETUP, st);
-            const int bpi = (F + 255) / 256;
-            hipLaunchKernelGGL(sr_setup_kernel, dim3((unsigned)(N * bpi)), dim3(256), 0, st, faces, recs, rects, grects,
-                               faces_info, F, bpi, sqrtf(A.thr), IS);
-        }
-        if ((rc = launch_ok())) return rc;
-    }
-    const int tiles_x = (IS + TILE - 1) / TILE;
-    const dim3 grid((unsigned)(N * tiles_x * tiles_x));
-    // which of the 8x8-tile kernels (LASR's mode combination; six / nine channels).  0: one wave per tile, 1: four waves, 2: eight
-    // waves, 3: four waves AND one wave are launched and the device chooses.
+        P.order_groups = (N & 7) == 0 && k_order_group_images > 0 && (N >> 3) % k_order_group_images == 0 ? (N >> 3) / k_order_group_images : 0;
+    const bool use_order = total > 0 && tile_kernels && N >= k_order_min_frames && (tileso & 7) == 0 &&
+                           tiles8o <= g_order_max_tiles && P.tso <= ORDER_MAX_SIDE && P.order_groups > 0 &&
+                           tileso <= 8ll * P.order_groups * ORDER_MAX_ENTRIES && N < 32768;
+    P.ordered = use_order;
+    // which of the 8x8-tile kernels (LASR's mode combination; six / nine channels): eight waves, four waves, four waves AND one wave
+    // with the choice left to the device, or one wave per tile (profiles/r03_coop_ab.txt, the table above).
     // (six / nine channels are LASR.forward's render: its frames are cropped around the object and nearly every tile is busy, so
     // the launch size itself is the estimate and the extra launches of the device-side choice are saved)
     // With the launch's own tile order the one-wave kernel catches up earlier (tools/prof/kernel_choice_sweep.py, forward + order
@@ -886,295 +931,275 @@ static int forward_impl(const float* faces, const float* textures, float* faces_
     // .264 | .237, 32: .339 | .289; object filling the frame, 8: .151 | .154, 16: .275 | .217): four waves up to 4/7 of
     // coop_max_tiles, the device decides up to 7/16 of choose_max_tiles -- on the launch's count of NON-EMPTY tiles, which
     // sr_order_kernel has anyway (at most 3/8 of coop_max_tiles: four waves), not on sr_choose_kernel's bounding-box estimate.
-    const bool tile_kernels = nch > 3 || is_lasr_fast(A.m);
-    const bool rx = (flags & LASR_SR_RELAXED_MATH) && is_lasr_fast(A.m);
+    const bool rx = (flags & LASR_SR_RELAXED_MATH) && is_lasr_fast(c.m);
     const long long coop8_max = nch > 3 ? g_coop8_max_tiles / 8 * 5 : g_coop8_max_tiles;
     const long long coop_max_plain = nch > 3 ? g_coop_max_tiles / 8 * 5 : g_coop_max_tiles;
     const long long coop_max = use_order && nch == 3 ? coop_max_plain / 7 * 4 : coop_max_plain;      // (nine channels, 6 | 8 | 12 frames: .146 | .164 | .238 four, .165 | .167 | .200 one)
     const long long choose_max = nch > 3 ? coop_max : use_order ? g_choose_max_tiles / 16 * 7 : g_choose_max_tiles;
-    int plan = !tile_kernels || rx ? 0 : tiles8o <= coop8_max ? 2 : tiles8o <= coop_max ? 1 :
-               (tiles8o <= choose_max && total > 0 && coop_max > 0) ? 3 : 0;
-    const bool seg_flag = (flags & LASR_SR_SEGMENTED) != 0;
-    if (pairs) plan = 5;
-    (void)seg_flag;
-    if (use_order) {
-        int* order = (int*)(slot + 256);
-        unsigned char* keys = (unsigned char*)order + align_up((size_t)tileso * sizeof(int), 256);
-        int* busy = plan == 3 ? (int*)slot : nullptr;
+    // LASR_SR_SEGMENTED pays up to about twice the eight-wave range (measured: -17 % at one frame, -6 % at four, +8 % at
+    // sixteen, sr_forward_coop.h); beyond that the flag is ignored, as it is by a launch the pair walk takes
+    const bool seg = (flags & LASR_SR_SEGMENTED) != 0 && tiles8o <= 2 * coop8_max;
+    P.choose_threshold = coop_max;       // sr_choose_kernel: four waves while its estimate of the busy tiles is at most this
+    P.choice_max = -1;
+    P.grid = tiles8o;                    // one block per 8x8 tile
+    if (!tile_kernels) {
+        const int tiles_x = (IS + TILE - 1) / TILE;
+        P.form = LASR_SR_FORM_GENERIC;
+        P.grid = (long long)N * tiles_x * tiles_x;
+    } else if (pairs) {
+        // two teams per tile while the launch cannot fill the chip with one (its time is then the heaviest tile's chain of
+        // phases: k_pair_teams_max_tiles); LASR_SR_PAIR_ONE_TEAM / LASR_SR_PAIR_TWO_TEAMS force either
+        const int t16 = (IS + PW_TILE - 1) / PW_TILE;
+        const long long tiles16 = (long long)N * t16 * t16;
+        const bool teams2 = (flags & LASR_SR_PAIR_TWO_TEAMS) || (!(flags & LASR_SR_PAIR_ONE_TEAM) && tiles16 <= k_pair_teams_max_tiles);
+        P.form = teams2 ? LASR_SR_FORM_PAIRS_TWO_TEAMS : LASR_SR_FORM_PAIRS_ONE_TEAM;
+        P.grid = tiles16;
+    } else if (rx) P.form = LASR_SR_FORM_ONE_WAVE_RELAXED;
+    else if (tiles8o <= coop8_max) P.form = seg ? LASR_SR_FORM_SEG_EIGHT : LASR_SR_FORM_EIGHT_WAVES;
+    else if (tiles8o <= coop_max) P.form = seg ? LASR_SR_FORM_SEG_FOUR : LASR_SR_FORM_FOUR_WAVES;
+    else if (tiles8o <= choose_max && total > 0 && coop_max > 0) {
+        P.form = seg ? LASR_SR_FORM_SEG_FOUR : LASR_SR_FORM_FOUR_WAVES;
+        P.both = 1;                      // ... and LASR_SR_FORM_ONE_WAVE after it; the one the device did not choose returns at once
+        P.choice_source = use_order ? LASR_SR_CHOICE_NONEMPTY_TILES : LASR_SR_CHOICE_BBOX_ESTIMATE;
+        if (use_order) P.choice_max = (int)std::min<long long>(coop_max_plain / 8 * 3, 0x7fffffff);
+    } else P.form = LASR_SR_FORM_ONE_WAVE;
+    P.threads = k_forward[P.form][channel_index(nch)].threads;
+    return P;
+}
+
+static int forward_impl(const SrCall& c, const float* faces, const float* textures, float* faces_info, float* aggrs_info,
+                        float* soft_colors, void* workspace, size_t workspace_bytes)
+{
+    int rc = check_common(c);
+    if (rc) return rc;
+    if (c.N == 0 || c.IS == 0) return LASR_OK;
+    if (!aggrs_info || !soft_colors || (c.F > 0 && (!faces || !textures))) return LASR_E_BADARG;
+    const SrLayout L = sr_layout(c.N, c.F, c.IS);
+    if (!workspace || workspace_bytes < L.total) return LASR_E_WORKSPACE;
+    char* const base = workspace_base(workspace);
+    RasterArgs A = make_args(c, base, L, textures);
+    const ForwardPlan P = plan_forward(c);
+    const int ci = channel_index(c.nch);
+    const ForwardEntry first = k_forward[P.form][ci], second = k_forward[LASR_SR_FORM_ONE_WAVE][ci];      // (the second: when P.both)
+    if (!first.fn || (P.both && !second.fn)) return LASR_E_BADMODE;
+    hipStream_t st = c.stream;
+    if (c.N * c.F > 0 && (rc = launch_setup(c, base, L, faces, faces_info, A.thr))) return rc;
+    int* const choice = (int*)(base + L.choice);
+    if (P.ordered) {
+        const long long tileso = (long long)c.N * P.tso * P.tso;
+        int* order = (int*)(base + L.order);
+        unsigned char* keys = (unsigned char*)(base + L.keys(tileso));
+        int* busy = P.choice_source == LASR_SR_CHOICE_NONEMPTY_TILES ? choice : nullptr;
         ProfScope po(K_SR_ORDER, st);
-        hipLaunchKernelGGL(sr_tile_weight_kernel, dim3((unsigned)N), dim3(512), (size_t)(tso + 1) * (tso + 1) * sizeof(int), st, rects, F, tso, keys, busy, tile_shift);
-        hipLaunchKernelGGL(sr_order_kernel, dim3(8 * order_groups), dim3(ORDER_THREADS), align_up((size_t)(tileso / 8 / order_groups), 16), st,
-                           keys, N, tso, order, busy);
+        hipLaunchKernelGGL(sr_tile_weight_kernel, dim3((unsigned)c.N), dim3(512), (size_t)(P.tso + 1) * (P.tso + 1) * sizeof(int), st,
+                           A.rects, c.F, P.tso, keys, busy, P.tile_shift);
+        hipLaunchKernelGGL(sr_order_kernel, dim3(8 * P.order_groups), dim3(ORDER_THREADS), align_up((size_t)(tileso / 8 / P.order_groups), 16), st,
+                           keys, c.N, P.tso, order, busy);
         A.order = order;
-        if (plan == 3) {
-            A.choice = busy;
-            A.choice_max = (int)std::min<long long>(coop_max_plain / 8 * 3, 0x7fffffff);
-        }
     }
+    if (P.both) { A.choice = choice; A.choice_max = P.choice_max; }
     {
         ProfScope ps(K_SR_FORWARD, st);
-        if (tile_kernels) {
-            const long long tiles8 = tiles8o;
-            const dim3 grid8((unsigned)tiles8);
-            if (plan == 3 && !use_order) {
-                int* choice = (int*)slot;
-                hipLaunchKernelGGL(sr_choose_kernel, dim3(1), dim3(64), 0, st, grects, N, groups_of_host(F), IS, coop_max, choice);
-                A.choice = choice;
-            }
-            // LASR_SR_SEGMENTED pays up to about twice the eight-wave range (measured: -17 % at one frame, -6 % at four, +8 % at
-            // sixteen, sr_forward_coop.h); beyond that the flag is ignored
-            const bool seg = (flags & LASR_SR_SEGMENTED) != 0 && tiles8 <= 2 * coop8_max;
-            if (seg && plan == 2) {
-                if (nch == 9) hipLaunchKernelGGL((sr_forward_seg_kernel<9, 8>), grid8, dim3(512), 0, st, A, aggrs_info, soft_colors);
-                else if (nch == 6) hipLaunchKernelGGL((sr_forward_seg_kernel<6, 8>), grid8, dim3(512), 0, st, A, aggrs_info, soft_colors);
-                else hipLaunchKernelGGL((sr_forward_seg_kernel<3, 8>), grid8, dim3(512), 0, st, A, aggrs_info, soft_colors);
-            } else if (seg && (plan == 1 || plan == 3)) {
-                if (nch == 9) hipLaunchKernelGGL((sr_forward_seg_kernel<9, 4>), grid8, dim3(256), 0, st, A, aggrs_info, soft_colors);
-                else if (nch == 6) hipLaunchKernelGGL((sr_forward_seg_kernel<6, 4>), grid8, dim3(256), 0, st, A, aggrs_info, soft_colors);
-                else hipLaunchKernelGGL((sr_forward_seg_kernel<3, 4>), grid8, dim3(256), 0, st, A, aggrs_info, soft_colors);
-            }
-            if (!seg && plan == 2) {
-                if (nch == 9) hipLaunchKernelGGL((sr_forward_coop_kernel<9, 8, 1, 0>), grid8, dim3(512), 0, st, A, aggrs_info, soft_colors);
-                else if (nch == 6) hipLaunchKernelGGL((sr_forward_coop_kernel<6, 8, 1, 0>), grid8, dim3(512), 0, st, A, aggrs_info, soft_colors);
-                else hipLaunchKernelGGL((sr_forward_coop_kernel<3, 8, 1, 0>), grid8, dim3(512), 0, st, A, aggrs_info, soft_colors);
-            }
-            if (!seg && (plan == 1 || plan == 3)) {
-                if (nch == 9) hipLaunchKernelGGL((sr_forward_coop_kernel<9, 4, 1, 0>), grid8, dim3(256), 0, st, A, aggrs_info, soft_colors);
-                else if (nch == 6) hipLaunchKernelGGL((sr_forward_coop_kernel<6, 4, 1, 0>), grid8, dim3(256), 0, st, A, aggrs_info, soft_colors);
-                else hipLaunchKernelGGL((sr_forward_coop_kernel<3, 4, 2, 1>), grid8, dim3(256), 0, st, A, aggrs_info, soft_colors);
-            }
-            if (plan == 5) {
-                const int t16 = (IS + PW_TILE - 1) / PW_TILE;
-                const dim3 grid16((unsigned)(N * t16 * t16));
-                // two teams per tile while the launch cannot fill the chip with one (its time is then the heaviest tile's chain of
-                // phases); LASR_SR_PAIR_ONE_TEAM / LASR_SR_PAIR_TWO_TEAMS force either
-                const long long tiles16 = (long long)N * t16 * t16;
-                const bool teams2 = (flags & LASR_SR_PAIR_TWO_TEAMS) || (!(flags & LASR_SR_PAIR_ONE_TEAM) && tiles16 <= k_pair_teams_max_tiles);
-                if (teams2) {
-                    if (nch == 9) hipLaunchKernelGGL((sr_forward_pairs_teams_kernel<9, 2>), grid16, dim3(512), 0, st, A, aggrs_info, soft_colors);
-                    else if (nch == 6) hipLaunchKernelGGL((sr_forward_pairs_teams_kernel<6, 2>), grid16, dim3(512), 0, st, A, aggrs_info, soft_colors);
-                    else hipLaunchKernelGGL((sr_forward_pairs_teams_kernel<3, 2>), grid16, dim3(512), 0, st, A, aggrs_info, soft_colors);
-                } else if (nch == 9) hipLaunchKernelGGL((sr_forward_pairs_kernel<9>), grid16, dim3(256), 0, st, A, aggrs_info, soft_colors);
-                else if (nch == 6) hipLaunchKernelGGL((sr_forward_pairs_kernel<6>), grid16, dim3(256), 0, st, A, aggrs_info, soft_colors);
-                else hipLaunchKernelGGL(sr_forward_pairs3_kernel, grid16, dim3(256), 0, st, A, aggrs_info, soft_colors);
-            }
-            if (plan == 0 || plan == 3) {
-                if (nch == 9 && rx) hipLaunchKernelGGL((sr_forward_kernel<true, 9, true, true>), grid8, dim3(64), 0, st, A, aggrs_info, soft_colors);
-                else if (nch == 9) hipLaunchKernelGGL((sr_forward_kernel<true, 9, false, true>), grid8, dim3(64), 0, st, A, aggrs_info, soft_colors);
-                else if (nch == 6 && rx) hipLaunchKernelGGL((sr_forward_kernel<true, 6, true, true>), grid8, dim3(64), 0, st, A, aggrs_info, soft_colors);
-                else if (nch == 6) hipLaunchKernelGGL((sr_forward_kernel<true, 6, false, true>), grid8, dim3(64), 0, st, A, aggrs_info, soft_colors);
-                else if (rx) hipLaunchKernelGGL((sr_forward_kernel<true, 3, true, true>), grid8, dim3(64), 0, st, A, aggrs_info, soft_colors);
-                else hipLaunchKernelGGL((sr_forward_kernel<true, 3, false, true>), grid8, dim3(64), 0, st, A, aggrs_info, soft_colors);
-            }
-        } else hipLaunchKernelGGL((sr_forward_kernel<false, 3>), grid, dim3(256), 0, st, A, aggrs_info, soft_colors);
+        if (P.choice_source == LASR_SR_CHOICE_BBOX_ESTIMATE)
+            hipLaunchKernelGGL(sr_choose_kernel, dim3(1), dim3(64), 0, st, A.grects, c.N, groups_of_host(c.F), c.IS, P.choose_threshold, choice);
+        hipLaunchKernelGGL(first.fn, dim3((unsigned)P.grid), dim3(first.threads), 0, st, A, aggrs_info, soft_colors);
+        if (P.both) hipLaunchKernelGGL(second.fn, dim3((unsigned)P.grid), dim3(second.threads), 0, st, A, aggrs_info, soft_colors);
     }
     return launch_ok();
 }
 
-static int backward_impl(const float* faces, const float* textures, const float* soft_colors,
-                         const float* faces_info, const float* aggrs_info, float* grad_faces,
-                         float* grad_textures, const float* grad_soft_colors, void* workspace,
-                         size_t workspace_bytes, int N, int F, int T, int IS, float near, float far, float eps,
-                         float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb,
-                         int func_id_alpha, int texture_sample_type, int double_side, void* hip_stream, int nch,
-                         const float* near_far_dev, int flags)
+static int backward_impl(const SrCall& c, const float* faces, const float* textures, const float* soft_colors,
+                         const float* aggrs_info, float* grad_faces, float* grad_textures, const float* grad_soft_colors,
+                         void* workspace, size_t workspace_bytes)
 {
-    (void)faces_info;
-    int rc = check_common(N, F, T, IS, func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type);
+    int rc = check_common(c);
     if (rc) return rc;
-    if (N == 0 || IS == 0 || F == 0) return LASR_OK;
-    if (!faces || !textures || !soft_colors || !aggrs_info || !grad_faces || !grad_textures || !grad_soft_colors)
-        return LASR_E_BADARG;
+    if (c.N == 0 || c.IS == 0 || c.F == 0) return LASR_OK;
+    if (!faces || !textures || !soft_colors || !aggrs_info || !grad_faces || !grad_textures || !grad_soft_colors) return LASR_E_BADARG;
     // the backward touches the records, the rects and the group rects only: a workspace without the forward's tile-order table
     // (lasr_sr_workspace_bytes(N, F, T, 0), the size of ABI versions 1-2) is enough
-    if (!workspace || workspace_bytes < lasr_sr_workspace_bytes(N, F, T, 0)) return LASR_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)hip_stream;
-    float* recs; short4* rects; short4* grects;
-    RasterArgs A = make_args(workspace, textures, N, F, T, IS, near, far, eps, sigma_val, func_id_dist, dist_eps,
-                             gamma_val, func_id_rgb, func_id_alpha, texture_sample_type, double_side, &recs, &rects, &grects);
-    A.near_far_dev = near_far_dev;
-    A.overwrite_grads = (flags & LASR_SR_GRADS_OVERWRITE) && texture_sample_type == 1;
-    const int total = N * F;
-    if (!(flags & LASR_SR_RECORDS_VALID)) {      // the caller vouches that the forward's records are still in the workspace
-        {
-            ProfScope ps(K_SR_SETUP, st);
-            const int bpi = (F + 255) / 256;
-            hipLaunchKernelGGL(sr_setup_kernel, dim3((unsigned)(N * bpi)), dim3(256), 0, st, faces, recs, rects, grects,
-                               (float*)nullptr, F, bpi, sqrtf(A.thr), IS);
-        }
-        if ((rc = launch_ok())) return rc;
-    }
+    const SrLayout L = sr_layout(c.N, c.F, 0);
+    if (!workspace || workspace_bytes < L.total) return LASR_E_WORKSPACE;
+    char* const base = workspace_base(workspace);
+    RasterArgs A = make_args(c, base, L, textures);
+    A.overwrite_grads = (c.flags & LASR_SR_GRADS_OVERWRITE) && c.m.tex == 1;
+    // without LASR_SR_RECORDS_VALID (the caller vouches that the forward's records are still in the workspace) they are rebuilt
+    if (!(c.flags & LASR_SR_RECORDS_VALID) && (rc = launch_setup(c, base, L, faces, nullptr, A.thr))) return rc;
     // one wave (= one face) per workgroup: faces differ a lot in size, and a 4-wave workgroup holds its LDS and wave slots
     // until its largest face is done (measured: 1.65 ms vs 1.78 ms per 256 frames with 4 waves, 1.90 ms with 8)
-    const dim3 grid((unsigned)total);
+    const dim3 grid((unsigned)(c.N * c.F));
     {
-        ProfScope ps(K_SR_BACKWARD, st);
-        if (nch > 3 || is_lasr_fast(A.m))
-            launch_backward_fast(nch, grid, st, A, soft_colors, aggrs_info, grad_soft_colors, grad_faces, grad_textures);
+        ProfScope ps(K_SR_BACKWARD, c.stream);
+        if (c.nch > 3 || is_lasr_fast(A.m))
+            launch_backward_fast(c.nch, grid, c.stream, A, soft_colors, aggrs_info, grad_soft_colors, grad_faces, grad_textures);
         else
-            hipLaunchKernelGGL((sr_backward_kernel<false, 3>), grid, dim3(BWD_THREADS), 0, st, A, soft_colors, aggrs_info,
+            hipLaunchKernelGGL((sr_backward_kernel<false, 3>), grid, dim3(BWD_THREADS), 0, c.stream, A, soft_colors, aggrs_info,
                                grad_soft_colors, grad_faces, grad_textures);
     }
     return launch_ok();
 }
 
-static int check_nch(int channels, int dist, int rgb, int alpha, int tex, int double_side, int T)
+// Entry points (include/lasr_sr.h).  Each applies its own preconditions and flag mask, fills the call record by name and hands it
+// to forward_impl / backward_impl.
+extern "C" int lasr_sr_forward(const float* faces, const float* textures, float* faces_info, float* aggrs_info, float* soft_colors,
+                               void* workspace, size_t workspace_bytes, int N, int F, int T, int IS, float near, float far, float eps,
+                               float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb, int func_id_alpha,
+                               int texture_sample_type, int double_side, void* hip_stream)
 {
-    if (channels == 3) return LASR_OK;
-    // the 6- and 9-channel passes exist for LASR's renders only (two flow attribute triples; + the texture colours when the
-    // three renders of a step share their geometry): euclidean / softmax / prod / vertex attributes, double sided
-    if ((channels != 6 && channels != 9) || T != 3 || !(dist == 2 && rgb == 1 && alpha == 2 && tex == 1 && double_side)) return LASR_E_BADMODE;
-    return LASR_OK;
+    const SrCall c = {.N = N, .F = F, .T = T, .nch = 3, .IS = IS, .near = near, .far = far, .eps = eps, .sigma = sigma_val,
+                      .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side},
+                      .stream = (hipStream_t)hip_stream};
+    return forward_impl(c, faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes);
 }
 
-extern "C" int lasr_sr_forward(const float* faces, const float* textures, float* faces_info, float* aggrs_info,
-                               float* soft_colors, void* workspace, size_t workspace_bytes, int N, int F, int T, int IS,
-                               float near, float far, float eps, float sigma_val, int func_id_dist, float dist_eps,
-                               float gamma_val, int func_id_rgb, int func_id_alpha, int texture_sample_type,
-                               int double_side, void* hip_stream)
+// (faces_info is accepted for signature compatibility and ignored, here and in lasr_sr_backward_dev)
+extern "C" int lasr_sr_backward(const float* faces, const float* textures, const float* soft_colors, const float*,
+                                const float* aggrs_info, float* grad_faces, float* grad_textures, const float* grad_soft_colors,
+                                void* workspace, size_t workspace_bytes, int N, int F, int T, int IS, float near, float far, float eps,
+                                float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb, int func_id_alpha,
+                                int texture_sample_type, int double_side, void* hip_stream)
 {
-    return forward_impl(faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes, N, F, T, IS, near,
-                        far, eps, sigma_val, func_id_dist, dist_eps, gamma_val, func_id_rgb, func_id_alpha,
-                        texture_sample_type, double_side, hip_stream, 3, nullptr, default_flags());
+    const SrCall c = {.N = N, .F = F, .T = T, .nch = 3, .IS = IS, .near = near, .far = far, .eps = eps, .sigma = sigma_val,
+                      .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side},
+                      .stream = (hipStream_t)hip_stream};
+    return backward_impl(c, faces, textures, soft_colors, aggrs_info, grad_faces, grad_textures, grad_soft_colors, workspace, workspace_bytes);
 }
 
-extern "C" int lasr_sr_backward(const float* faces, const float* textures, const float* soft_colors,
-                                const float* faces_info, const float* aggrs_info, float* grad_faces,
-                                float* grad_textures, const float* grad_soft_colors, void* workspace,
-                                size_t workspace_bytes, int N, int F, int T, int IS, float near, float far, float eps,
-                                float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb,
-                                int func_id_alpha, int texture_sample_type, int double_side, void* hip_stream)
-{
-    return backward_impl(faces, textures, soft_colors, faces_info, aggrs_info, grad_faces, grad_textures, grad_soft_colors,
-                         workspace, workspace_bytes, N, F, T, IS, near, far, eps, sigma_val, func_id_dist, dist_eps,
-                         gamma_val, func_id_rgb, func_id_alpha, texture_sample_type, double_side, hip_stream, 3, nullptr, 0);
-}
-
-// Multi-attribute variants: `channels` per-vertex attributes (3 or 6) interpolated and depth-blended in ONE pass over the
-// geometry.  textures [N,F,3,channels], soft_colors / grad_soft_colors [N,channels+1,IS,IS] (alpha last), grad_textures
-// [N,F,3,channels].  near_far_dev may be NULL (then near/far are used).  See include/lasr_sr.h.
-extern "C" int lasr_sr_forward_attr(const float* faces, const float* textures, float* aggrs_info, float* soft_colors,
-                                    void* workspace, size_t workspace_bytes, int N, int F, int channels, int IS,
-                                    float near, float far, const float* near_far_dev, float eps, float sigma_val,
-                                    int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb, int func_id_alpha,
-                                    int texture_sample_type, int double_side, void* hip_stream)
-{
-    const int rc = check_nch(channels, func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side, 3);
-    if (rc) return rc;
-    return forward_impl(faces, textures, nullptr, aggrs_info, soft_colors, workspace, workspace_bytes, N, F, 3, IS,
-                        near, far, eps, sigma_val, func_id_dist, dist_eps, gamma_val, func_id_rgb, func_id_alpha,
-                        texture_sample_type, double_side, hip_stream, channels, near_far_dev, default_flags());
-}
-
-extern "C" int lasr_sr_backward_attr(const float* faces, const float* textures, const float* soft_colors,
-                                     const float* aggrs_info, float* grad_faces, float* grad_textures,
-                                     const float* grad_soft_colors, void* workspace, size_t workspace_bytes, int N, int F,
-                                     int channels, int IS, float near, float far, const float* near_far_dev, float eps,
-                                     float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb,
-                                     int func_id_alpha, int texture_sample_type, int double_side, void* hip_stream)
-{
-    const int rc = check_nch(channels, func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side, 3);
-    if (rc) return rc;
-    return backward_impl(faces, textures, soft_colors, nullptr, aggrs_info, grad_faces, grad_textures,
-                         grad_soft_colors, workspace, workspace_bytes, N, F, 3, IS, near, far, eps, sigma_val,
-                         func_id_dist, dist_eps, gamma_val, func_id_rgb, func_id_alpha, texture_sample_type,
-                         double_side, hip_stream, channels, near_far_dev, 0);
-}
-
-// near/far taken from device memory ({near, far} as two floats): LASR recomputes them from the projected
-// vertices every iteration (nnutils/mesh_net.py:304-311); the reference converts the 0-dim tensors to Python
-// floats at each extension call (an implicit device->host sync per call), this variant never leaves the device.
-extern "C" int lasr_sr_forward_dev(const float* faces, const float* textures, float* faces_info, float* aggrs_info,
-                                   float* soft_colors, void* workspace, size_t workspace_bytes, int N, int F, int T, int IS,
-                                   const float* near_far_dev, float eps, float sigma_val, int func_id_dist, float dist_eps,
-                                   float gamma_val, int func_id_rgb, int func_id_alpha, int texture_sample_type,
-                                   int double_side, void* hip_stream)
-{
-    if (!near_far_dev) return LASR_E_BADARG;
-    return forward_impl(faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes, N, F, T, IS, 0.f,
-                        0.f, eps, sigma_val, func_id_dist, dist_eps, gamma_val, func_id_rgb, func_id_alpha,
-                        texture_sample_type, double_side, hip_stream, 3, near_far_dev, default_flags());
-}
-
-extern "C" int lasr_sr_backward_dev(const float* faces, const float* textures, const float* soft_colors,
-                                    const float* faces_info, const float* aggrs_info, float* grad_faces,
-                                    float* grad_textures, const float* grad_soft_colors, void* workspace,
-                                    size_t workspace_bytes, int N, int F, int T, int IS, const float* near_far_dev,
-                                    float eps, float sigma_val, int func_id_dist, float dist_eps, float gamma_val,
-                                    int func_id_rgb, int func_id_alpha, int texture_sample_type, int double_side,
+// Multi-attribute variants: `channels` (3, 6 or 9) per-vertex attributes in ONE pass over the geometry; near_far_dev may be NULL.
+extern "C" int lasr_sr_forward_attr(const float* faces, const float* textures, float* aggrs_info, float* soft_colors, void* workspace,
+                                    size_t workspace_bytes, int N, int F, int channels, int IS, float near, float far,
+                                    const float* near_far_dev, float eps, float sigma_val, int func_id_dist, float dist_eps,
+                                    float gamma_val, int func_id_rgb, int func_id_alpha, int texture_sample_type, int double_side,
                                     void* hip_stream)
 {
+    const SrCall c = {.N = N, .F = F, .T = 3, .nch = channels, .IS = IS, .near = near, .far = far, .near_far_dev = near_far_dev, .eps = eps,
+                      .sigma = sigma_val, .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side},
+                      .stream = (hipStream_t)hip_stream};
+    if (const int rc = check_flags_nch(c, 0)) return rc;
+    return forward_impl(c, faces, textures, nullptr, aggrs_info, soft_colors, workspace, workspace_bytes);
+}
+
+extern "C" int lasr_sr_backward_attr(const float* faces, const float* textures, const float* soft_colors, const float* aggrs_info,
+                                     float* grad_faces, float* grad_textures, const float* grad_soft_colors, void* workspace,
+                                     size_t workspace_bytes, int N, int F, int channels, int IS, float near, float far,
+                                     const float* near_far_dev, float eps, float sigma_val, int func_id_dist, float dist_eps,
+                                     float gamma_val, int func_id_rgb, int func_id_alpha, int texture_sample_type, int double_side,
+                                     void* hip_stream)
+{
+    const SrCall c = {.N = N, .F = F, .T = 3, .nch = channels, .IS = IS, .near = near, .far = far, .near_far_dev = near_far_dev, .eps = eps,
+                      .sigma = sigma_val, .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side},
+                      .stream = (hipStream_t)hip_stream};
+    if (const int rc = check_flags_nch(c, 0)) return rc;
+    return backward_impl(c, faces, textures, soft_colors, aggrs_info, grad_faces, grad_textures, grad_soft_colors, workspace, workspace_bytes);
+}
+
+// near/far taken from device memory ({near, far} as two floats): no device->host synchronisation per call (include/lasr_sr.h)
+extern "C" int lasr_sr_forward_dev(const float* faces, const float* textures, float* faces_info, float* aggrs_info, float* soft_colors,
+                                   void* workspace, size_t workspace_bytes, int N, int F, int T, int IS, const float* near_far_dev,
+                                   float eps, float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb,
+                                   int func_id_alpha, int texture_sample_type, int double_side, void* hip_stream)
+{
     if (!near_far_dev) return LASR_E_BADARG;
-    return backward_impl(faces, textures, soft_colors, faces_info, aggrs_info, grad_faces, grad_textures, grad_soft_colors,
-                         workspace, workspace_bytes, N, F, T, IS, 0.f, 0.f, eps, sigma_val, func_id_dist, dist_eps,
-                         gamma_val, func_id_rgb, func_id_alpha, texture_sample_type, double_side, hip_stream, 3,
-                         near_far_dev, 0);
+    const SrCall c = {.N = N, .F = F, .T = T, .nch = 3, .IS = IS, .near_far_dev = near_far_dev, .eps = eps, .sigma = sigma_val,
+                      .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side},
+                      .stream = (hipStream_t)hip_stream};
+    return forward_impl(c, faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes);
+}
+
+extern "C" int lasr_sr_backward_dev(const float* faces, const float* textures, const float* soft_colors, const float*,
+                                    const float* aggrs_info, float* grad_faces, float* grad_textures, const float* grad_soft_colors,
+                                    void* workspace, size_t workspace_bytes, int N, int F, int T, int IS, const float* near_far_dev,
+                                    float eps, float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb,
+                                    int func_id_alpha, int texture_sample_type, int double_side, void* hip_stream)
+{
+    if (!near_far_dev) return LASR_E_BADARG;
+    const SrCall c = {.N = N, .F = F, .T = T, .nch = 3, .IS = IS, .near_far_dev = near_far_dev, .eps = eps, .sigma = sigma_val,
+                      .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side},
+                      .stream = (hipStream_t)hip_stream};
+    return backward_impl(c, faces, textures, soft_colors, aggrs_info, grad_faces, grad_textures, grad_soft_colors, workspace, workspace_bytes);
 }
 
 // Supersets of the entry points above (include/lasr_sr.h): every option is an argument, nothing is read from process state.
-extern "C" int lasr_sr_forward_ex(const float* faces, const float* textures, float* faces_info, float* aggrs_info,
-                                  float* soft_colors, void* workspace, size_t workspace_bytes, int N, int F, int T,
-                                  int channels, int IS, float near, float far, const float* near_far_dev, float eps,
-                                  float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb,
-                                  int func_id_alpha, int texture_sample_type, int double_side, int flags, void* hip_stream)
+extern "C" int lasr_sr_forward_opt(const float* faces, const float* textures, float* faces_info, float* aggrs_info, float* soft_colors,
+                                   void* workspace, size_t workspace_bytes, int N, int F, int T, int channels, int IS, float near,
+                                   float far, const float* near_far_dev, float eps, float sigma_val, int func_id_dist, float dist_eps,
+                                   float gamma_val, int func_id_rgb, int func_id_alpha, int texture_sample_type, int double_side,
+                                   const float* background, int flags, const lasr_sr_options* options, void* hip_stream)
 {
-    if (flags == LASR_SR_DEFAULT_FLAGS) flags = default_flags();
-    if (flags & ~(LASR_SR_RELAXED_MATH | LASR_SR_SEGMENTED | LASR_SR_PAIR_ONE_TEAM | LASR_SR_PAIR_TWO_TEAMS)) return LASR_E_BADARG;
-    const int rc = check_nch(channels, func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side, T);
-    if (rc) return rc;
-    return forward_impl(faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes, N, F, T, IS, near,
-                        far, eps, sigma_val, func_id_dist, dist_eps, gamma_val, func_id_rgb, func_id_alpha,
-                        texture_sample_type, double_side, hip_stream, channels, near_far_dev, flags);
+    const SrCall c = {.N = N, .F = F, .T = T, .nch = channels, .IS = IS, .near = near, .far = far, .near_far_dev = near_far_dev, .eps = eps,
+                      .sigma = sigma_val, .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side}, .flags = forward_flags(flags),
+                      .background = background, .options = options, .stream = (hipStream_t)hip_stream};
+    if (const int rc = check_flags_nch(c, FORWARD_FLAGS)) return rc;
+    return forward_impl(c, faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes);
 }
 
-extern "C" int lasr_sr_forward_bg(const float* faces, const float* textures, float* faces_info, float* aggrs_info,
-                                  float* soft_colors, void* workspace, size_t workspace_bytes, int N, int F, int T,
-                                  int channels, int IS, float near, float far, const float* near_far_dev, float eps,
-                                  float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb,
-                                  int func_id_alpha, int texture_sample_type, int double_side, const float* background, int flags,
-                                  void* hip_stream)
+extern "C" int lasr_sr_forward_ex(const float* faces, const float* textures, float* faces_info, float* aggrs_info, float* soft_colors,
+                                  void* workspace, size_t workspace_bytes, int N, int F, int T, int channels, int IS, float near,
+                                  float far, const float* near_far_dev, float eps, float sigma_val, int func_id_dist, float dist_eps,
+                                  float gamma_val, int func_id_rgb, int func_id_alpha, int texture_sample_type, int double_side,
+                                  int flags, void* hip_stream)
+{
+    const SrCall c = {.N = N, .F = F, .T = T, .nch = channels, .IS = IS, .near = near, .far = far, .near_far_dev = near_far_dev, .eps = eps,
+                      .sigma = sigma_val, .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side}, .flags = forward_flags(flags),
+                      .stream = (hipStream_t)hip_stream};
+    if (const int rc = check_flags_nch(c, FORWARD_FLAGS)) return rc;
+    return forward_impl(c, faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes);
+}
+
+extern "C" int lasr_sr_forward_bg(const float* faces, const float* textures, float* faces_info, float* aggrs_info, float* soft_colors,
+                                  void* workspace, size_t workspace_bytes, int N, int F, int T, int channels, int IS, float near,
+                                  float far, const float* near_far_dev, float eps, float sigma_val, int func_id_dist, float dist_eps,
+                                  float gamma_val, int func_id_rgb, int func_id_alpha, int texture_sample_type, int double_side,
+                                  const float* background, int flags, void* hip_stream)
 {
     if (!background) return LASR_E_BADARG;
-    if (flags == LASR_SR_DEFAULT_FLAGS) flags = default_flags();
-    if (flags & ~(LASR_SR_RELAXED_MATH | LASR_SR_SEGMENTED | LASR_SR_PAIR_ONE_TEAM | LASR_SR_PAIR_TWO_TEAMS)) return LASR_E_BADARG;
-    const int rc = check_nch(channels, func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side, T);
-    if (rc) return rc;
-    return forward_impl(faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes, N, F, T, IS, near,
-                        far, eps, sigma_val, func_id_dist, dist_eps, gamma_val, func_id_rgb, func_id_alpha,
-                        texture_sample_type, double_side, hip_stream, channels, near_far_dev, flags, background);
+    const SrCall c = {.N = N, .F = F, .T = T, .nch = channels, .IS = IS, .near = near, .far = far, .near_far_dev = near_far_dev, .eps = eps,
+                      .sigma = sigma_val, .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side}, .flags = forward_flags(flags),
+                      .background = background, .stream = (hipStream_t)hip_stream};
+    if (const int rc = check_flags_nch(c, FORWARD_FLAGS)) return rc;
+    return forward_impl(c, faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes);
 }
 
-extern "C" int lasr_sr_forward_opt(const float* faces, const float* textures, float* faces_info, float* aggrs_info,
-                                   float* soft_colors, void* workspace, size_t workspace_bytes, int N, int F, int T,
-                                   int channels, int IS, float near, float far, const float* near_far_dev, float eps,
-                                   float sigma_val, int func_id_dist, float dist_eps, float gamma_val, int func_id_rgb,
-                                   int func_id_alpha, int texture_sample_type, int double_side, const float* background, int flags,
-                                   const lasr_sr_options* options, void* hip_stream)
+extern "C" int lasr_sr_backward_ex(const float* faces, const float* textures, const float* soft_colors, const float* aggrs_info,
+                                   float* grad_faces, float* grad_textures, const float* grad_soft_colors, void* workspace,
+                                   size_t workspace_bytes, int N, int F, int T, int channels, int IS, float near, float far,
+                                   const float* near_far_dev, float eps, float sigma_val, int func_id_dist, float dist_eps,
+                                   float gamma_val, int func_id_rgb, int func_id_alpha, int texture_sample_type, int double_side,
+                                   int flags, void* hip_stream)
 {
-    if (flags == LASR_SR_DEFAULT_FLAGS) flags = default_flags();
-    if (flags & ~(LASR_SR_RELAXED_MATH | LASR_SR_SEGMENTED | LASR_SR_PAIR_ONE_TEAM | LASR_SR_PAIR_TWO_TEAMS)) return LASR_E_BADARG;
-    const int rc = check_nch(channels, func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side, T);
-    if (rc) return rc;
-    return forward_impl(faces, textures, faces_info, aggrs_info, soft_colors, workspace, workspace_bytes, N, F, T, IS, near,
-                        far, eps, sigma_val, func_id_dist, dist_eps, gamma_val, func_id_rgb, func_id_alpha,
-                        texture_sample_type, double_side, hip_stream, channels, near_far_dev, flags, background, options);
+    const SrCall c = {.N = N, .F = F, .T = T, .nch = channels, .IS = IS, .near = near, .far = far, .near_far_dev = near_far_dev, .eps = eps,
+                      .sigma = sigma_val, .dist_eps = dist_eps, .gamma = gamma_val,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side}, .flags = flags,
+                      .stream = (hipStream_t)hip_stream};
+    if (const int rc = check_flags_nch(c, BACKWARD_FLAGS)) return rc;
+    return backward_impl(c, faces, textures, soft_colors, aggrs_info, grad_faces, grad_textures, grad_soft_colors, workspace, workspace_bytes);
 }
 
-extern "C" int lasr_sr_backward_ex(const float* faces, const float* textures, const float* soft_colors,
-                                   const float* aggrs_info, float* grad_faces, float* grad_textures,
-                                   const float* grad_soft_colors, void* workspace, size_t workspace_bytes, int N, int F,
-                                   int T, int channels, int IS, float near, float far, const float* near_far_dev,
-                                   float eps, float sigma_val, int func_id_dist, float dist_eps, float gamma_val,
-                                   int func_id_rgb, int func_id_alpha, int texture_sample_type, int double_side, int flags,
-                                   void* hip_stream)
+// Test hook, host only (no launch, no device access): the plan a forward call with these arguments would follow.  The argument
+// checks and their return codes are the forward's (lasr_sr_forward_opt); an empty batch (N = 0 or IS = 0) leaves a zeroed plan.
+extern "C" int lasr_sr_plan_forward(int N, int F, int T, int channels, int IS, int func_id_dist, int func_id_rgb, int func_id_alpha,
+                                    int texture_sample_type, int double_side, int flags, const lasr_sr_options* options,
+                                    lasr_sr_plan* out)
 {
-    if (flags & ~(LASR_SR_RECORDS_VALID | LASR_SR_GRADS_OVERWRITE)) return LASR_E_BADARG;
-    const int rc = check_nch(channels, func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side, T);
-    if (rc) return rc;
-    return backward_impl(faces, textures, soft_colors, nullptr, aggrs_info, grad_faces, grad_textures, grad_soft_colors,
-                         workspace, workspace_bytes, N, F, T, IS, near, far, eps, sigma_val, func_id_dist, dist_eps,
-                         gamma_val, func_id_rgb, func_id_alpha, texture_sample_type, double_side, hip_stream, channels,
-                         near_far_dev, flags);
+    if (!out) return LASR_E_BADARG;
+    *out = lasr_sr_plan{};
+    const SrCall c = {.N = N, .F = F, .T = T, .nch = channels, .IS = IS, .near_far_dev = nullptr,
+                      .m = {func_id_dist, func_id_rgb, func_id_alpha, texture_sample_type, double_side}, .flags = forward_flags(flags),
+                      .options = options};
+    int rc = check_flags_nch(c, FORWARD_FLAGS);
+    if (rc || (rc = check_common(c))) return rc;
+    if (N == 0 || IS == 0) return LASR_OK;
+    *out = plan_forward(c);
+    return k_forward[out->form][channel_index(channels)].fn ? LASR_OK : LASR_E_BADMODE;
 }
 
 // Test hook: number of (a[i], b[i]) pairs for which div_by_recip(a, b, RN(1/b)) != a / b bitwise (added to *mismatches).
@@ -1209,10 +1234,7 @@ extern "C" int lasr_selftest_div3(const float* a, const float* b, int* mismatche
 extern "C" int lasr_sr_peek_choice(const void* workspace, int N, int F, int* choice, void* hip_stream)
 {
     if (!workspace || !choice || N < 0 || F < 0) return LASR_E_BADARG;
-    const size_t nf = (size_t)N * (size_t)F;
-    const char* p = (const char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    p += align_up(nf * REC * sizeof(float), 256) + align_up(nf * sizeof(short4), 256) +
-         align_up((size_t)N * groups_of_host(F) * sizeof(short4), 256);
+    const char* p = workspace_base(workspace) + sr_layout(N, F, 0).choice;
     if (hipMemcpyAsync(choice, p, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)hip_stream) != hipSuccess) return LASR_E_LAUNCH;
     return hipStreamSynchronize((hipStream_t)hip_stream) == hipSuccess ? LASR_OK : LASR_E_LAUNCH;
 }

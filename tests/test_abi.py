@@ -144,6 +144,26 @@ def test_options_struct_of_the_python_mirror_is_the_header_s():
     assert h.lasr_sr_workspace_bytes(8, 100, 3, 0) <= small
 
 
+def test_plan_struct_of_the_python_mirror_is_the_header_s():
+    # lasr_sr_plan (include/lasr_sr.h) <-> _lib.SrPlan: same fields, same order, same types; the enums the plan speaks in too
+    import ctypes
+    import re
+    from lasr_amd import _lib
+    sr = open(os.path.join(ROOT, 'include', 'lasr_sr.h')).read()
+    body = re.search(r'typedef struct lasr_sr_plan \{(.*?)\} lasr_sr_plan;', sr, re.S).group(1)
+    fields = re.findall(r'^\s*(int|long long)\s+(\w+);', body, re.M)
+    ctype = {'int': ctypes.c_int, 'long long': ctypes.c_longlong}
+    assert [(n, ctype[t]) for t, n in fields] == list(_lib.SrPlan._fields_) and len(fields) == 11
+    assert ctypes.sizeof(_lib.SrPlan) == 9 * 4 + 4 + 2 * 8                      # nine ints, padding, two long longs
+    for enum, prefix in (('lasr_sr_form', 'SR_FORM_'), ('lasr_sr_choice_source', 'SR_CHOICE_')):
+        body = re.search(r'enum %s \{(.*?)\};' % enum, sr, re.S).group(1)
+        values = {n: int(v) for n, v in re.findall(r'LASR_(\w+) = (\d+)', body)}
+        mirror = {n: getattr(_lib, n) for n in dir(_lib) if n.startswith(prefix)}
+        count = values.pop('SR_FORM_COUNT', None)
+        assert values == mirror and sorted(values.values()) == list(range(len(values))) and count in (None, len(values))
+    assert _lib.SIGNATURES['lasr_sr_plan_forward'][1] == [ctypes.c_int] * 11 + [ctypes.c_void_p] * 2
+
+
 def test_operator_launch_options_are_per_call_arguments_not_library_state():
     # the operator keeps its lasr_sr_options struct on the Python side and passes it with every forward call (the library has
     # no setters since round 4); no arguments = NULL = every default
