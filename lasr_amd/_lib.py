@@ -7,6 +7,8 @@ infrastructure and is never imported from here.
 import ctypes
 import os
 
+import torch                                        # (first: liblasr_hip.so must bind to the HIP runtime torch bundles, see lib())
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('LASR_HIP_LIB') or os.path.join(_HERE, 'csrc', 'liblasr_hip.so')   # env override: kernel A/B builds
 
@@ -193,7 +195,6 @@ MASKPROP_BINS, MASKPROP_MAX_SIZE, MASKPROP_MAX_RADIUS = 4096, 16384, 8   # LASR_
 TRACK_MAX_SNAP, TRACK_MAX_WINDOW, TRACK_MAX_RADIUS, TRACK_MAX_SIZE, TRACK_SPLAT_ALPHA = 16, 2, 8, 8192, 192   # LASR_TRACK_* of include/lasr_ops.h
 
 
-
 class SrOptions(ctypes.Structure):
     """lasr_sr_options (include/lasr_sr.h): per-call kernel-choice thresholds of the forward pass and the size limit of the
     heaviest-first tile order; a negative field = default."""
@@ -248,8 +249,7 @@ def lib():
                 '(hipcc --offload-arch=gfx950); there is no CPU fallback.' % LIB_PATH)
         # torch bundles its own libamdhip64.so.7; load it FIRST so that this library
         # binds to the same HIP runtime instance (stream handles are only valid
-        # inside the runtime that created them).
-        import torch  # noqa: F401
+        # inside the runtime that created them): the import at the top of this module.
         h = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(h, name)       # AttributeError here == ABI mismatch: let it propagate
@@ -272,12 +272,58 @@ def check(rc, what):
 
 
 def stream_of(t):
-    """(device-guard context, raw hipStream_t) for the tensor's device: kernels go on torch's current stream."""
-    import torch
-    return torch.cuda.device(t.device), torch.cuda.current_stream(t.device).cuda_stream
+    """(device-guard context, raw hipStream_t) for the device of a tensor (or for a torch.device): kernels go on torch's current
+    stream."""
+    dev = getattr(t, 'device', t)
+    return torch.cuda.device(dev), torch.cuda.current_stream(dev).cuda_stream
+
+
+_NEED_CUDA = 'lasr_amd kernels support only cuda (HIP) tensors; there is no CPU fallback'
 
 
 def need_cuda(*tensors):
     for t in tensors:
         if t is not None and t.device.type != 'cuda':
-            raise TypeError('lasr_amd kernels support only cuda (HIP) tensors; there is no CPU fallback')
+            raise TypeError(_NEED_CUDA)
+
+
+def call(name, *args, on=None):
+    """One native launch: lib().<name>(*args, stream), checked.  Tensors go over as their data_ptr(); None, numbers, ctypes
+    objects and plain integers (a pointer computed by hand, a host buffer) go over as they are.  The stream is torch's current
+    one on the device of `on` (a tensor or a torch.device; default: the first tensor of args), read here and passed last, as
+    every streamed entry point of include/*.h takes it.  Refused before the call: a tensor that is not on a GPU (TypeError), a
+    tensor of another GPU than `on` (ValueError), a wrong number of arguments (TypeError; ctypes itself lets surplus ones pass)."""
+    fn = getattr(lib(), name)
+    dev = getattr(on, 'device', on)
+    if dev is not None:
+        if dev.type != 'cuda':
+            raise TypeError(_NEED_CUDA)
+        if dev.index is None:                           # 'cuda' = the current device
+            dev = torch.device('cuda', torch.cuda.current_device())
+    raw = []
+    for a in args:
+        if isinstance(a, torch.Tensor):
+            d = a.device
+            if d != dev:
+                if d.type != 'cuda':
+                    raise TypeError(_NEED_CUDA)
+                if dev is not None:
+                    raise ValueError('%s: a tensor of %s among arguments of %s' % (name, d, dev))
+                dev = d
+            a = a.data_ptr()
+        raw.append(a)
+    if len(raw) + 1 != len(fn.argtypes):
+        raise TypeError('%s takes %d arguments and the stream, %d given' % (name, len(fn.argtypes) - 1, len(raw)))
+    if dev is None:
+        raise TypeError('%s: no tensor among the arguments, say on= which device' % name)
+    guard, st = stream_of(dev)
+    with guard:
+        rc = fn(*raw, st)
+    if rc != 0:
+        check(rc, name)
+
+
+def f32(*tensors):
+    """.contiguous().float() of each tensor (None stays None): one value for one argument, a tuple for several."""
+    out = tuple(None if t is None else t.contiguous().float() for t in tensors)
+    return out[0] if len(out) == 1 else out

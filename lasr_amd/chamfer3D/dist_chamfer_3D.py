@@ -28,12 +28,12 @@ def nn_tiled(a, b, R=None, T=None, splits=0):
     _lib.need_cuda(a, b, R, T)
     if (R is None) != (T is None):
         raise ValueError('R and T come together')
-    a, b = a.detach().contiguous().float(), b.detach().contiguous().float()
+    a, b = _lib.f32(a.detach(), b.detach())
     if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3 or a.shape[0] != b.shape[0]:
         raise ValueError('expected a [N,P,3] and b [N,Q,3], got %s and %s' % (tuple(a.shape), tuple(b.shape)))
     N, P, Q = a.shape[0], a.shape[1], b.shape[1]
     if R is not None:
-        R, T = R.detach().contiguous().float(), T.detach().contiguous().float()
+        R, T = _lib.f32(R.detach(), T.detach())
         if R.shape != (N, 3, 3) or T.shape != (N, 3):
             raise ValueError('expected R [N,3,3] and T [N,3]')
     h = _lib.lib()
@@ -41,11 +41,7 @@ def nn_tiled(a, b, R=None, T=None, splits=0):
     idx = torch.empty(N, P, dtype=torch.int32, device=a.device)
     nbytes = h.lasr_chamfer3d_workspace_bytes(N, P, 0)
     ws = _workspace(nbytes, a.device)
-    guard, st = _lib.stream_of(a)
-    with guard:
-        rc = h.lasr_nn_tiled(a.data_ptr(), b.data_ptr(), R.data_ptr() if R is not None else None, T.data_ptr() if T is not None else None,
-                             d2.data_ptr(), idx.data_ptr(), ws.data_ptr(), nbytes, N, P, Q, splits, st)
-    _lib.check(rc, 'lasr_nn_tiled')
+    _lib.call('lasr_nn_tiled', a, b, R, T, d2, idx, ws, nbytes, N, P, Q, splits)
     return d2, idx
 
 
@@ -64,7 +60,7 @@ class chamfer_3DFunction(Function):
         _lib.need_cuda(xyz1, xyz2)
         if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[2] != 3 or xyz2.shape[2] != 3 or xyz1.shape[0] != xyz2.shape[0]:
             raise ValueError('expected [N,P,3] and [N,Q,3], got %s and %s' % (tuple(xyz1.shape), tuple(xyz2.shape)))
-        x1, x2 = xyz1.detach().contiguous().float(), xyz2.detach().contiguous().float()
+        x1, x2 = _lib.f32(xyz1.detach(), xyz2.detach())
         N, P, Q = x1.shape[0], x1.shape[1], x2.shape[1]
         dev = x1.device
         h = _lib.lib()
@@ -72,11 +68,7 @@ class chamfer_3DFunction(Function):
         idx1, idx2 = torch.empty(N, P, dtype=torch.int32, device=dev), torch.empty(N, Q, dtype=torch.int32, device=dev)
         nbytes = h.lasr_chamfer3d_workspace_bytes(N, P, Q)
         ws = _workspace(nbytes, dev)
-        guard, st = _lib.stream_of(x1)
-        with guard:
-            rc = h.lasr_chamfer3d_forward(x1.data_ptr(), x2.data_ptr(), dist1.data_ptr(), dist2.data_ptr(), idx1.data_ptr(),
-                                          idx2.data_ptr(), ws.data_ptr(), nbytes, N, P, Q, splits, st)
-        _lib.check(rc, 'lasr_chamfer3d_forward')
+        _lib.call('lasr_chamfer3d_forward', x1, x2, dist1, dist2, idx1, idx2, ws, nbytes, N, P, Q, splits)
         ctx.save_for_backward(x1, x2, idx1, idx2)
         ctx.mark_non_differentiable(idx1, idx2)
         return dist1, dist2, idx1, idx2
@@ -90,12 +82,7 @@ class chamfer_3DFunction(Function):
         row_ptr1, col1 = _inverse_csr(idx2, P)                  # per xyz1 point: the xyz2 points that chose it
         row_ptr2, col2 = _inverse_csr(idx1, Q)
         gx1, gx2 = torch.empty_like(x1), torch.empty_like(x2)
-        guard, st = _lib.stream_of(x1)
-        with guard:
-            rc = _lib.lib().lasr_chamfer3d_backward(x1.data_ptr(), x2.data_ptr(), idx1.data_ptr(), idx2.data_ptr(), g1.data_ptr(),
-                                                    g2.data_ptr(), row_ptr1.data_ptr(), col1.data_ptr(), row_ptr2.data_ptr(),
-                                                    col2.data_ptr(), gx1.data_ptr(), gx2.data_ptr(), N, P, Q, st)
-        _lib.check(rc, 'lasr_chamfer3d_backward')
+        _lib.call('lasr_chamfer3d_backward', x1, x2, idx1, idx2, g1, g2, row_ptr1, col1, row_ptr2, col2, gx1, gx2, N, P, Q)
         return gx1, gx2, None
 
 

@@ -77,9 +77,6 @@ class PackedTable:
             for o, n, oo in zip(self.seg_off, self.seg_len, self.out_off):
                 self.out[oo:oo + B * n] = sel[:, o:o + n].reshape(-1)
             return self.views
-        guard, st = _lib.stream_of(self.table)
-        with guard:
-            rc = _lib.lib().lasr_gather_rows(self.table.data_ptr(), self.W, self.n_pairs, ids.data_ptr(), B, len(self.keys),
-                                             self._c[0], self._c[1], self._c[2], self.out.data_ptr(), st)
-        _lib.check(rc, 'lasr_gather_rows')
+        _lib.call('lasr_gather_rows', self.table, self.W, self.n_pairs, ids, B, len(self.keys), self._c[0], self._c[1], self._c[2],
+                  self.out)
         return self.views

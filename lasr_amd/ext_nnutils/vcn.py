@@ -42,14 +42,8 @@ def corr_proj(c1, c2, flow, weight, scale, shift, md, mdv):
     flow = None if flow is None else flow.to(**f32).contiguous()
     weight, scale, shift = (t.detach().to(**f32).contiguous() for t in (weight, scale, shift))
     out = torch.empty(b, Fo, 2 * md + 1, 2 * mdv + 1, h, w, **f32)
-    h_ = _lib.lib()
-    ws = torch.empty(max(int(h_.lasr_vcn_corr_proj_workspace_bytes(b, h, w)), 4) // 4, **f32)
-    guard, st = _lib.stream_of(c1)
-    with guard:
-        rc = h_.lasr_vcn_corr_proj(c1.data_ptr(), c2.data_ptr(), flow.data_ptr() if flow is not None else None,
-                                   weight.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                   ws.numel() * 4, b, C, Fo, h, w, int(md), int(mdv), st)
-    _lib.check(rc, 'lasr_vcn_corr_proj')
+    ws = torch.empty(max(int(_lib.lib().lasr_vcn_corr_proj_workspace_bytes(b, h, w)), 4) // 4, **f32)
+    _lib.call('lasr_vcn_corr_proj', c1, c2, flow, weight, scale, shift, out, ws, ws.numel() * 4, b, C, Fo, h, w, int(md), int(mdv))
     return out
 
 
@@ -65,11 +59,7 @@ def flow_reg(cost, up_flow, md, mdv):
     up_flow = None if up_flow is None else up_flow.to(**f32).contiguous()
     flow = torch.empty(b, 2 * Fo, h, w, **f32)
     ent = torch.empty(b, 2 * Fo, h, w, **f32)
-    guard, st = _lib.stream_of(cost)
-    with guard:
-        rc = _lib.lib().lasr_vcn_flow_reg(cost.data_ptr(), up_flow.data_ptr() if up_flow is not None else None, flow.data_ptr(),
-                                          ent.data_ptr(), b, Fo, h, w, int(md), int(mdv), st)
-    _lib.check(rc, 'lasr_vcn_flow_reg')
+    _lib.call('lasr_vcn_flow_reg', cost, up_flow, flow, ent, b, Fo, h, w, int(md), int(mdv))
     return flow, ent
 
 

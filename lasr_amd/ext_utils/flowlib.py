@@ -52,9 +52,5 @@ def flow_to_image(flow, mask=None):
         m = m.detach().float().contiguous()
     out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=t.device)
     if out.numel():
-        guard, st = _lib.stream_of(t)
-        with guard:
-            rc = _lib.lib().lasr_flow_to_image(t.data_ptr(), m.data_ptr() if m is not None else None, out.data_ptr(),
-                                               _stats_scratch(t.device, B).data_ptr(), B, H, W, C, st)
-        _lib.check(rc, 'lasr_flow_to_image')
+        _lib.call('lasr_flow_to_image', t, m, out, _stats_scratch(t.device, B), B, H, W, C)
     return out[0].cpu().numpy() if is_np else out

@@ -38,8 +38,7 @@ def face_index_raster(verts, faces, K, IS):
     """Hard-mode raster of N frames -> aggrs_info [N,2,IS,IS] (plane 1: nearest face per pixel or -1)."""
     near, far = depth_range(verts)
     fv = ndc_vertices(verts, K, IS)[:, faces.long()].contiguous()
-    stream = torch.cuda.current_stream(verts.device).cuda_stream
-    return vis._raster(_lib.lib(), fv, IS, near, far, stream)
+    return vis.hard_raster(fv, IS, near, far)
 
 
 def bake_texture(verts, faces, K, frames, masks=None, texture_res=8, power=2, fallback=None):
@@ -92,20 +91,13 @@ def bake_texture(verts, faces, K, frames, masks=None, texture_res=8, power=2, fa
     weight = torch.empty(F, R * R, dtype=torch.float32, device=dev)
     if F == 0:
         return textures, weight
-    h = _lib.lib()
-    guard, stream = _lib.stream_of(verts)
-    with guard:
-        for i in range(0, T, CHUNK_FRAMES):
-            j = min(i + CHUNK_FRAMES, T)
-            v, k, fr = verts[i:j], K[i:j], frames[i:j]
-            raster = face_index_raster(v, faces32, k, IS)
-            rc = h.lasr_bake_accumulate(v.data_ptr(), faces32.data_ptr(), k.data_ptr(), raster.data_ptr(), fr.data_ptr(),
-                                        masks[i:j].data_ptr() if masks is not None else None, accum.data_ptr(), j - i, V, F, R,
-                                        IS, H, W, power, stream)
-            _lib.check(rc, 'lasr_bake_accumulate')
-        rc = h.lasr_bake_resolve(accum.data_ptr(), faces32.data_ptr(), fallback.data_ptr() if fallback is not None else None,
-                                 textures.data_ptr(), weight.data_ptr(), V, F, R, stream)
-        _lib.check(rc, 'lasr_bake_resolve')
+    for i in range(0, T, CHUNK_FRAMES):
+        j = min(i + CHUNK_FRAMES, T)
+        v, k, fr = verts[i:j], K[i:j], frames[i:j]
+        raster = face_index_raster(v, faces32, k, IS)
+        _lib.call('lasr_bake_accumulate', v, faces32, k, raster, fr, masks[i:j] if masks is not None else None, accum, j - i, V, F, R,
+                  IS, H, W, power)
+    _lib.call('lasr_bake_resolve', accum, faces32, fallback, textures, weight, V, F, R)
     return textures, weight
 
 

@@ -2,6 +2,8 @@
 
 Each function replaces a run of eager elementwise ops of the reference (file:line in its docstring) and has a torch
 restatement in oracle/path_oracle.py that the GPU tests compare against."""
+import ctypes
+
 import torch
 from torch.autograd import Function
 
@@ -14,16 +16,12 @@ class _FlowReproject(Function):
         _lib.need_cuda(px, pp0, pp1, fl0, fl1)
         N = px.shape[0]
         P = px[0, 0].numel()
-        px = px.contiguous().float()
-        pp0, pp1 = pp0.contiguous().float(), pp1.contiguous().float()
-        fl0, fl1 = fl0.contiguous().float(), fl1.contiguous().float()
+        px = _lib.f32(px)
+        pp0, pp1 = _lib.f32(pp0, pp1)
+        fl0, fl1 = _lib.f32(fl0, fl1)
         flow = torch.empty(px.shape[0], *px.shape[2:], 2, dtype=torch.float32, device=px.device)
         bg = torch.empty(px.shape[0], *px.shape[2:], dtype=torch.uint8, device=px.device)
-        guard, st = _lib.stream_of(px)
-        with guard:
-            rc = _lib.lib().lasr_flow_reproject_forward(px.data_ptr(), pp0.data_ptr(), pp1.data_ptr(), fl0.data_ptr(),
-                                                        fl1.data_ptr(), flow.data_ptr(), bg.data_ptr(), N, P, st)
-        _lib.check(rc, 'lasr_flow_reproject_forward')
+        _lib.call('lasr_flow_reproject_forward', px, pp0, pp1, fl0, fl1, flow, bg, N, P)
         ctx.save_for_backward(px, fl1)
         bg = bg.view(torch.bool)
         ctx.mark_non_differentiable(bg)
@@ -34,17 +32,12 @@ class _FlowReproject(Function):
         px, fl1 = ctx.saved_tensors
         N = px.shape[0]
         P = px[0, 0].numel()
-        gflow = gflow.contiguous().float()
+        gflow = _lib.f32(gflow)
         gpx = torch.empty_like(px)
         gpp1 = torch.empty(N, 2, dtype=torch.float32, device=px.device)
         gfl1 = torch.empty(N, dtype=torch.float32, device=px.device)
-        h = _lib.lib()
-        scratch = torch.empty(h.lasr_flow_reproject_scratch_floats(N, P), dtype=torch.float32, device=px.device)
-        guard, st = _lib.stream_of(px)
-        with guard:
-            rc = h.lasr_flow_reproject_backward(px.data_ptr(), fl1.data_ptr(), gflow.data_ptr(), gpx.data_ptr(),
-                                                gpp1.data_ptr(), gfl1.data_ptr(), scratch.data_ptr(), N, P, st)
-        _lib.check(rc, 'lasr_flow_reproject_backward')
+        scratch = torch.empty(_lib.lib().lasr_flow_reproject_scratch_floats(N, P), dtype=torch.float32, device=px.device)
+        _lib.call('lasr_flow_reproject_backward', px, fl1, gflow, gpx, gpp1, gfl1, scratch, N, P)
         return gpx, None, gpp1, None, gfl1
 
 
@@ -63,15 +56,11 @@ class _FlowReprojectPlanes(Function):
         if pos6.dtype != torch.float32 or pos6.shape[1] != 6 or (N > 0 and not pos6[0].is_contiguous()):
             raise ValueError('pos6 must be float32 [N,6,IS,IS] with the six planes of an image contiguous')
         stride = pos6.stride(0) if N > 1 else 6 * P
-        pp0, pp1 = pp0.contiguous().float(), pp1.contiguous().float()
-        fl0, fl1 = fl0.contiguous().float(), fl1.contiguous().float()
+        pp0, pp1 = _lib.f32(pp0, pp1)
+        fl0, fl1 = _lib.f32(fl0, fl1)
         flow = torch.empty(N, *pos6.shape[2:], 2, dtype=torch.float32, device=pos6.device)
         bg = torch.empty(N, *pos6.shape[2:], dtype=torch.uint8, device=pos6.device)
-        guard, st = _lib.stream_of(pos6)
-        with guard:
-            rc = _lib.lib().lasr_flow_reproject_planes_forward(pos6.data_ptr(), stride, pp0.data_ptr(), pp1.data_ptr(), fl0.data_ptr(),
-                                                               fl1.data_ptr(), flow.data_ptr(), bg.data_ptr(), N, P, st)
-        _lib.check(rc, 'lasr_flow_reproject_planes_forward')
+        _lib.call('lasr_flow_reproject_planes_forward', pos6, stride, pp0, pp1, fl0, fl1, flow, bg, N, P)
         ctx.save_for_backward(pos6, fl1)
         ctx.stride = stride
         bg = bg.view(torch.bool)
@@ -82,17 +71,12 @@ class _FlowReprojectPlanes(Function):
     def backward(ctx, gflow, _gbg):
         pos6, fl1 = ctx.saved_tensors
         N, P = pos6.shape[0], pos6[0, 0].numel()
-        gflow = gflow.contiguous().float()
+        gflow = _lib.f32(gflow)
         gpos = torch.empty(pos6.shape, dtype=torch.float32, device=pos6.device)
         gpp1 = torch.empty(N, 2, dtype=torch.float32, device=pos6.device)
         gfl1 = torch.empty(N, dtype=torch.float32, device=pos6.device)
-        h = _lib.lib()
-        scratch = torch.empty(h.lasr_flow_reproject_scratch_floats(N, P), dtype=torch.float32, device=pos6.device)
-        guard, st = _lib.stream_of(pos6)
-        with guard:
-            rc = h.lasr_flow_reproject_planes_backward(pos6.data_ptr(), ctx.stride, fl1.data_ptr(), gflow.data_ptr(), gpos.data_ptr(),
-                                                       gpp1.data_ptr(), gfl1.data_ptr(), scratch.data_ptr(), N, P, st)
-        _lib.check(rc, 'lasr_flow_reproject_planes_backward')
+        scratch = torch.empty(_lib.lib().lasr_flow_reproject_scratch_floats(N, P), dtype=torch.float32, device=pos6.device)
+        _lib.call('lasr_flow_reproject_planes_backward', pos6, ctx.stride, fl1, gflow, gpos, gpp1, gfl1, scratch, N, P)
         return gpos, None, gpp1, None, gfl1
 
 
@@ -107,30 +91,25 @@ class _RenderTables(Function):
         if px.dtype != torch.float32 or px.shape[1] != 10 or N != I * H or obspair.shape[0] != (I if from_imgs else 2 * I):
             raise ValueError('px must be float32 [I*H,10,IS,IS], obspair [2I,3,IS,IS] (or the images [I,3,IS,IS])')
         px = px.contiguous()
-        masks, occ, flow_obs = masks.contiguous().float(), occ.contiguous().float(), flow_obs.contiguous().float()
-        obspair, pp, fl = obspair.detach().contiguous().float(), pp.contiguous().float(), fl.contiguous().float()
+        masks, occ, flow_obs = _lib.f32(masks, occ, flow_obs)
+        obspair, pp, fl = _lib.f32(obspair.detach(), pp, fl)
         imgs = obspair if from_imgs else None
         if from_imgs:                                      # the pair is formed by the pass itself (lasr_render_tables_forward_imgs)
             obspair = torch.empty(2 * I, *imgs.shape[1:], dtype=torch.float32, device=px.device)
         dev, hw = px.device, px.shape[2:]
-        h = _lib.lib()
         tabs = torch.empty(3, I, H, dtype=torch.float32, device=dev)
         flow = torch.empty(N, *hw, 2, dtype=torch.float32, device=dev)
         bg = torch.empty(N, *hw, dtype=torch.uint8, device=dev)
         fmap = torch.empty(N, *hw, dtype=torch.float32, device=dev)
         vis = torch.empty(N, *hw, dtype=torch.uint8, device=dev)
         pair = torch.empty(2 * N, 3, *hw, dtype=torch.float32, device=dev) if want_pair else None
-        scratch = torch.empty(h.lasr_render_tables_scratch_floats(I, H, P), dtype=torch.float32, device=dev)
-        guard, st = _lib.stream_of(px)
-        with guard:
-            tail = (pp.data_ptr(), fl.data_ptr(), float(wt), tabs[0].data_ptr(), tabs[1].data_ptr(), tabs[2].data_ptr(), flow.data_ptr(),
-                    bg.data_ptr(), fmap.data_ptr(), vis.data_ptr(), pair.data_ptr() if want_pair else None, scratch.data_ptr(), I, H, P, st)
-            head = (px.data_ptr(), masks.data_ptr(), occ.data_ptr(), flow_obs.data_ptr(), flow_obs[0].numel())
-            if from_imgs:
-                rc = h.lasr_render_tables_forward_imgs(*head, imgs.data_ptr(), obspair.data_ptr(), *tail)
-            else:
-                rc = h.lasr_render_tables_forward(*head, obspair.data_ptr(), obspair[I:].data_ptr(), *tail)
-        _lib.check(rc, 'lasr_render_tables_forward')
+        scratch = torch.empty(_lib.lib().lasr_render_tables_scratch_floats(I, H, P), dtype=torch.float32, device=dev)
+        head = (px, masks, occ, flow_obs, flow_obs[0].numel())
+        tail = (pp, fl, float(wt), tabs[0], tabs[1], tabs[2], flow, bg, fmap, vis, pair, scratch, I, H, P)
+        if from_imgs:
+            _lib.call('lasr_render_tables_forward_imgs', *head, imgs, obspair, *tail)
+        else:
+            _lib.call('lasr_render_tables_forward', *head, obspair, obspair[I:], *tail)
         ctx.save_for_backward(px, masks, occ, flow_obs, obspair, pp, fl, scratch)
         ctx.wt, ctx.geom = float(wt), (I, H, P)
         ctx.from_imgs, ctx.want_pair = bool(from_imgs), bool(want_pair)
@@ -160,18 +139,12 @@ class _RenderTables(Function):
                 return zero
             return g.contiguous().float()
         g_mask, g_flow, g_tex = tab(g_mask), tab(g_flow), tab(g_tex)
-        g_pair = g_pair.contiguous().float() if g_pair is not None else None
+        g_pair = _lib.f32(g_pair)
         gpx = torch.empty_like(px)
         gpp = torch.empty_like(pp)
         gfl = torch.empty_like(fl)
-        guard, st = _lib.stream_of(px)
-        with guard:
-            rc = _lib.lib().lasr_render_tables_backward(
-                px.data_ptr(), masks.data_ptr(), occ.data_ptr(), flow_obs.data_ptr(), flow_obs[0].numel(), obspair.data_ptr(),
-                obspair[I:].data_ptr(), pp.data_ptr(), fl.data_ptr(), ctx.wt, g_mask.data_ptr(), g_flow.data_ptr(), g_tex.data_ptr(),
-                g_pair.data_ptr() if g_pair is not None else None, scratch.data_ptr(), gpx.data_ptr(), gpp.data_ptr(),
-                gfl.data_ptr(), I, H, P, st)
-        _lib.check(rc, 'lasr_render_tables_backward')
+        _lib.call('lasr_render_tables_backward', px, masks, occ, flow_obs, flow_obs[0].numel(), obspair, obspair[I:], pp, fl, ctx.wt,
+                  g_mask, g_flow, g_tex, g_pair, scratch, gpx, gpp, gfl, I, H, P)
         return gpx, None, None, None, None, gpp, gfl, None, None, None
 
 
@@ -196,21 +169,16 @@ class _RasterInputs(Function):
     @staticmethod
     def forward(ctx, verts_cam, tex, pp, fl, eye):
         _lib.need_cuda(verts_cam, tex, pp, fl)
-        import ctypes
         N, V = verts_cam.shape[:2]
-        verts_cam, tex = verts_cam.contiguous().float(), tex.contiguous().float()
-        pp, fl = pp.contiguous().float(), fl.contiguous().float()
+        verts_cam, tex = _lib.f32(verts_cam, tex)
+        pp, fl = _lib.f32(pp, fl)
         dev = verts_cam.device
         pre = torch.empty(N, V, 3, dtype=torch.float32, device=dev)
         attrs = torch.empty(N, V, 9, dtype=torch.float32, device=dev)
         nf = torch.empty(2, dtype=torch.float32, device=dev)
         scratch = torch.empty(2 * N, dtype=torch.float32, device=dev)
-        guard, st = _lib.stream_of(verts_cam)
-        with guard:
-            rc = _lib.lib().lasr_raster_inputs_forward(verts_cam.data_ptr(), tex.data_ptr(), pp.data_ptr(), fl.data_ptr(),
-                                                       (ctypes.c_float * 3)(*[float(e) for e in eye]), pre.data_ptr(),
-                                                       attrs.data_ptr(), nf.data_ptr(), scratch.data_ptr(), N, V, st)
-        _lib.check(rc, 'lasr_raster_inputs_forward')
+        _lib.call('lasr_raster_inputs_forward', verts_cam, tex, pp, fl, (ctypes.c_float * 3)(*[float(e) for e in eye]), pre, attrs, nf,
+                  scratch, N, V)
         ctx.save_for_backward(verts_cam, fl)
         ctx.mark_non_differentiable(nf)
         return pre, attrs, nf
@@ -224,11 +192,7 @@ class _RasterInputs(Function):
         g_attrs = g_attrs.contiguous().float() if g_attrs is not None else torch.zeros(N, V, 9, device=dev)
         g_cam, g_tex = torch.empty_like(verts_cam), torch.empty_like(verts_cam)
         g_pp, g_fl = torch.empty(N, 2, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
-        guard, st = _lib.stream_of(verts_cam)
-        with guard:
-            rc = _lib.lib().lasr_raster_inputs_backward(verts_cam.data_ptr(), fl.data_ptr(), g_pre.data_ptr(), g_attrs.data_ptr(),
-                                                        g_cam.data_ptr(), g_tex.data_ptr(), g_pp.data_ptr(), g_fl.data_ptr(), N, V, st)
-        _lib.check(rc, 'lasr_raster_inputs_backward')
+        _lib.call('lasr_raster_inputs_backward', verts_cam, fl, g_pre, g_attrs, g_cam, g_tex, g_pp, g_fl, N, V)
         return g_cam, g_tex, g_pp, g_fl, None
 
 
@@ -259,11 +223,10 @@ def face_incidence(faces, num_vertices):
 class _RasterFaces(Function):
     @staticmethod
     def forward(ctx, verts_cam, tex, pp, fl, eye, faces, inc_ptr, inc):
-        import ctypes
         _lib.need_cuda(verts_cam, tex, pp, fl, faces, inc_ptr, inc)
         N, V = verts_cam.shape[:2]
-        verts_cam, tex = verts_cam.contiguous().float(), tex.contiguous().float()
-        pp, fl = pp.contiguous().float(), fl.contiguous().float()
+        verts_cam, tex = _lib.f32(verts_cam, tex)
+        pp, fl = _lib.f32(pp, fl)
         faces = faces.contiguous().long()
         shared = int(faces.shape[0] == 1 and N != 1)
         if faces.shape[0] not in (1, N) or inc_ptr.shape[0] != faces.shape[0] or inc.shape[0] != faces.shape[0]:
@@ -277,17 +240,12 @@ class _RasterFaces(Function):
                              '(got %s %s and %s %s for V = %d, F = %d)' % (inc_ptr.dtype, tuple(inc_ptr.shape), inc.dtype,
                                                                             tuple(inc.shape), V, F_))
         dev = verts_cam.device
-        h = _lib.lib()
         fv = torch.empty(N, F_, 3, 3, dtype=torch.float32, device=dev)
         fa = torch.empty(N, F_, 3, 9, dtype=torch.float32, device=dev)
         nf = torch.empty(2, dtype=torch.float32, device=dev)
-        scratch = torch.empty(h.lasr_raster_faces_scratch_floats(N, V, F_), dtype=torch.float32, device=dev)
-        guard, st = _lib.stream_of(verts_cam)
-        with guard:
-            rc = h.lasr_raster_faces_forward(verts_cam.data_ptr(), tex.data_ptr(), pp.data_ptr(), fl.data_ptr(),
-                                             (ctypes.c_float * 3)(*[float(e) for e in eye]), faces.data_ptr(), shared,
-                                             fv.data_ptr(), fa.data_ptr(), nf.data_ptr(), scratch.data_ptr(), N, V, F_, st)
-        _lib.check(rc, 'lasr_raster_faces_forward')
+        scratch = torch.empty(_lib.lib().lasr_raster_faces_scratch_floats(N, V, F_), dtype=torch.float32, device=dev)
+        _lib.call('lasr_raster_faces_forward', verts_cam, tex, pp, fl, (ctypes.c_float * 3)(*[float(e) for e in eye]), faces, shared,
+                  fv, fa, nf, scratch, N, V, F_)
         ctx.save_for_backward(verts_cam, fl, inc_ptr, inc)
         ctx.dims = (N, V, F_, shared)
         ctx.mark_non_differentiable(nf)
@@ -302,14 +260,9 @@ class _RasterFaces(Function):
         g_fa = g_fa.contiguous().float() if g_fa is not None else torch.zeros(N, F_, 3, 9, device=dev)
         g_cam, g_tex = torch.empty_like(verts_cam), torch.empty_like(verts_cam)
         g_pp, g_fl = torch.empty(N, 2, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
-        h = _lib.lib()
-        scratch = torch.empty(h.lasr_raster_faces_scratch_floats(N, V, F_), dtype=torch.float32, device=dev)
-        guard, st = _lib.stream_of(verts_cam)
-        with guard:
-            rc = h.lasr_raster_faces_backward(verts_cam.data_ptr(), fl.data_ptr(), inc_ptr.data_ptr(), inc.data_ptr(), shared,
-                                              g_fv.data_ptr(), g_fa.data_ptr(), g_cam.data_ptr(), g_tex.data_ptr(),
-                                              g_pp.data_ptr(), g_fl.data_ptr(), scratch.data_ptr(), N, V, F_, st)
-        _lib.check(rc, 'lasr_raster_faces_backward')
+        scratch = torch.empty(_lib.lib().lasr_raster_faces_scratch_floats(N, V, F_), dtype=torch.float32, device=dev)
+        _lib.call('lasr_raster_faces_backward', verts_cam, fl, inc_ptr, inc, shared, g_fv, g_fa, g_cam, g_tex, g_pp, g_fl, scratch, N,
+                  V, F_)
         return g_cam, g_tex, g_pp, g_fl, None, None, None, None
 
 
@@ -331,25 +284,19 @@ class _QuatToRotmat(Function):
     @staticmethod
     def forward(ctx, q):
         _lib.need_cuda(q)
-        q = q.contiguous().float()
+        q = _lib.f32(q)
         M = q.shape[0]
         R = torch.empty(M, 9, dtype=torch.float32, device=q.device)
-        guard, st = _lib.stream_of(q)
-        with guard:
-            rc = _lib.lib().lasr_quat_to_rotmat_forward(q.data_ptr(), R.data_ptr(), M, st)
-        _lib.check(rc, 'lasr_quat_to_rotmat_forward')
+        _lib.call('lasr_quat_to_rotmat_forward', q, R, M)
         ctx.save_for_backward(q)
         return R
 
     @staticmethod
     def backward(ctx, gR):
         q, = ctx.saved_tensors
-        gR = gR.contiguous().float()
+        gR = _lib.f32(gR)
         gq = torch.empty_like(q)
-        guard, st = _lib.stream_of(q)
-        with guard:
-            rc = _lib.lib().lasr_quat_to_rotmat_backward(q.data_ptr(), gR.data_ptr(), gq.data_ptr(), q.shape[0], st)
-        _lib.check(rc, 'lasr_quat_to_rotmat_backward')
+        _lib.call('lasr_quat_to_rotmat_backward', q, gR, gq, q.shape[0])
         return gq
 
 
@@ -365,13 +312,9 @@ class _SkinWeights(Function):
         _lib.need_cuda(ts, rs, lc, verts)
         H, V = verts.shape[:2]
         J = ts.shape[0] // H
-        ts, rs, lc, verts = (t.contiguous().float() for t in (ts, rs, lc, verts))
+        ts, rs, lc, verts = _lib.f32(ts, rs, lc, verts)
         skin = torch.empty(H, J, V, dtype=torch.float32, device=ts.device)
-        guard, st = _lib.stream_of(ts)
-        with guard:
-            rc = _lib.lib().lasr_skin_weights_forward(ts.data_ptr(), rs.data_ptr(), lc.data_ptr(), verts.data_ptr(),
-                                                      skin.data_ptr(), H, J, V, st)
-        _lib.check(rc, 'lasr_skin_weights_forward')
+        _lib.call('lasr_skin_weights_forward', ts, rs, lc, verts, skin, H, J, V)
         ctx.save_for_backward(ts, rs, lc, verts, skin)
         return skin
 
@@ -379,15 +322,10 @@ class _SkinWeights(Function):
     def backward(ctx, g):
         ts, rs, lc, verts, skin = ctx.saved_tensors
         H, J, V = skin.shape
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         gts, grs, glc = torch.empty_like(ts), torch.empty_like(rs), torch.empty_like(lc)
         scratch = torch.empty(H * V + 1, dtype=torch.float32, device=ts.device)
-        guard, st = _lib.stream_of(ts)
-        with guard:
-            rc = _lib.lib().lasr_skin_weights_backward(ts.data_ptr(), rs.data_ptr(), lc.data_ptr(), verts.data_ptr(),
-                                                       skin.data_ptr(), g.data_ptr(), gts.data_ptr(), grs.data_ptr(),
-                                                       glc.data_ptr(), scratch.data_ptr(), H, J, V, st)
-        _lib.check(rc, 'lasr_skin_weights_backward')
+        _lib.call('lasr_skin_weights_backward', ts, rs, lc, verts, skin, g, gts, grs, glc, scratch, H, J, V)
         return gts, grs, glc, None
 
 
@@ -401,14 +339,11 @@ class _Flatten(Function):
     @staticmethod
     def forward(ctx, x, quads, inc_ptr, inc):
         _lib.need_cuda(x, quads, inc_ptr, inc)
-        x = x.contiguous().float()
+        x = _lib.f32(x)
         N, V = x.shape[:2]
         E = quads.shape[0]
         loss = torch.empty(N, dtype=torch.float32, device=x.device)
-        guard, st = _lib.stream_of(x)
-        with guard:
-            rc = _lib.lib().lasr_flatten_forward(x.data_ptr(), quads.data_ptr(), loss.data_ptr(), N, V, E, st)
-        _lib.check(rc, 'lasr_flatten_forward')
+        _lib.call('lasr_flatten_forward', x, quads, loss, N, V, E)
         ctx.save_for_backward(x, quads, inc_ptr, inc)
         return loss
 
@@ -417,14 +352,10 @@ class _Flatten(Function):
         x, quads, inc_ptr, inc = ctx.saved_tensors
         N, V = x.shape[:2]
         E = quads.shape[0]
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         gx = torch.empty_like(x)
         scratch = torch.empty(N * E * 12 + 1, dtype=torch.float32, device=x.device)
-        guard, st = _lib.stream_of(x)
-        with guard:
-            rc = _lib.lib().lasr_flatten_backward(x.data_ptr(), quads.data_ptr(), inc_ptr.data_ptr(), inc.data_ptr(),
-                                                  g.data_ptr(), gx.data_ptr(), scratch.data_ptr(), N, V, E, st)
-        _lib.check(rc, 'lasr_flatten_backward')
+        _lib.call('lasr_flatten_backward', x, quads, inc_ptr, inc, g, gx, scratch, N, V, E)
         return gx, None, None, None
 
 
@@ -437,7 +368,7 @@ class _MeshReg(Function):
     @staticmethod
     def forward(ctx, x, dx, ax, ca, cb, lap_ptr, lap_col, arap_ptr, arap_col, quads, inc_ptr, inc):
         _lib.need_cuda(x, dx, ax, lap_ptr, lap_col, arap_ptr, arap_col, quads, inc_ptr, inc)
-        x, dx, ax = x.contiguous().float(), dx.contiguous().float(), ax.contiguous().float()
+        x, dx, ax = _lib.f32(x, dx, ax)
         N, V = x.shape[:2]
         NA, E = dx.shape[0], quads.shape[0]
         if dx.shape != ax.shape or (NA and dx.shape[1] != V):
@@ -447,20 +378,14 @@ class _MeshReg(Function):
         nn = None
         if ca is not None:
             _lib.need_cuda(ca, cb)
-            ca, cb = ca.contiguous().float(), cb.contiguous().float()
+            ca, cb = _lib.f32(ca, cb)
             NC, P, Q = ca.shape[0], ca.shape[1], cb.shape[1]
             nn = torch.empty(NC * (P + Q), dtype=torch.int32, device=dev)
         out = torch.empty(2 * N + NA + NC, dtype=torch.float32, device=dev)
         lx = torch.empty_like(x)
-        ptr = lambda t_: t_.data_ptr() if t_ is not None else None            # noqa: E731
-        guard, st = _lib.stream_of(x)
-        with guard:
-            rc = _lib.lib().lasr_step_regularisers_forward(
-                x.data_ptr(), dx.data_ptr(), ax.data_ptr(), lap_ptr.data_ptr(), lap_col.data_ptr(), arap_ptr.data_ptr(), arap_col.data_ptr(),
-                quads.data_ptr(), out.data_ptr(), lx.data_ptr(), out[N:].data_ptr(), out[2 * N:].data_ptr(), N, NA, V, E,
-                ptr(ca), ptr(cb), out[2 * N + NA:].data_ptr() if NC else None, ptr(nn), (nn.data_ptr() + 4 * NC * P) if NC else None,
-                NC, P, Q, st)
-        _lib.check(rc, 'lasr_step_regularisers_forward')
+        _lib.call('lasr_step_regularisers_forward', x, dx, ax, lap_ptr, lap_col, arap_ptr, arap_col, quads, out, lx, out[N:],
+                  out[2 * N:], N, NA, V, E, ca, cb, out[2 * N + NA:] if NC else None, nn, nn[NC * P:] if NC else None,
+                  NC, P, Q)
         ctx.save_for_backward(x, dx, ax, lx, lap_ptr, lap_col, arap_ptr, arap_col, quads, inc_ptr, inc, ca, cb, nn)
         if NC:
             return out[:N], out[N:2 * N], out[2 * N:2 * N + NA], out[2 * N + NA:]
@@ -483,15 +408,9 @@ class _MeshReg(Function):
             NC, P, Q = ca.shape[0], ca.shape[1], cb.shape[1]
             g_cham = g_cham.contiguous().float() if g_cham is not None else zeros(NC)
             gca, gcb = torch.empty_like(ca), torch.empty_like(cb)
-        ptr = lambda t_: t_.data_ptr() if t_ is not None else None            # noqa: E731
-        guard, st = _lib.stream_of(x)
-        with guard:
-            rc = _lib.lib().lasr_step_regularisers_backward(
-                x.data_ptr(), dx.data_ptr(), ax.data_ptr(), lap_ptr.data_ptr(), lap_col.data_ptr(), arap_ptr.data_ptr(), arap_col.data_ptr(),
-                quads.data_ptr(), inc_ptr.data_ptr(), inc.data_ptr(), lx.data_ptr(), g_lap.data_ptr(), g_flat.data_ptr(), g_arap.data_ptr(),
-                gx.data_ptr(), gdx.data_ptr(), gax.data_ptr(), N, NA, V, E, ptr(ca), ptr(cb), ptr(nn),
-                (nn.data_ptr() + 4 * NC * P) if NC else None, ptr(g_cham) if NC else None, ptr(gca), ptr(gcb), NC, P, Q, st)
-        _lib.check(rc, 'lasr_step_regularisers_backward')
+        _lib.call('lasr_step_regularisers_backward', x, dx, ax, lap_ptr, lap_col, arap_ptr, arap_col, quads, inc_ptr, inc, lx, g_lap,
+                  g_flat, g_arap, gx, gdx, gax, N, NA, V, E, ca, cb, nn, nn[NC * P:] if NC else None,
+                  g_cham if NC else None, gca, gcb, NC, P, Q)
         return (gx, gdx, gax, gca, gcb) + (None,) * 7
 
 
@@ -514,14 +433,11 @@ def nearest_point(a, b):
     """a [N,P,3], b [N,Q,3] -> (squared distance [N,P], index [N,P] int64) of the nearest b point; not differentiable
     (chamfer3D's dist1/idx1, /root/reference/nnutils/mesh_net.py:477)."""
     _lib.need_cuda(a, b)
-    a, b = a.detach().contiguous().float(), b.detach().contiguous().float()
+    a, b = _lib.f32(a.detach(), b.detach())
     N, P = a.shape[:2]
     d2 = torch.empty(N, P, dtype=torch.float32, device=a.device)
     idx = torch.empty(N, P, dtype=torch.int32, device=a.device)
-    guard, st = _lib.stream_of(a)
-    with guard:
-        rc = _lib.lib().lasr_nearest_point(a.data_ptr(), b.data_ptr(), d2.data_ptr(), idx.data_ptr(), N, P, b.shape[1], st)
-    _lib.check(rc, 'lasr_nearest_point')
+    _lib.call('lasr_nearest_point', a, b, d2, idx, N, P, b.shape[1])
     return d2, idx.long()
 
 
@@ -529,7 +445,7 @@ class _PointMesh(Function):
     @staticmethod
     def forward(ctx, verts, faces, points):
         _lib.need_cuda(verts, faces, points)
-        verts, points = verts.contiguous().float(), points.contiguous().float()
+        verts, points = _lib.f32(verts, points)
         faces = faces.contiguous().long()
         N, V = verts.shape[:2]
         F_, P = faces.shape[0], points.shape[1]
@@ -537,13 +453,8 @@ class _PointMesh(Function):
         dp, df = torch.empty(N, P, device=dev), torch.empty(N, F_, device=dev)
         ap = torch.empty(N, P, dtype=torch.int32, device=dev)
         af = torch.empty(N, F_, dtype=torch.int32, device=dev)
-        h = _lib.lib()
-        scratch = torch.empty(h.lasr_point_mesh_scratch_floats(N, F_, P), dtype=torch.float32, device=dev)
-        guard, st = _lib.stream_of(verts)
-        with guard:
-            rc = h.lasr_point_mesh_forward(verts.data_ptr(), faces.data_ptr(), points.data_ptr(), dp.data_ptr(),
-                                           ap.data_ptr(), df.data_ptr(), af.data_ptr(), scratch.data_ptr(), N, V, F_, P, st)
-        _lib.check(rc, 'lasr_point_mesh_forward')
+        scratch = torch.empty(_lib.lib().lasr_point_mesh_scratch_floats(N, F_, P), dtype=torch.float32, device=dev)
+        _lib.call('lasr_point_mesh_forward', verts, faces, points, dp, ap, df, af, scratch, N, V, F_, P)
         ctx.save_for_backward(verts, faces, points, ap, af)
         from ..soft_renderer.functional.geometry import _incidence_of
         ctx.inc = _incidence_of(faces, V)                # the model's face tensor is seen every step: vertex -> corner lists, built once
@@ -554,24 +465,16 @@ class _PointMesh(Function):
         verts, faces, points, ap, af = ctx.saved_tensors
         N, V = verts.shape[:2]
         F_, P = faces.shape[0], points.shape[1]
-        h = _lib.lib()
         gtri = torch.empty(N, F_, 3, 3, dtype=torch.float32, device=verts.device)
         gpts = torch.empty_like(points)
         gverts = torch.empty_like(verts)
         faces_n = faces[None].expand(N, F_, 3).contiguous() if ctx.inc is None else None
-        guard, st = _lib.stream_of(verts)
-        with guard:
-            # unit weights here; the incoming scalar gradient multiplies the results (it may live on the device)
-            rc = h.lasr_point_mesh_backward(verts.data_ptr(), faces.data_ptr(), points.data_ptr(), ap.data_ptr(),
-                                            af.data_ptr(), 1.0 / (N * P), 1.0 / (N * F_), gtri.data_ptr(), gpts.data_ptr(),
-                                            N, V, F_, P, st)
-            _lib.check(rc, 'lasr_point_mesh_backward')
-            if ctx.inc is not None:                      # same sums, same order, no scan of the face tensor (and no expanded copy of it)
-                rc = h.lasr_face_gather_backward_csr(gtri.data_ptr(), ctx.inc[0].data_ptr(), ctx.inc[1].data_ptr(), 1, gverts.data_ptr(),
-                                                     N, V, F_, 3, st)
-            else:
-                rc = h.lasr_face_gather_backward(gtri.data_ptr(), faces_n.data_ptr(), gverts.data_ptr(), N, V, F_, 3, st)
-        _lib.check(rc, 'lasr_face_gather_backward')
+        # unit weights here; the incoming scalar gradient multiplies the results (it may live on the device)
+        _lib.call('lasr_point_mesh_backward', verts, faces, points, ap, af, 1.0 / (N * P), 1.0 / (N * F_), gtri, gpts, N, V, F_, P)
+        if ctx.inc is not None:                          # same sums, same order, no scan of the face tensor (and no expanded copy of it)
+            _lib.call('lasr_face_gather_backward_csr', gtri, ctx.inc[0], ctx.inc[1], 1, gverts, N, V, F_, 3)
+        else:
+            _lib.call('lasr_face_gather_backward', gtri, faces_n, gverts, N, V, F_, 3)
         return gverts * g, None, gpts * g
 
 
@@ -585,16 +488,12 @@ class _CosDist(Function):
     @staticmethod
     def forward(ctx, fa, fb, rep):
         _lib.need_cuda(fa, fb)
-        fa, fb = fa.detach().contiguous().float(), fb.contiguous().float()
+        fa, fb = _lib.f32(fa.detach(), fb)
         N, C = fb.shape[:2]
         P = fb[0, 0].numel()
-        h = _lib.lib()
         d = torch.empty(N, dtype=torch.float32, device=fb.device)
-        scratch = torch.empty(h.lasr_cosdist_scratch_floats(N, P), dtype=torch.float32, device=fb.device)
-        guard, st = _lib.stream_of(fb)
-        with guard:
-            rc = h.lasr_cosdist_forward(fa.data_ptr(), fb.data_ptr(), d.data_ptr(), scratch.data_ptr(), N, C, P, rep, st)
-        _lib.check(rc, 'lasr_cosdist_forward')
+        scratch = torch.empty(_lib.lib().lasr_cosdist_scratch_floats(N, P), dtype=torch.float32, device=fb.device)
+        _lib.call('lasr_cosdist_forward', fa, fb, d, scratch, N, C, P, rep)
         ctx.save_for_backward(fa, fb)
         ctx.rep = rep
         return d
@@ -604,12 +503,9 @@ class _CosDist(Function):
         fa, fb = ctx.saved_tensors
         N, C = fb.shape[:2]
         P = fb[0, 0].numel()
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         gb = torch.empty_like(fb)
-        guard, st = _lib.stream_of(fb)
-        with guard:
-            rc = _lib.lib().lasr_cosdist_backward(fa.data_ptr(), fb.data_ptr(), g.data_ptr(), gb.data_ptr(), N, C, P, ctx.rep, st)
-        _lib.check(rc, 'lasr_cosdist_backward')
+        _lib.call('lasr_cosdist_backward', fa, fb, g, gb, N, C, P, ctx.rep)
         return None, gb, None
 
 
@@ -625,7 +521,6 @@ class _CosDistMulti(Function):
 
     @staticmethod
     def forward(ctx, rep, *feats):
-        import ctypes
         L = len(feats) // 2
         _lib.need_cuda(*feats)
         fa = [f.detach().contiguous().float() for f in feats[:L]]
@@ -636,34 +531,26 @@ class _CosDistMulti(Function):
         for a, b in zip(fa, fb):
             if b.shape[0] != N or a.shape[0] * rep != N or a.shape[1:] != b.shape[1:]:
                 raise ValueError('feature maps must be [N/rep,C,h,w] / [N,C,h,w] per layer')
-        h = _lib.lib()
         dev = fb[0].device
         d = torch.empty(N, dtype=torch.float32, device=dev)
-        scratch = torch.empty(h.lasr_cosdist_multi_scratch_floats(Ps, L, N), dtype=torch.float32, device=dev)
+        scratch = torch.empty(_lib.lib().lasr_cosdist_multi_scratch_floats(Ps, L, N), dtype=torch.float32, device=dev)
         pa = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fa])
         pb = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fb])
-        guard, st = _lib.stream_of(fb[0])
-        with guard:
-            rc = h.lasr_cosdist_multi_forward(pa, pb, Cs, Ps, L, d.data_ptr(), scratch.data_ptr(), N, rep, st)
-        _lib.check(rc, 'lasr_cosdist_multi_forward')
+        _lib.call('lasr_cosdist_multi_forward', pa, pb, Cs, Ps, L, d, scratch, N, rep, on=dev)
         ctx.save_for_backward(*fa, *fb)
         ctx.rep, ctx.dims = rep, (Cs, Ps, L, N)
         return d
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
         Cs, Ps, L, N = ctx.dims
         fa, fb = ctx.saved_tensors[:L], ctx.saved_tensors[L:]
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         gb = [torch.empty_like(f) for f in fb]
         pa = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fa])
         pb = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fb])
         pg = (ctypes.c_void_p * L)(*[f.data_ptr() for f in gb])
-        guard, st = _lib.stream_of(fb[0])
-        with guard:
-            rc = _lib.lib().lasr_cosdist_multi_backward(pa, pb, Cs, Ps, L, g.data_ptr(), pg, N, ctx.rep, st)
-        _lib.check(rc, 'lasr_cosdist_multi_backward')
+        _lib.call('lasr_cosdist_multi_backward', pa, pb, Cs, Ps, L, g, pg, N, ctx.rep, on=fb[0])
         return (None,) + (None,) * L + tuple(gb)
 
 
@@ -682,26 +569,19 @@ class _Geodesic(Function):
     @staticmethod
     def forward(ctx, m1, m2):
         _lib.need_cuda(m1, m2)
-        m1, m2 = m1.contiguous().float(), m2.contiguous().float()
+        m1, m2 = _lib.f32(m1, m2)
         n = m1.numel() // 9
         angle = torch.empty(n, dtype=torch.float32, device=m1.device)
-        guard, st = _lib.stream_of(m1)
-        with guard:
-            rc = _lib.lib().lasr_geodesic_forward(m1.data_ptr(), m2.data_ptr(), angle.data_ptr(), n, st)
-        _lib.check(rc, 'lasr_geodesic_forward')
+        _lib.call('lasr_geodesic_forward', m1, m2, angle, n)
         ctx.save_for_backward(m1, m2)
         return angle
 
     @staticmethod
     def backward(ctx, g):
         m1, m2 = ctx.saved_tensors
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         g1, g2 = torch.empty_like(m1), torch.empty_like(m2)
-        guard, st = _lib.stream_of(m1)
-        with guard:
-            rc = _lib.lib().lasr_geodesic_backward(m1.data_ptr(), m2.data_ptr(), g.data_ptr(), g1.data_ptr(), g2.data_ptr(),
-                                                   m1.numel() // 9, st)
-        _lib.check(rc, 'lasr_geodesic_backward')
+        _lib.call('lasr_geodesic_backward', m1, m2, g, g1, g2, m1.numel() // 9)
         return g1, g2
 
 
@@ -713,7 +593,6 @@ def geodesic_distance(m1, m2):
 class _WeightedMeans(Function):
     @staticmethod
     def forward(ctx, weights, groups, n_groups, *xs):
-        import ctypes
         _lib.need_cuda(*xs)
         xs = [x.contiguous().float() for x in xs]
         n = len(xs)
@@ -722,10 +601,7 @@ class _WeightedMeans(Function):
         ptrs = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
         grp = (ctypes.c_int * n)(*[int(g) for g in groups])
         out = torch.empty(n_groups + 1, dtype=torch.float32, device=xs[0].device)
-        guard, st = _lib.stream_of(xs[0])
-        with guard:
-            rc = _lib.lib().lasr_weighted_means_forward(ptrs, ctx.numels, ctx.weights, grp, n, n_groups, out.data_ptr(), st)
-        _lib.check(rc, 'lasr_weighted_means_forward')
+        _lib.call('lasr_weighted_means_forward', ptrs, ctx.numels, ctx.weights, grp, n, n_groups, out, on=xs[0])
         ctx.shapes = [x.shape for x in xs]
         ctx.device = xs[0].device
         total, sums = out[n_groups], out[:n_groups]
@@ -735,12 +611,9 @@ class _WeightedMeans(Function):
     @staticmethod
     def backward(ctx, g, _gs):
         n = len(ctx.shapes)
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         coef = torch.empty(n, dtype=torch.float32, device=ctx.device)
-        guard, st = _lib.stream_of(coef)
-        with guard:
-            rc = _lib.lib().lasr_weighted_means_backward(ctx.numels, ctx.weights, n, g.data_ptr(), coef.data_ptr(), st)
-        _lib.check(rc, 'lasr_weighted_means_backward')
+        _lib.call('lasr_weighted_means_backward', ctx.numels, ctx.weights, n, g, coef, on=coef)
         return (None, None, None) + tuple(coef[t].expand(ctx.shapes[t]) for t in range(n))
 
 
@@ -758,16 +631,11 @@ class _Intrinsics(Function):
     @staticmethod
     def forward(ctx, cams, pp, scale, depth, ppoint, half):
         _lib.need_cuda(cams, pp, scale, depth, ppoint)
-        cams, pp = cams.contiguous().float(), pp.contiguous().float()
-        scale, depth, ppoint = scale.contiguous().float(), depth.contiguous().float(), ppoint.contiguous().float()
+        cams, pp = _lib.f32(cams, pp)
+        scale, depth, ppoint = _lib.f32(scale, depth, ppoint)
         n2, H, K = scale.shape[0], scale.shape[1], depth.shape[1]
         so, do, po = torch.empty_like(scale), torch.empty_like(depth), torch.empty_like(ppoint)
-        guard, st = _lib.stream_of(scale)
-        with guard:
-            rc = _lib.lib().lasr_intrinsics_forward(cams.data_ptr(), cams.shape[1], pp.data_ptr(), scale.data_ptr(), depth.data_ptr(),
-                                                    ppoint.data_ptr(), so.data_ptr(), do.data_ptr(), po.data_ptr(), n2 // 2, H, K,
-                                                    float(half), st)
-        _lib.check(rc, 'lasr_intrinsics_forward')
+        _lib.call('lasr_intrinsics_forward', cams, cams.shape[1], pp, scale, depth, ppoint, so, do, po, n2 // 2, H, K, float(half))
         ctx.save_for_backward(cams)
         ctx.dims = (n2 // 2, H, K)
         return so, do, po
@@ -776,13 +644,9 @@ class _Intrinsics(Function):
     def backward(ctx, gs, gd, gp):
         cams, = ctx.saved_tensors
         B, H, K = ctx.dims
-        gs, gd, gp = gs.contiguous().float(), gd.contiguous().float(), gp.contiguous().float()
+        gs, gd, gp = _lib.f32(gs, gd, gp)
         a, b, c = torch.empty_like(gs), torch.empty_like(gd), torch.empty_like(gp)
-        guard, st = _lib.stream_of(gs)
-        with guard:
-            rc = _lib.lib().lasr_intrinsics_backward(cams.data_ptr(), cams.shape[1], gs.data_ptr(), gd.data_ptr(), gp.data_ptr(),
-                                                     a.data_ptr(), b.data_ptr(), c.data_ptr(), B, H, K, st)
-        _lib.check(rc, 'lasr_intrinsics_backward')
+        _lib.call('lasr_intrinsics_backward', cams, cams.shape[1], gs, gd, gp, a, b, c, B, H, K)
         return None, None, a, b, c, None
 
 
@@ -796,21 +660,17 @@ class _BoneFixup(Function):
     @staticmethod
     def forward(ctx, quat, trans, depth, rest_ts, H, K, pair):
         _lib.need_cuda(quat, trans, depth, rest_ts)
-        quat, trans, depth = quat.contiguous().float(), trans.contiguous().float(), depth.contiguous().float()
-        rest = rest_ts.contiguous().float() if rest_ts is not None else None
+        quat, trans, depth = _lib.f32(quat, trans, depth)
+        rest = _lib.f32(rest_ts)
         MK = quat.numel() // 9
         M = MK // K
         rmat = torch.empty(MK, 3, 3, dtype=torch.float32, device=quat.device)
         tmat = torch.empty(MK, 3, dtype=torch.float32, device=quat.device)
         angle = torch.empty(MK // 2, dtype=torch.float32, device=quat.device) if pair else None
-        h = _lib.lib()
-        guard, st = _lib.stream_of(quat)
-        with guard:
-            args = (quat.data_ptr(), trans.data_ptr(), depth.data_ptr(), rest.data_ptr() if rest is not None else None,
-                    rmat.data_ptr(), tmat.data_ptr())
-            rc = h.lasr_bone_fixup_pair_forward(*args, angle.data_ptr(), M, H, K, st) if pair else \
-                h.lasr_bone_fixup_forward(*args, M, H, K, st)
-        _lib.check(rc, 'lasr_bone_fixup_forward')
+        if pair:
+            _lib.call('lasr_bone_fixup_pair_forward', quat, trans, depth, rest, rmat, tmat, angle, M, H, K)
+        else:
+            _lib.call('lasr_bone_fixup_forward', quat, trans, depth, rest, rmat, tmat, M, H, K)
         ctx.save_for_backward(quat, rest)
         ctx.dims = (M, H, K, bool(pair))
         ctx.in_shapes = (quat.shape, trans.shape, depth.shape, None if rest is None else rest_ts.shape)
@@ -827,17 +687,11 @@ class _BoneFixup(Function):
         gt = torch.empty(M * K, 2, dtype=torch.float32, device=dev)
         gd = torch.empty(M * K, dtype=torch.float32, device=dev)
         gr = torch.empty(H, K - 1, 3, dtype=torch.float32, device=dev) if rest is not None else None
-        h = _lib.lib()
-        guard, st = _lib.stream_of(quat)
-        with guard:
-            head = (quat.data_ptr(), rest.data_ptr() if rest is not None else None, gR.data_ptr(), gT.data_ptr())
-            tail = (gq.data_ptr(), gt.data_ptr(), gd.data_ptr(), gr.data_ptr() if gr is not None else None, M, H, K, st)
-            if pair:
-                g_angle = g_angle.contiguous().float() if g_angle is not None else torch.zeros(M * K // 2, device=dev)
-                rc = h.lasr_bone_fixup_pair_backward(*head, g_angle.data_ptr(), *tail)
-            else:
-                rc = h.lasr_bone_fixup_backward(*head, *tail)
-        _lib.check(rc, 'lasr_bone_fixup_backward')
+        if pair:
+            g_angle = g_angle.contiguous().float() if g_angle is not None else torch.zeros(M * K // 2, device=dev)
+            _lib.call('lasr_bone_fixup_pair_backward', quat, rest, gR, gT, g_angle, gq, gt, gd, gr, M, H, K)
+        else:
+            _lib.call('lasr_bone_fixup_backward', quat, rest, gR, gT, gq, gt, gd, gr, M, H, K)
         qs, ts, ds, rs = ctx.in_shapes
         return gq.view(qs), gt.view(ts), gd.view(ds), (gr.view(rs) if gr is not None else None), None, None, None
 
@@ -855,19 +709,15 @@ class _ProjectPoints(Function):
     @staticmethod
     def forward(ctx, rest, ctl, Rmat, Tmat, pp, fl, H, K):
         _lib.need_cuda(rest, ctl, Rmat, Tmat, pp, fl)
-        rest, ctl = rest.contiguous().float(), ctl.contiguous().float()
-        Rmat, Tmat = Rmat.detach().contiguous().float(), Tmat.detach().contiguous().float()
-        pp, fl = pp.detach().contiguous().float(), fl.detach().contiguous().float()
+        rest, ctl = _lib.f32(rest, ctl)
+        Rmat, Tmat = _lib.f32(Rmat.detach(), Tmat.detach())
+        pp, fl = _lib.f32(pp.detach(), fl.detach())
         M = Rmat.numel() // (9 * K)
         if Tmat.numel() != 3 * M * K or fl.numel() != M or pp.numel() != 2 * (M // H) or rest.numel() != 3 * H * (K - 1) \
                 or ctl.numel() != rest.numel():
             raise ValueError('project_points: rest_ts / ctl_ts [H,K-1,3], Rmat [M*K,3,3], Tmat [M*K,3], pp [M/H,2], fl [M]')
         proj = torch.empty(M, 2 * (K - 1), 4, dtype=torch.float32, device=rest.device)
-        guard, st = _lib.stream_of(rest)
-        with guard:
-            rc = _lib.lib().lasr_project_points_forward(rest.data_ptr(), ctl.data_ptr(), Rmat.data_ptr(), Tmat.data_ptr(), pp.data_ptr(),
-                                                        fl.data_ptr(), proj.data_ptr(), M, H, K, st)
-        _lib.check(rc, 'lasr_project_points_forward')
+        _lib.call('lasr_project_points_forward', rest, ctl, Rmat, Tmat, pp, fl, proj, M, H, K)
         ctx.save_for_backward(rest, ctl, Rmat, Tmat, fl)
         ctx.dims = (M, H, K)
         return proj
@@ -876,13 +726,9 @@ class _ProjectPoints(Function):
     def backward(ctx, g):
         rest, ctl, Rmat, Tmat, fl = ctx.saved_tensors
         M, H, K = ctx.dims
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         grest, gctl = torch.empty_like(rest), torch.empty_like(ctl)
-        guard, st = _lib.stream_of(rest)
-        with guard:
-            rc = _lib.lib().lasr_project_points_backward(rest.data_ptr(), ctl.data_ptr(), Rmat.data_ptr(), Tmat.data_ptr(), fl.data_ptr(),
-                                                         g.data_ptr(), grest.data_ptr(), gctl.data_ptr(), M, H, K, st)
-        _lib.check(rc, 'lasr_project_points_backward')
+        _lib.call('lasr_project_points_backward', rest, ctl, Rmat, Tmat, fl, g, grest, gctl, M, H, K)
         return grest, gctl, None, None, None, None, None, None
 
 
@@ -898,8 +744,7 @@ class _PoseChain(Function):
     @staticmethod
     def forward(ctx, cams, pp, scale, depth, ppoint, quat4, trans, rest, ctl, H, K, half, pair):
         _lib.need_cuda(cams, pp, scale, depth, ppoint, quat4, trans)
-        f = lambda t: None if t is None else t.contiguous().float()                                   # noqa: E731
-        cams, pp, scale, depth, ppoint, quat4, trans, rest, ctl = map(f, (cams, pp, scale, depth, ppoint, quat4, trans, rest, ctl))
+        cams, pp, scale, depth, ppoint, quat4, trans, rest, ctl = _lib.f32(cams, pp, scale, depth, ppoint, quat4, trans, rest, ctl)
         n2 = scale.shape[0]
         M, MK = n2 * H, n2 * H * K
         if scale.numel() != M or depth.numel() != n2 * K or ppoint.numel() != 2 * n2 or quat4.numel() != 4 * MK or \
@@ -912,15 +757,8 @@ class _PoseChain(Function):
         trep, drep, rmat, tmat = new(MK, 2), new(MK, 1), new(MK, 3, 3), new(MK, 3)
         angle = new(MK // 2) if pair else None
         proj = new(M, 2 * (K - 1), 4) if K > 1 else None
-        ptr = lambda t: None if t is None else t.data_ptr()                                           # noqa: E731
-        guard, st = _lib.stream_of(scale)
-        with guard:
-            rc = _lib.lib().lasr_pose_chain_forward(cams.data_ptr(), cams.shape[1], pp.data_ptr(), scale.data_ptr(), depth.data_ptr(),
-                                                    ppoint.data_ptr(), quat4.data_ptr(), trans.data_ptr(), ptr(rest), ptr(ctl),
-                                                    so.data_ptr(), do.data_ptr(), po.data_ptr(), trep.data_ptr(), drep.data_ptr(),
-                                                    rmat.data_ptr(), tmat.data_ptr(), ptr(angle), ptr(proj), n2 // 2, H, K,
-                                                    float(half), st)
-        _lib.check(rc, 'lasr_pose_chain_forward')
+        _lib.call('lasr_pose_chain_forward', cams, cams.shape[1], pp, scale, depth, ppoint, quat4, trans, rest, ctl, so, do, po, trep,
+                  drep, rmat, tmat, angle, proj, n2 // 2, H, K, float(half))
         ctx.save_for_backward(cams, quat4, rest, ctl, rmat, tmat, so)
         ctx.dims = (n2 // 2, H, K)
         ctx.in_shapes = (scale.shape, depth.shape, ppoint.shape, quat4.shape, trans.shape)
@@ -932,24 +770,16 @@ class _PoseChain(Function):
         B, H, K = ctx.dims
         n2, MK = 2 * B, 2 * B * H * K
         dev = quat4.device
-        f = lambda t: None if t is None else t.contiguous().float()                                   # noqa: E731
-        g_so, g_po, g_trep, g_drep, g_angle, g_proj = map(f, (g_so, g_po, g_trep, g_drep, g_angle, g_proj))
-        gR = f(gR) if gR is not None else torch.zeros(MK, 3, 3, device=dev)
-        gT = f(gT) if gT is not None else torch.zeros(MK, 3, device=dev)
+        g_so, g_po, g_trep, g_drep, g_angle, g_proj = _lib.f32(g_so, g_po, g_trep, g_drep, g_angle, g_proj)
+        gR = _lib.f32(gR) if gR is not None else torch.zeros(MK, 3, 3, device=dev)
+        gT = _lib.f32(gT) if gT is not None else torch.zeros(MK, 3, device=dev)
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)                     # noqa: E731
         gs, gd, gp, gq, gt = new(n2, H), new(n2, K), new(n2, 2), new(MK, 4), new(n2 * K, 2)
         gr = torch.empty_like(rest) if rest is not None else None
         gc = torch.empty_like(ctl) if ctl is not None else None
         scratch = new(MK, 3)
-        ptr = lambda t: None if t is None else t.data_ptr()                                           # noqa: E731
-        guard, st = _lib.stream_of(quat4)
-        with guard:
-            rc = _lib.lib().lasr_pose_chain_backward(cams.data_ptr(), cams.shape[1], quat4.data_ptr(), ptr(rest), ptr(ctl), rmat.data_ptr(),
-                                                     tmat.data_ptr(), so.data_ptr(), ptr(g_so), ptr(g_po), ptr(g_trep), ptr(g_drep),
-                                                     gR.data_ptr(), gT.data_ptr(), ptr(g_angle), ptr(g_proj), gs.data_ptr(), gd.data_ptr(),
-                                                     gp.data_ptr(), gq.data_ptr(), gt.data_ptr(), ptr(gr), ptr(gc), scratch.data_ptr(),
-                                                     B, H, K, st)
-        _lib.check(rc, 'lasr_pose_chain_backward')
+        _lib.call('lasr_pose_chain_backward', cams, cams.shape[1], quat4, rest, ctl, rmat, tmat, so, g_so, g_po, g_trep, g_drep, gR, gT,
+                  g_angle, g_proj, gs, gd, gp, gq, gt, gr, gc, scratch, B, H, K)
         ss, ds, ps, qs, ts = ctx.in_shapes
         return None, None, gs.view(ss), gd.view(ds), gp.view(ps), gq.view(qs), gt.view(ts), gr, gc, None, None, None, None
 
@@ -970,15 +800,11 @@ class _Chamfer(Function):
     @staticmethod
     def forward(ctx, a, b):
         _lib.need_cuda(a, b)
-        a, b = a.contiguous().float(), b.contiguous().float()
+        a, b = _lib.f32(a, b)
         N, P, Q = a.shape[0], a.shape[1], b.shape[1]
         out = torch.empty(N, dtype=torch.float32, device=a.device)
         nn = torch.empty(N * (P + Q), dtype=torch.int32, device=a.device)
-        guard, st = _lib.stream_of(a)
-        with guard:
-            rc = _lib.lib().lasr_chamfer_forward(a.data_ptr(), b.data_ptr(), out.data_ptr(), nn.data_ptr(),
-                                                 nn.data_ptr() + 4 * N * P, N, P, Q, st)
-        _lib.check(rc, 'lasr_chamfer_forward')
+        _lib.call('lasr_chamfer_forward', a, b, out, nn, nn[N * P:], N, P, Q)
         ctx.save_for_backward(a, b, nn)
         return out
 
@@ -986,13 +812,9 @@ class _Chamfer(Function):
     def backward(ctx, g):
         a, b, nn = ctx.saved_tensors
         N, P, Q = a.shape[0], a.shape[1], b.shape[1]
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         ga, gb = torch.empty_like(a), torch.empty_like(b)
-        guard, st = _lib.stream_of(a)
-        with guard:
-            rc = _lib.lib().lasr_chamfer_backward(a.data_ptr(), b.data_ptr(), nn.data_ptr(), nn.data_ptr() + 4 * N * P, g.data_ptr(),
-                                                  ga.data_ptr(), gb.data_ptr(), N, P, Q, st)
-        _lib.check(rc, 'lasr_chamfer_backward')
+        _lib.call('lasr_chamfer_backward', a, b, nn, nn[N * P:], g, ga, gb, N, P, Q)
         return ga, gb
 
 
@@ -1006,18 +828,13 @@ class _MeanShape(Function):
     @staticmethod
     def forward(ctx, mean_v, tex, flip, mask, R, S):
         _lib.need_cuda(mean_v, tex, flip, mask)
-        mean_v, tex = mean_v.contiguous().float(), tex.contiguous().float()
+        mean_v, tex = _lib.f32(mean_v, tex)
         flip = flip.contiguous().float().reshape(-1) if flip is not None else None
-        mask = mask.contiguous().float() if mask is not None else None
+        mask = _lib.f32(mask)
         H, Vp = mean_v.shape[0], mean_v.shape[1]
         out_v = torch.empty(R * H, Vp + S, 3, dtype=torch.float32, device=mean_v.device)
         out_t = torch.empty_like(out_v)
-        guard, st = _lib.stream_of(mean_v)
-        with guard:
-            rc = _lib.lib().lasr_mean_shape_forward(mean_v.data_ptr(), tex.data_ptr(), flip.data_ptr() if flip is not None else None,
-                                                    mask.data_ptr() if mask is not None else None, out_v.data_ptr(), out_t.data_ptr(),
-                                                    R, H, Vp, S, st)
-        _lib.check(rc, 'lasr_mean_shape_forward')
+        _lib.call('lasr_mean_shape_forward', mean_v, tex, flip, mask, out_v, out_t, R, H, Vp, S)
         ctx.save_for_backward(tex, flip, mask)
         ctx.dims = (R, H, Vp, S)
         return out_v, out_t
@@ -1031,12 +848,7 @@ class _MeanShape(Function):
         gt = gt.contiguous().float() if need_t else None
         gm = torch.empty(H, Vp, 3, dtype=torch.float32, device=tex.device) if need_v else None
         gp = torch.empty(H, Vp, 3, dtype=torch.float32, device=tex.device) if need_t else None
-        guard, st = _lib.stream_of(tex)
-        ptr = lambda t: t.data_ptr() if t is not None else None                  # noqa: E731
-        with guard:
-            rc = _lib.lib().lasr_mean_shape_backward(tex.data_ptr(), ptr(flip), ptr(mask), ptr(gv), ptr(gt), ptr(gm), ptr(gp),
-                                                     R, H, Vp, S, st)
-        _lib.check(rc, 'lasr_mean_shape_backward')
+        _lib.call('lasr_mean_shape_backward', tex, flip, mask, gv, gt, gm, gp, R, H, Vp, S)
         return gm, gp, None, None, None, None
 
 
@@ -1051,13 +863,10 @@ def obs_pair(imgs, masks):
     """Observed image on black and on white for the texture losses (/root/reference/nnutils/mesh_net.py:364-366):
     imgs [n,3,IS,IS], masks [n,IS,IS] -> [2n,3,IS,IS] = cat(imgs * fg, 1 - fg + imgs * fg), fg = masks > 0.  Data, no gradient."""
     _lib.need_cuda(imgs, masks)
-    imgs, masks = imgs.detach().contiguous().float(), masks.detach().contiguous().float()
+    imgs, masks = _lib.f32(imgs.detach(), masks.detach())
     n, P = imgs.shape[0], masks[0].numel()
     out = torch.empty(2 * n, *imgs.shape[1:], dtype=torch.float32, device=imgs.device)
-    guard, st = _lib.stream_of(imgs)
-    with guard:
-        rc = _lib.lib().lasr_obs_pair(imgs.data_ptr(), masks.data_ptr(), out.data_ptr(), n, P, st)
-    _lib.check(rc, 'lasr_obs_pair')
+    _lib.call('lasr_obs_pair', imgs, masks, out, n, P)
     return out
 
 
@@ -1065,15 +874,11 @@ def obs_pair(imgs, masks):
 def fill_planes(dst, values):
     """dst [N, C, ...] (contiguous fp32, on the GPU): channel plane c of every image := values[c], in place -- the background fill
     in front of the forward raster kernel (/root/reference/third_party/softras/soft_renderer/functional/soft_rasterize.py:50-53)."""
-    import ctypes
     _lib.need_cuda(dst)
     C = dst.shape[1]
     if len(values) != C or dst.dtype != torch.float32 or not dst.is_contiguous():
         raise ValueError('fill_planes: dst must be contiguous fp32 [N, %d, ...]' % len(values))
     N = dst.shape[0]
     P = dst[0, 0].numel() if N else 0
-    guard, st = _lib.stream_of(dst)
-    with guard:
-        rc = _lib.lib().lasr_fill_planes(dst.data_ptr(), (ctypes.c_float * C)(*[float(v) for v in values]), C, N, P, st)
-    _lib.check(rc, 'lasr_fill_planes')
+    _lib.call('lasr_fill_planes', dst, (ctypes.c_float * C)(*[float(v) for v in values]), C, N, P)
     return dst

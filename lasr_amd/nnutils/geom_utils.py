@@ -12,16 +12,11 @@ class _LBS(Function):
         _lib.need_cuda(verts, Rmat, Tmat, skin)
         N, V = verts.shape[:2]
         # shapes are normalised by obj_to_cam() below (autograd then maps the gradients back)
-        verts, Rmat, Tmat = verts.contiguous().float(), Rmat.contiguous().float(), Tmat.contiguous().float()
+        verts, Rmat, Tmat = _lib.f32(verts, Rmat, Tmat)
         if K > 1:
-            skin = skin.contiguous().float()
+            skin = _lib.f32(skin)
         out = torch.empty(N, V, 3, dtype=torch.float32, device=verts.device)
-        guard, st = _lib.stream_of(verts)
-        with guard:
-            rc = _lib.lib().lasr_lbs_forward(verts.data_ptr(), Rmat.data_ptr(), Tmat.data_ptr(),
-                                             skin.data_ptr() if K > 1 else None, out.data_ptr(),
-                                             N, V, K, 1 if tocam else 0, st)
-        _lib.check(rc, 'lasr_lbs_forward')
+        _lib.call('lasr_lbs_forward', verts, Rmat, Tmat, skin if K > 1 else None, out, N, V, K, 1 if tocam else 0)
         ctx.save_for_backward(verts, Rmat, Tmat, skin if K > 1 else verts.new_empty(0))
         ctx.meta = (N, V, K, tocam)
         return out
@@ -30,7 +25,7 @@ class _LBS(Function):
     def backward(ctx, gout):
         verts, Rmat, Tmat, skin = ctx.saved_tensors
         N, V, K, tocam = ctx.meta
-        gout = gout.contiguous().float()
+        gout = _lib.f32(gout)
         # only what the caller differentiates: LASR's joint / control-point call passes detached transforms and a constant skin
         # (mesh_net.py:285-288), so its backward is the g_verts part alone -- no transposed contraction, no fold launch
         need_v, need_R, need_T, need_s = ctx.needs_input_grad[:4]
@@ -41,13 +36,8 @@ class _LBS(Function):
         gs = torch.empty(N, K - 1, V, dtype=torch.float32, device=verts.device) if (K > 1 and need_s) else None
         h = _lib.lib()
         scratch = torch.empty(h.lasr_lbs_backward_scratch_floats(N, V, K), dtype=torch.float32, device=verts.device) if want_rt else None
-        ptr = lambda t: t.data_ptr() if t is not None else None                  # noqa: E731
-        guard, st = _lib.stream_of(verts)
-        with guard:
-            rc = h.lasr_lbs_backward(verts.data_ptr(), Rmat.data_ptr(), Tmat.data_ptr(),
-                                     skin.data_ptr() if K > 1 else None, gout.data_ptr(), ptr(gv), ptr(gR), ptr(gT), ptr(gs),
-                                     ptr(scratch), N, V, K, 1 if tocam else 0, st)
-        _lib.check(rc, 'lasr_lbs_backward')
+        _lib.call('lasr_lbs_backward', verts, Rmat, Tmat, skin if K > 1 else None, gout, gv, gR, gT, gs, scratch, N, V, K,
+                  1 if tocam else 0)
         return gv, gR if need_R else None, gT if need_T else None, gs, None, None
 
 
@@ -58,16 +48,11 @@ class _LBSBoth(Function):
     def forward(ctx, verts, Rmat, Tmat, skin, K):
         _lib.need_cuda(verts, Rmat, Tmat, skin)
         N, V = verts.shape[:2]
-        verts, Rmat, Tmat = verts.contiguous().float(), Rmat.contiguous().float(), Tmat.contiguous().float()
+        verts, Rmat, Tmat = _lib.f32(verts, Rmat, Tmat)
         if K > 1:
-            skin = skin.contiguous().float()
+            skin = _lib.f32(skin)
         out = torch.empty(2, N, V, 3, dtype=torch.float32, device=verts.device)
-        guard, st = _lib.stream_of(verts)
-        with guard:
-            rc = _lib.lib().lasr_lbs_forward_both(verts.data_ptr(), Rmat.data_ptr(), Tmat.data_ptr(),
-                                                  skin.data_ptr() if K > 1 else None, out[0].data_ptr(), out[1].data_ptr(),
-                                                  N, V, K, st)
-        _lib.check(rc, 'lasr_lbs_forward_both')
+        _lib.call('lasr_lbs_forward_both', verts, Rmat, Tmat, skin if K > 1 else None, out[0], out[1], N, V, K)
         ctx.save_for_backward(verts, Rmat, Tmat, skin if K > 1 else verts.new_empty(0))
         ctx.meta = (N, V, K)
         return out[0], out[1]
@@ -76,17 +61,13 @@ class _LBSBoth(Function):
     def backward(ctx, gcam, gblend):
         verts, Rmat, Tmat, skin = ctx.saved_tensors
         N, V, K = ctx.meta
-        gcam, gblend = gcam.contiguous().float(), gblend.contiguous().float()
+        gcam, gblend = _lib.f32(gcam, gblend)
         gv, gR, gT = torch.empty_like(verts), torch.empty_like(Rmat), torch.empty_like(Tmat)
         gs = torch.empty(N, K - 1, V, dtype=torch.float32, device=verts.device) if K > 1 else None
         h = _lib.lib()
         scratch = torch.empty(h.lasr_lbs_backward_scratch_floats(N, V, K), dtype=torch.float32, device=verts.device)
-        guard, st = _lib.stream_of(verts)
-        with guard:
-            rc = h.lasr_lbs_backward_both(verts.data_ptr(), Rmat.data_ptr(), Tmat.data_ptr(), skin.data_ptr() if K > 1 else None,
-                                          gcam.data_ptr(), gblend.data_ptr(), gv.data_ptr(), gR.data_ptr(), gT.data_ptr(),
-                                          gs.data_ptr() if K > 1 else None, scratch.data_ptr(), N, V, K, st)
-        _lib.check(rc, 'lasr_lbs_backward_both')
+        _lib.call('lasr_lbs_backward_both', verts, Rmat, Tmat, skin if K > 1 else None, gcam, gblend, gv, gR, gT, gs if K > 1 else None,
+                  scratch, N, V, K)
         return gv, gR, gT, gs, None
 
 
@@ -144,14 +125,11 @@ class _Pinhole(Function):
     def forward(ctx, verts, pp, fl):
         _lib.need_cuda(verts, pp, fl)
         N, V = verts.shape[:2]
-        verts = verts.contiguous().float()
-        pp = pp.contiguous().float()
-        fl = fl.contiguous().float()
+        verts = _lib.f32(verts)
+        pp = _lib.f32(pp)
+        fl = _lib.f32(fl)
         out = torch.empty_like(verts)
-        guard, st = _lib.stream_of(verts)
-        with guard:
-            rc = _lib.lib().lasr_pinhole_forward(verts.data_ptr(), pp.data_ptr(), fl.data_ptr(), out.data_ptr(), N, V, st)
-        _lib.check(rc, 'lasr_pinhole_forward')
+        _lib.call('lasr_pinhole_forward', verts, pp, fl, out, N, V)
         ctx.save_for_backward(verts, pp, fl)
         return out
 
@@ -159,13 +137,9 @@ class _Pinhole(Function):
     def backward(ctx, gout):
         verts, pp, fl = ctx.saved_tensors
         N, V = verts.shape[:2]
-        gout = gout.contiguous().float()
+        gout = _lib.f32(gout)
         gv, gpp, gfl = torch.empty_like(verts), torch.empty_like(pp), torch.empty_like(fl)
-        guard, st = _lib.stream_of(verts)
-        with guard:
-            rc = _lib.lib().lasr_pinhole_backward(verts.data_ptr(), pp.data_ptr(), fl.data_ptr(), gout.data_ptr(),
-                                                  gv.data_ptr(), gpp.data_ptr(), gfl.data_ptr(), N, V, st)
-        _lib.check(rc, 'lasr_pinhole_backward')
+        _lib.call('lasr_pinhole_backward', verts, pp, fl, gout, gv, gpp, gfl, N, V)
         return gv, gpp, gfl
 
 

@@ -47,7 +47,7 @@ def iterative_closest_point(X, Y, max_iterations=100, relative_rmse_thr=1e-6, es
     if N < 1 or N > _lib.ICP_MAX_BATCH or P < 1 or Q < 1:
         raise ValueError('need 1 <= N <= %d clouds with at least one point each' % _lib.ICP_MAX_BATCH)
     dtype = X.dtype
-    Xf, Yf = X.detach().contiguous().float(), Y.detach().contiguous().float()
+    Xf, Yf = _lib.f32(X.detach(), Y.detach())
     dev = Xf.device
     h = _lib.lib()
     R = torch.empty(N, 3, 3, dtype=torch.float32, device=dev)
@@ -59,17 +59,13 @@ def iterative_closest_point(X, Y, max_iterations=100, relative_rmse_thr=1e-6, es
         raise ValueError('clouds of %d and %d points are beyond what lasr_icp_iterate takes' % (P, Q))
     ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
     chunk = min(int(chunk), _lib.ICP_MAX_CHUNK)
-    guard, st = _lib.stream_of(Xf)
-    with guard:
-        _lib.check(h.lasr_icp_init(R.data_ptr(), T.data_ptr(), rmse.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, N, P, Q, st),
-                   'lasr_icp_init')
-        done, converged = 0, False
-        while done < max_iterations and not converged:
-            n = min(chunk, max_iterations - done)
-            _lib.check(h.lasr_icp_iterate(Xf.data_ptr(), Yf.data_ptr(), R.data_ptr(), T.data_ptr(), rmse.data_ptr(), status.data_ptr(),
-                                          ws.data_ptr(), nbytes, N, P, Q, n, float(relative_rmse_thr), splits, st), 'lasr_icp_iterate')
-            done += n
-            converged = bool(status[0].item())                  # the one host read of a chunk: 4 bytes
+    _lib.call('lasr_icp_init', R, T, rmse, status, ws, nbytes, N, P, Q)
+    done, converged = 0, False
+    while done < max_iterations and not converged:
+        n = min(chunk, max_iterations - done)
+        _lib.call('lasr_icp_iterate', Xf, Yf, R, T, rmse, status, ws, nbytes, N, P, Q, n, float(relative_rmse_thr), splits)
+        done += n
+        converged = bool(status[0].item())                      # the one host read of a chunk: 4 bytes
     iterations = int(status[1].item())
     Xt = torch.baddbmm(T[:, None], Xf, R)
     return ICPSolution(converged, rmse[:, 0].to(dtype), Xt.to(dtype), SimilarityTransform(R.to(dtype), T.to(dtype),

@@ -17,14 +17,10 @@ class _MaskLoss(Function):
         _lib.need_cuda(pred, masks, occ)
         I, H = pred.shape[:2]
         P = pred[0, 0].numel()
-        pred, masks, occ = pred.contiguous().float(), masks.contiguous().float(), occ.contiguous().float()
+        pred, masks, occ = _lib.f32(pred, masks, occ)
         loss = torch.empty(I, H, dtype=torch.float32, device=pred.device)
         scratch = _scratch(pred.device, I, H, P)
-        guard, st = _lib.stream_of(pred)
-        with guard:
-            rc = _lib.lib().lasr_mask_loss_forward(pred.data_ptr(), masks.data_ptr(), occ.data_ptr(), loss.data_ptr(),
-                                                   scratch.data_ptr(), I, H, P, st)
-        _lib.check(rc, 'lasr_mask_loss_forward')
+        _lib.call('lasr_mask_loss_forward', pred, masks, occ, loss, scratch, I, H, P)
         ctx.save_for_backward(pred, masks, occ, scratch)
         return loss
 
@@ -33,13 +29,9 @@ class _MaskLoss(Function):
         pred, masks, occ, scratch = ctx.saved_tensors
         I, H = pred.shape[:2]
         P = pred[0, 0].numel()
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         gp = torch.empty_like(pred)
-        guard, st = _lib.stream_of(pred)
-        with guard:
-            rc = _lib.lib().lasr_mask_loss_backward(pred.data_ptr(), masks.data_ptr(), occ.data_ptr(), g.data_ptr(),
-                                                    scratch.data_ptr(), gp.data_ptr(), I, H, P, st)
-        _lib.check(rc, 'lasr_mask_loss_backward')
+        _lib.call('lasr_mask_loss_backward', pred, masks, occ, g, scratch, gp, I, H, P)
         return gp, None, None
 
 
@@ -55,22 +47,17 @@ class _FlowLoss(Function):
         _lib.need_cuda(flow_rd, flow_obs, bg, occ, masks)
         I, H = flow_rd.shape[:2]
         P = occ[0].numel()
-        flow_rd = flow_rd.contiguous().float()
+        flow_rd = _lib.f32(flow_rd)
         flow_obs = flow_obs.contiguous().float()                  # [I, C>=2, IS, IS]
         stride = flow_obs[0].numel()
         bg8 = bg.contiguous()
         bg8 = bg8.view(torch.uint8) if bg8.dtype == torch.bool else bg8.to(torch.uint8)       # bool: same bytes, no copy
-        occ, masks = occ.contiguous().float(), masks.contiguous().float()
+        occ, masks = _lib.f32(occ, masks)
         loss = torch.empty(I, H, dtype=torch.float32, device=flow_rd.device)
         fmap = torch.empty(flow_rd.shape[:-1], dtype=torch.float32, device=flow_rd.device)
         vis = torch.empty(flow_rd.shape[:-1], dtype=torch.uint8, device=flow_rd.device)
         scratch = _scratch(flow_rd.device, I, H, P)
-        guard, st = _lib.stream_of(flow_rd)
-        with guard:
-            rc = _lib.lib().lasr_flow_loss_forward_vis(flow_rd.data_ptr(), flow_obs.data_ptr(), bg8.data_ptr(), occ.data_ptr(),
-                                                       masks.data_ptr(), loss.data_ptr(), fmap.data_ptr(), vis.data_ptr(),
-                                                       scratch.data_ptr(), I, H, P, stride, st)
-        _lib.check(rc, 'lasr_flow_loss_forward_vis')
+        _lib.call('lasr_flow_loss_forward_vis', flow_rd, flow_obs, bg8, occ, masks, loss, fmap, vis, scratch, I, H, P, stride)
         ctx.save_for_backward(flow_rd, flow_obs, bg8, occ, masks, scratch)
         vis = vis.view(torch.bool)
         ctx.mark_non_differentiable(fmap, vis)
@@ -81,14 +68,9 @@ class _FlowLoss(Function):
         flow_rd, flow_obs, bg8, occ, masks, scratch = ctx.saved_tensors
         I, H = flow_rd.shape[:2]
         P = occ[0].numel()
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         gf = torch.empty_like(flow_rd)
-        guard, st = _lib.stream_of(flow_rd)
-        with guard:
-            rc = _lib.lib().lasr_flow_loss_backward(flow_rd.data_ptr(), flow_obs.data_ptr(), bg8.data_ptr(), occ.data_ptr(),
-                                                    masks.data_ptr(), scratch.data_ptr(), g.data_ptr(), gf.data_ptr(),
-                                                    I, H, P, flow_obs[0].numel(), st)
-        _lib.check(rc, 'lasr_flow_loss_backward')
+        _lib.call('lasr_flow_loss_backward', flow_rd, flow_obs, bg8, occ, masks, scratch, g, gf, I, H, P, flow_obs[0].numel())
         return gf, None, None, None, None
 
 
@@ -109,11 +91,7 @@ class _TexLoss(Function):
         ts = [t.contiguous().float() for t in (img_obs, img_white, rnd, fg, occ)]
         loss = torch.empty(I, H, dtype=torch.float32, device=rnd.device)
         scratch = _scratch(rnd.device, I, H, P)
-        guard, st = _lib.stream_of(rnd)
-        with guard:
-            rc = _lib.lib().lasr_tex_loss_forward(*[t.data_ptr() for t in ts], loss.data_ptr(), scratch.data_ptr(),
-                                                  float(wt), I, H, P, st)
-        _lib.check(rc, 'lasr_tex_loss_forward')
+        _lib.call('lasr_tex_loss_forward', *ts, loss, scratch, float(wt), I, H, P)
         ctx.save_for_backward(*ts, scratch)
         ctx.wt = float(wt)
         return loss
@@ -124,13 +102,9 @@ class _TexLoss(Function):
         rnd, fg, occ = ts[2], ts[3], ts[4]
         I, H = rnd.shape[:2]
         P = occ[0].numel()
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         grnd, gfg = torch.empty_like(rnd), torch.empty_like(fg)
-        guard, st = _lib.stream_of(rnd)
-        with guard:
-            rc = _lib.lib().lasr_tex_loss_backward(*[t.data_ptr() for t in ts], g.data_ptr(), scratch.data_ptr(),
-                                                   grnd.data_ptr(), gfg.data_ptr(), ctx.wt, I, H, P, st)
-        _lib.check(rc, 'lasr_tex_loss_backward')
+        _lib.call('lasr_tex_loss_backward', *ts, g, scratch, grnd, gfg, ctx.wt, I, H, P)
         return None, None, grnd, gfg, None, None
 
 

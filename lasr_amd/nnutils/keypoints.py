@@ -41,9 +41,5 @@ def kp_transfer(colors, kp, H, W):
     kp = kp.to(device=(colors if colors is not None else kp).device, dtype=torch.float32).contiguous()
     idx = torch.empty(B, J, dtype=torch.int64, device=kp.device)
     pred = torch.empty(B, J, 2, dtype=torch.float32, device=kp.device)
-    guard, st = _lib.stream_of(kp)
-    with guard:
-        rc = _lib.lib().lasr_kp_transfer(colors.data_ptr() if colors is not None else None, kp.data_ptr(), idx.data_ptr(),
-                                         pred.data_ptr(), B, J, S, H, W, st)
-    _lib.check(rc, 'lasr_kp_transfer')
+    _lib.call('lasr_kp_transfer', colors, kp, idx, pred, B, J, S, H, W)
     return idx, pred

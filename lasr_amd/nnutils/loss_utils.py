@@ -30,13 +30,9 @@ class _ARAP(Function):
     def forward(ctx, dx, x, row_ptr, col):
         _lib.need_cuda(dx, x, row_ptr, col)
         N, V = x.shape[:2]
-        dx, x = dx.contiguous().float(), x.contiguous().float()
+        dx, x = _lib.f32(dx, x)
         loss = torch.empty(N, dtype=torch.float32, device=x.device)
-        guard, st = _lib.stream_of(x)
-        with guard:
-            rc = _lib.lib().lasr_arap_forward(dx.data_ptr(), x.data_ptr(), row_ptr.data_ptr(), col.data_ptr(),
-                                              loss.data_ptr(), N, V, st)
-        _lib.check(rc, 'lasr_arap_forward')
+        _lib.call('lasr_arap_forward', dx, x, row_ptr, col, loss, N, V)
         ctx.save_for_backward(dx, x, row_ptr, col)
         return loss
 
@@ -44,13 +40,9 @@ class _ARAP(Function):
     def backward(ctx, g):
         dx, x, row_ptr, col = ctx.saved_tensors
         N, V = x.shape[:2]
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         gdx, gx = torch.empty_like(dx), torch.empty_like(x)
-        guard, st = _lib.stream_of(x)
-        with guard:
-            rc = _lib.lib().lasr_arap_backward(dx.data_ptr(), x.data_ptr(), row_ptr.data_ptr(), col.data_ptr(),
-                                               g.data_ptr(), gdx.data_ptr(), gx.data_ptr(), N, V, st)
-        _lib.check(rc, 'lasr_arap_backward')
+        _lib.call('lasr_arap_backward', dx, x, row_ptr, col, g, gdx, gx, N, V)
         return gdx, gx, None, None
 
 
@@ -59,13 +51,9 @@ class _Laplacian(Function):
     def forward(ctx, x, row_ptr, col):
         _lib.need_cuda(x, row_ptr, col)
         N, V = x.shape[:2]
-        x = x.contiguous().float()
+        x = _lib.f32(x)
         loss = torch.empty(N, dtype=torch.float32, device=x.device)
-        guard, st = _lib.stream_of(x)
-        with guard:
-            rc = _lib.lib().lasr_laplacian_forward(x.data_ptr(), row_ptr.data_ptr(), col.data_ptr(), loss.data_ptr(),
-                                                   N, V, st)
-        _lib.check(rc, 'lasr_laplacian_forward')
+        _lib.call('lasr_laplacian_forward', x, row_ptr, col, loss, N, V)
         ctx.save_for_backward(x, row_ptr, col)
         return loss
 
@@ -73,13 +61,9 @@ class _Laplacian(Function):
     def backward(ctx, g):
         x, row_ptr, col = ctx.saved_tensors
         N, V = x.shape[:2]
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         gx, lx = torch.empty_like(x), torch.empty_like(x)
-        guard, st = _lib.stream_of(x)
-        with guard:
-            rc = _lib.lib().lasr_laplacian_backward(x.data_ptr(), row_ptr.data_ptr(), col.data_ptr(), g.data_ptr(),
-                                                    gx.data_ptr(), lx.data_ptr(), N, V, st)
-        _lib.check(rc, 'lasr_laplacian_backward')
+        _lib.call('lasr_laplacian_backward', x, row_ptr, col, g, gx, lx, N, V)
         return gx, None, None
 
 

@@ -29,10 +29,7 @@ def repair(voxels, ws=None):
     S = voxels.shape[0]
     ws = _ws(S, voxels.device) if ws is None else ws
     info = torch.zeros(2, dtype=torch.int32, device=voxels.device)
-    guard, st = _lib.stream_of(voxels)
-    with guard:
-        rc = _lib.lib().lasr_manifold_repair(voxels.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(), S, st)
-    _lib.check(rc, 'lasr_manifold_repair')
+    _lib.call('lasr_manifold_repair', voxels, info, ws, ws.numel(), S)
     return info
 
 
@@ -40,10 +37,7 @@ def count(voxels, ws):
     """-> counts int32 [3] on the device: (solid voxels with an empty 6-neighbour, boundary vertices, boundary triangles).
     Leaves in ws what extract() needs."""
     counts = torch.zeros(3, dtype=torch.int32, device=voxels.device)
-    guard, st = _lib.stream_of(voxels)
-    with guard:
-        rc = _lib.lib().lasr_manifold_count(voxels.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), voxels.shape[0], st)
-    _lib.check(rc, 'lasr_manifold_count')
+    _lib.call('lasr_manifold_count', voxels, counts, ws, ws.numel(), voxels.shape[0])
     return counts
 
 
@@ -52,11 +46,7 @@ def extract(voxels, ws, V, F):
     in the orders of include/lasr_ops.h (vertices by lattice index, triangles by voxel index then direction)."""
     verts = torch.empty(V, 3, dtype=torch.float32, device=voxels.device)
     faces = torch.empty(F, 3, dtype=torch.int64, device=voxels.device)
-    guard, st = _lib.stream_of(voxels)
-    with guard:
-        rc = _lib.lib().lasr_manifold_extract(voxels.data_ptr(), verts.data_ptr(), faces.data_ptr(), V, F, ws.data_ptr(), ws.numel(),
-                                              voxels.shape[0], st)
-    _lib.check(rc, 'lasr_manifold_extract')
+    _lib.call('lasr_manifold_extract', voxels, verts, faces, V, F, ws, ws.numel(), voxels.shape[0])
     return verts, faces
 
 
@@ -75,7 +65,6 @@ def boundary(voxels, ws=None):
 def project(lattice, in_verts, in_faces):
     """lattice [V,3], in_verts [Vin,3], in_faces [Fin,3] int64, one unit = one voxel -> every lattice point moved to its closest
     point on the input (closest face by lasr_point_mesh_forward)."""
-    h = _lib.lib()
     dev = lattice.device
     V, Vin, Fin = lattice.shape[0], in_verts.shape[0], in_faces.shape[0]
     out = torch.empty_like(lattice)
@@ -84,15 +73,9 @@ def project(lattice, in_verts, in_faces):
     dp, df = torch.empty(1, V, device=dev), torch.empty(1, Fin, device=dev)
     ap = torch.empty(1, V, dtype=torch.int32, device=dev)
     af = torch.empty(1, Fin, dtype=torch.int32, device=dev)
-    scratch = torch.empty(h.lasr_point_mesh_scratch_floats(1, Fin, V), dtype=torch.float32, device=dev)
-    guard, st = _lib.stream_of(lattice)
-    with guard:
-        rc = h.lasr_point_mesh_forward(in_verts.data_ptr(), in_faces.data_ptr(), lattice.data_ptr(), dp.data_ptr(), ap.data_ptr(),
-                                       df.data_ptr(), af.data_ptr(), scratch.data_ptr(), 1, Vin, Fin, V, st)
-        _lib.check(rc, 'lasr_point_mesh_forward')
-        rc = h.lasr_manifold_project(lattice.data_ptr(), in_verts.data_ptr(), in_faces.data_ptr(), ap.data_ptr(), out.data_ptr(), V, Vin,
-                                     Fin, st)
-    _lib.check(rc, 'lasr_manifold_project')
+    scratch = torch.empty(_lib.lib().lasr_point_mesh_scratch_floats(1, Fin, V), dtype=torch.float32, device=dev)
+    _lib.call('lasr_point_mesh_forward', in_verts, in_faces, lattice, dp, ap, df, af, scratch, 1, Vin, Fin, V)
+    _lib.call('lasr_manifold_project', lattice, in_verts, in_faces, ap, out, V, Vin, Fin)
     return out
 
 
@@ -101,11 +84,7 @@ def guard(lattice, verts, faces, min_area=MIN_AREA):
     fell below min_area (lattice units).  verts is changed in place.  -> rounds int32 [1] on the device."""
     rounds = torch.zeros(1, dtype=torch.int32, device=verts.device)
     flags = torch.empty(max(verts.shape[0], 1), dtype=torch.int32, device=verts.device)
-    g, st = _lib.stream_of(verts)
-    with g:
-        rc = _lib.lib().lasr_manifold_guard(lattice.data_ptr(), verts.data_ptr(), faces.data_ptr(), flags.data_ptr(), rounds.data_ptr(),
-                                            verts.shape[0], faces.shape[0], float(min_area), st)
-    _lib.check(rc, 'lasr_manifold_guard')
+    _lib.call('lasr_manifold_guard', lattice, verts, faces, flags, rounds, verts.shape[0], faces.shape[0], float(min_area))
     return rounds
 
 

@@ -99,11 +99,7 @@ def histogram(img, P, window, hist=None, hi=0.9, lo=0.1):
         raise ValueError('maskprop: hist must be a contiguous int32 [2, %d] tensor' % _lib.MASKPROP_BINS)
     _lib.need_cuda(hist)
     x0, y0, x1, y1 = (int(v) for v in window)
-    h = _lib.lib()
-    guard, stream = _lib.stream_of(img)
-    with guard:
-        _lib.check(h.lasr_maskprop_hist(img.data_ptr(), P.data_ptr(), hist.data_ptr(), H, W, x0, y0, x1, y1, float(hi), float(lo),
-                                        stream), 'lasr_maskprop_hist')
+    _lib.call('lasr_maskprop_hist', img, P, hist, H, W, x0, y0, x1, y1, float(hi), float(lo))
     return hist
 
 
@@ -120,12 +116,8 @@ def unary(img_t, P_s, flow_ts, flow_st, hist, tau=1., w_p=1., w_a=0.5, eps=1e-3,
     dev = img_t.device
     table = torch.empty(_lib.MASKPROP_BINS, dtype=torch.float32, device=dev)
     u, q0 = torch.empty(H, W, dtype=torch.float32, device=dev), torch.empty(H, W, dtype=torch.float32, device=dev)
-    h = _lib.lib()
-    guard, stream = _lib.stream_of(img_t)
-    with guard:
-        _lib.check(h.lasr_maskprop_unary(img_t.data_ptr(), P_s.data_ptr(), flow_ts.data_ptr(), flow_st.data_ptr(), hist.data_ptr(),
-                                         table.data_ptr(), u.data_ptr(), q0.data_ptr(), H, W, float(tau), float(w_p), float(w_a),
-                                         float(eps), float(U), stream), 'lasr_maskprop_unary')
+    _lib.call('lasr_maskprop_unary', img_t, P_s, flow_ts, flow_st, hist, table, u, q0, H, W, float(tau), float(w_p), float(w_a),
+              float(eps), float(U))
     return u, q0
 
 
@@ -135,17 +127,13 @@ def meanfield(img, u, q, K=5, R=4, sigma_i=12., sigma_s=3., w_s=0.3, every=False
     img = _image(img, 'img')
     H, W = img.shape[:2]
     u, q = _field(u, (H, W), 'u'), _field(q, (H, W), 'q')
-    h = _lib.lib()
-    guard, stream = _lib.stream_of(img)
     out = []
     bufs = [torch.empty_like(q), torch.empty_like(q)]
-    with guard:
-        for k in range(int(K)):
-            dst = torch.empty_like(q) if every else bufs[k & 1]
-            _lib.check(h.lasr_maskprop_meanfield(img.data_ptr(), u.data_ptr(), q.data_ptr(), dst.data_ptr(), H, W, int(R),
-                                                 float(sigma_i), float(sigma_s), float(w_s), stream), 'lasr_maskprop_meanfield')
-            q = dst
-            out.append(q)
+    for k in range(int(K)):
+        dst = torch.empty_like(q) if every else bufs[k & 1]
+        _lib.call('lasr_maskprop_meanfield', img, u, q, dst, H, W, int(R), float(sigma_i), float(sigma_s), float(w_s))
+        q = dst
+        out.append(q)
     return out if every else q
 
 

@@ -94,10 +94,7 @@ def sheet(planes, ctl, palette, IS, scratch):
         palette = palette.float().contiguous()
         inp.ctl, inp.palette, inp.n_ctl, inp.ctl_stride = ctl.data_ptr(), palette.data_ptr(), ctl.shape[0], ctl.shape[1]
     out = torch.empty(3 * IS, 3 * IS, 3, dtype=torch.uint8, device=dev)
-    guard, st = _lib.stream_of(scratch)
-    with guard:
-        rc = _lib.lib().lasr_monitor_sheet(ctypes.byref(inp), out.data_ptr(), scratch.data_ptr(), IS, st)
-    _lib.check(rc, 'lasr_monitor_sheet')
+    _lib.call('lasr_monitor_sheet', ctypes.byref(inp), out, scratch, IS)
     return out
 
 
@@ -134,10 +131,7 @@ class ScalarRing:
         if len(tensors) != self.K:
             raise ValueError('ScalarRing.push: %d tensors for %d columns' % (len(tensors), self.K))
         tab = self.table(tensors)
-        guard, st = _lib.stream_of(self.ring)
-        with guard:
-            rc = _lib.lib().lasr_scalar_ring_push(tab.data_ptr(), self.K, self.ring.data_ptr(), self.head.data_ptr(), self.capacity, st)
-        _lib.check(rc, 'lasr_scalar_ring_push')
+        _lib.call('lasr_scalar_ring_push', tab, self.K, self.ring, self.head, self.capacity)
         self.pushed += 1
 
     def drain(self, since):

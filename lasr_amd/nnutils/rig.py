@@ -17,10 +17,6 @@ from . import geom_utils
 ORTHO_TOL = 1e-4                                             # |R R^T - I| a transform may show and still count as a rotation
 
 
-def _call(name, *args):
-    _lib.check(getattr(_lib.lib(), name)(*args), name)
-
-
 def pack_influences(skin, k):
     """skin [J,V] (dense, >= 0) -> joints uint8 [V,k], weights float32 [V,k] (the k largest, renormalised; a zero weight carries
     joint 0), dropped float32 [V] (the weight left out, before renormalisation).  k is 4 or 8."""
@@ -35,9 +31,7 @@ def pack_influences(skin, k):
     joints = torch.empty(V, k, dtype=torch.uint8, device=skin.device)
     weights = torch.empty(V, k, dtype=torch.float32, device=skin.device)
     dropped = torch.empty(V, dtype=torch.float32, device=skin.device)
-    guard, stream = _lib.stream_of(skin)
-    with guard:
-        _call('lasr_rig_pack', skin.data_ptr(), J, V, k, joints.data_ptr(), weights.data_ptr(), dropped.data_ptr(), stream)
+    _lib.call('lasr_rig_pack', skin, J, V, k, joints, weights, dropped)
     return joints, weights, dropped
 
 
@@ -50,9 +44,7 @@ def rotation_keys(R):
     R = R.detach().float().contiguous()
     T, K = R.shape[:2]
     quat = torch.empty(T, K, 4, dtype=torch.float32, device=R.device)
-    guard, stream = _lib.stream_of(R)
-    with guard:
-        _call('lasr_rig_quats', R.data_ptr(), T, K, quat.data_ptr(), stream)
+    _lib.call('lasr_rig_quats', R, T, K, quat)
     return quat
 
 
@@ -80,10 +72,7 @@ def skin_packed(rest, joints, weights, quat, trans):
         joints, weights = joints.contiguous(), weights.detach().float().contiguous()
     rest, quat, trans = (t.detach().float().contiguous() for t in (rest, quat, trans))
     out = torch.empty(T, V, 3, dtype=torch.float32, device=rest.device)
-    guard, stream = _lib.stream_of(rest)
-    with guard:
-        _call('lasr_rig_skin', rest.data_ptr(), joints.data_ptr() if k else None, weights.data_ptr() if k else None,
-              quat.data_ptr(), trans.data_ptr(), T, K, V, k, out.data_ptr(), stream)
+    _lib.call('lasr_rig_skin', rest, joints if k else None, weights if k else None, quat, trans, T, K, V, k, out)
     return out
 
 
@@ -96,9 +85,7 @@ def deviation(posed, ref):
     posed, ref = posed.detach().float().contiguous(), ref.detach().float().contiguous()
     T, V = posed.shape[:2]
     stats = torch.zeros(T, 8, dtype=torch.float32, device=posed.device)
-    guard, stream = _lib.stream_of(posed)
-    with guard:
-        _call('lasr_rig_stats', posed.data_ptr(), ref.data_ptr(), T, V, stats.data_ptr(), stream)
+    _lib.call('lasr_rig_stats', posed, ref, T, V, stats)
     return stats
 
 

@@ -95,27 +95,20 @@ def track_points(verts, faces, K, queries, H, W, snap_radius=0, window=1):
     frame_major = torch.empty(T, Q, 2, dtype=torch.float32, device=dev)
     state_major = torch.empty(T, Q, dtype=torch.uint8, device=dev)
     if Q and T:
-        h = _lib.lib()
-        guard, stream = _lib.stream_of(verts)
         chunks = set((queries[:, 0].long() // CHUNK_FRAMES).unique().tolist())
-        with guard:
-            for i in range(0, T, CHUNK_FRAMES):                      # anchoring walk
-                if i // CHUNK_FRAMES not in chunks:
-                    continue
-                j = min(i + CHUNK_FRAMES, T)
-                v, k = verts[i:j], K[i:j]
-                raster = bake.face_index_raster(v, faces32, k, IS)
-                rc = h.lasr_track_anchor(v.data_ptr(), faces32.data_ptr(), k.data_ptr(), raster.data_ptr(), queries.data_ptr(),
-                                         rec.data_ptr(), snapped.data_ptr(), i, j - i, Q, V, F, IS, H, W, snap_radius, stream)
-                _lib.check(rc, 'lasr_track_anchor')
-            for i in range(0, T, CHUNK_FRAMES):                      # projection walk
-                j = min(i + CHUNK_FRAMES, T)
-                v, k = verts[i:j], K[i:j]
-                raster = bake.face_index_raster(v, faces32, k, IS)
-                rc = h.lasr_track_project(v.data_ptr(), faces32.data_ptr(), k.data_ptr(), raster.data_ptr(), rec.data_ptr(),
-                                          frame_major[i:j].data_ptr(), state_major[i:j].data_ptr(), j - i, Q, V, F, IS, H, W,
-                                          window, stream)
-                _lib.check(rc, 'lasr_track_project')
+        for i in range(0, T, CHUNK_FRAMES):                          # anchoring walk
+            if i // CHUNK_FRAMES not in chunks:
+                continue
+            j = min(i + CHUNK_FRAMES, T)
+            v, k = verts[i:j], K[i:j]
+            raster = bake.face_index_raster(v, faces32, k, IS)
+            _lib.call('lasr_track_anchor', v, faces32, k, raster, queries, rec, snapped, i, j - i, Q, V, F, IS, H, W, snap_radius)
+        for i in range(0, T, CHUNK_FRAMES):                          # projection walk
+            j = min(i + CHUNK_FRAMES, T)
+            v, k = verts[i:j], K[i:j]
+            raster = bake.face_index_raster(v, faces32, k, IS)
+            _lib.call('lasr_track_project', v, faces32, k, raster, rec, frame_major[i:j], state_major[i:j], j - i, Q, V, F, IS, H, W,
+                      window)
     c1, c2 = rec[:, 1], rec[:, 2]
     anchors = dict(face=rec.view(torch.int32)[:, 0].clone(), bary=torch.stack([1. - c1 - c2, c1, c2], 1), facing=rec[:, 3].clone(),
                    snapped=snapped)
@@ -152,12 +145,6 @@ def splat(frames, tracks, state, colors, radius=2):
     st = state.transpose(0, 1).contiguous()
     colors = colors.contiguous()
     keys = torch.zeros(T, H, W, dtype=torch.int32, device=frames.device)
-    h = _lib.lib()
-    guard, stream = _lib.stream_of(frames)
-    with guard:
-        rc = h.lasr_track_splat_keys(tr.data_ptr(), st.data_ptr(), keys.data_ptr(), T, Q, H, W, radius, stream)
-        _lib.check(rc, 'lasr_track_splat_keys')
-        rc = h.lasr_track_splat_resolve(keys.data_ptr(), colors.data_ptr() if Q else None, frames.data_ptr(), out.data_ptr(), T, Q, H,
-                                        W, stream)
-        _lib.check(rc, 'lasr_track_splat_resolve')
+    _lib.call('lasr_track_splat_keys', tr, st, keys, T, Q, H, W, radius)
+    _lib.call('lasr_track_splat_resolve', keys, colors if Q else None, frames, out, T, Q, H, W)
     return out

@@ -7,6 +7,7 @@ Differences, all behind the same calls:
   * the NaN-gradient guard of :282-291 costs one host sync per step instead of one per parameter tensor;
   * k-means bone initialisation (:243-251, kmeans_pytorch) is a small Lloyd iteration with farthest-point seeding.
 """
+import ctypes
 import os
 import sys
 from types import SimpleNamespace
@@ -510,7 +511,6 @@ class LASRTrainer:
         self.__dict__.pop('_tail_shared', None)
 
     def _step_tail_hip(self):
-        import ctypes
         c = self._tail_cache
         groups = self.optimizer.param_groups
         n = len(groups)
@@ -519,14 +519,10 @@ class LASRTrainer:
         def arr(kind, vals):
             return (kind * n)(*vals)
         b1, b2 = [g['betas'][0] for g in groups], [g['betas'][1] for g in groups]
-        guard, st = _lib.stream_of(c['ctl'])
-        with guard:
-            rc = _lib.lib().lasr_tail_step(
-                c['table'].data_ptr(), c['chunks'].data_ptr(), c['n_chunks'], c['partials'].data_ptr(), c['ctl'].data_ptr(), 1., 10.,
-                arr(ctypes.c_float, [g['lr'] for g in groups]), arr(ctypes.c_float, b1), arr(ctypes.c_float, b2),
-                arr(ctypes.c_float, [g['eps'] for g in groups]), arr(ctypes.c_float, [g['weight_decay'] for g in groups]),
-                arr(ctypes.c_double, [1. - b ** t for b in b1]), arr(ctypes.c_double, [1. - b ** t for b in b2]), n, st)
-        _lib.check(rc, 'lasr_tail_step')
+        _lib.call('lasr_tail_step', c['table'], c['chunks'], c['n_chunks'], c['partials'], c['ctl'], 1., 10.,
+                  arr(ctypes.c_float, [g['lr'] for g in groups]), arr(ctypes.c_float, b1), arr(ctypes.c_float, b2),
+                  arr(ctypes.c_float, [g['eps'] for g in groups]), arr(ctypes.c_float, [g['weight_decay'] for g in groups]),
+                  arr(ctypes.c_double, [1. - b ** t for b in b1]), arr(ctypes.c_double, [1. - b ** t for b in b2]), n, on=c['ctl'])
         self._tail_t = t
         ctl = c['ctl']
         self.grad_meanv_norm, self.grad_cam_norm = ctl[3], ctl[4]                # device scalars, read when logged

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from .soft_renderer.functional import vertex_normals
-from .vis import _raster
+from .vis import hard_raster
 
 CHUNK_FRAMES = 16                 # frames per raster + shade launch pair (the raster's maps of 16 512^2 frames: 32 MB)
 DEPTH_OFFSET = 1000.              # depth offset in units of the scene's depth range: the raster's 1/z interpolation stays ordered
@@ -67,13 +67,11 @@ def render(verts, faces, colors, S, background=(1., 1., 1.), return_maps=False, 
     verts = verts.float().contiguous()
     colors = torch.as_tensor(colors, dtype=torch.float32, device=dev).expand(N, V, 3)
     F = faces.shape[0]
-    h = _lib.lib()
     bg = (ctypes.c_float * 3)(*[float(c) for c in background])
     faces4 = torch.cat([faces, torch.zeros_like(faces[:, :1])], 1).int().contiguous()
     out = torch.empty(N, S, S, 4, device=dev)
     maps = None
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
         for i in range(0, N, CHUNK_FRAMES):
             v = verts[i:i + CHUNK_FRAMES]
             n = v.shape[0]
@@ -81,10 +79,8 @@ def render(verts, faces, colors, S, background=(1., 1., 1.), return_maps=False, 
             zero = torch.zeros_like(v[..., :1])
             vert_rec = torch.cat([v, zero, vn, zero, colors[i:i + n], zero], 2).contiguous()
             fv, near, far = raster_inputs(v, faces, cull_backfaces)
-            raster = _raster(h, fv, S, near, far, stream)
-            rc = h.lasr_phong_shade(vert_rec.data_ptr(), faces4.data_ptr(), raster.data_ptr(), bg, out[i:i + n].data_ptr(), n, V, F,
-                                    S, stream)
-            _lib.check(rc, 'lasr_phong_shade')
+            raster = hard_raster(fv, S, near, far)
+            _lib.call('lasr_phong_shade', vert_rec, faces4, raster, bg, out[i:i + n], n, V, F, S)
             if return_maps:
                 maps = dict(vert_rec=vert_rec, faces=faces4, raster=raster, fv=fv, near=near, far=far)
     return (out, maps) if return_maps else out

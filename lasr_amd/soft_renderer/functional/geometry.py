@@ -78,10 +78,7 @@ class _FaceGather(torch.autograd.Function):
         N, V, C = attr.shape
         F_ = faces.shape[1]
         out = torch.empty(N, F_, 3, C, dtype=torch.float32, device=attr.device)
-        guard, st = _lib.stream_of(attr)
-        with guard:
-            rc = _lib.lib().lasr_face_gather_forward(attr.data_ptr(), faces.data_ptr(), out.data_ptr(), N, V, F_, C, st)
-        _lib.check(rc, 'lasr_face_gather_forward')
+        _lib.call('lasr_face_gather_forward', attr, faces, out, N, V, F_, C)
         ctx.save_for_backward(faces)
         ctx.dims = (N, V, F_, C)
         ctx.inc = _incidence_of(faces_key, V, faces)
@@ -92,17 +89,12 @@ class _FaceGather(torch.autograd.Function):
         from ... import _lib
         faces, = ctx.saved_tensors
         N, V, F_, C = ctx.dims
-        g = g.contiguous().float()
+        g = _lib.f32(g)
         ga = torch.empty(N, V, C, dtype=torch.float32, device=g.device)
-        guard, st = _lib.stream_of(g)
-        with guard:
-            if ctx.inc is not None:                     # connectivity seen before: the vertex-centric sums without the scan (same bits)
-                inc_ptr, inc = ctx.inc
-                rc = _lib.lib().lasr_face_gather_backward_csr(g.data_ptr(), inc_ptr.data_ptr(), inc.data_ptr(), 0, ga.data_ptr(),
-                                                              N, V, F_, C, st)
-            else:
-                rc = _lib.lib().lasr_face_gather_backward(g.data_ptr(), faces.data_ptr(), ga.data_ptr(), N, V, F_, C, st)
-        _lib.check(rc, 'lasr_face_gather_backward')
+        if ctx.inc is not None:                         # connectivity seen before: the vertex-centric sums without the scan (same bits)
+            _lib.call('lasr_face_gather_backward_csr', g, ctx.inc[0], ctx.inc[1], 0, ga, N, V, F_, C)
+        else:
+            _lib.call('lasr_face_gather_backward', g, faces, ga, N, V, F_, C)
         return ga, None
 
 

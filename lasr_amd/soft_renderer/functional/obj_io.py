@@ -140,12 +140,8 @@ def create_texture_image(textures, texture_res=16):
     image = torch.empty(tile_height * R_out, tile_width * R_out, 3, dtype=textures.dtype, device=dev)
     tex = textures.detach().contiguous()
     fuv = torch.from_numpy(vertices).to(dev)
-    h = _lib.lib()
-    fn = h.lasr_create_texture_image_f64 if textures.dtype == torch.float64 else h.lasr_create_texture_image
-    guard, st = _lib.stream_of(tex)
-    with guard:
-        rc = fn(fuv.data_ptr(), tex.data_ptr(), image.data_ptr(), num_faces, R_in, R_out, 1e-5, st)
-    _lib.check(rc, 'lasr_create_texture_image')
+    _lib.call('lasr_create_texture_image_f64' if textures.dtype == torch.float64 else 'lasr_create_texture_image', fuv, tex, image,
+              num_faces, R_in, R_out, 1e-5)
     vertices[:, :, 0] /= dt(image.shape[1] - 1)
     vertices[:, :, 1] /= dt(image.shape[0] - 1)
     image = image.cpu().numpy()[::-1, ::1]

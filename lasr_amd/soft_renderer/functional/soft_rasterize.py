@@ -113,6 +113,19 @@ def _as_float(v):
     return float(v.item()) if torch.is_tensor(v) else float(v)
 
 
+def _mode_scalars(eps, sigma_val, dist_func, dist_eps, gamma_val, aggr_func_rgb, aggr_func_alpha, texture_type, fill_back):
+    """The nine scalars every raster entry point takes after near / far (include/lasr_sr.h), from the operator's arguments."""
+    return (float(eps), float(sigma_val), _DIST[dist_func], float(math.log(1. / dist_eps - 1.)), float(gamma_val),
+            _RGB[aggr_func_rgb], _ALPHA[aggr_func_alpha], _TEX[texture_type], 1 if fill_back else 0)
+
+
+def _faces_texels(face_vertices, textures):
+    """(fv [N,F,9], tx [N,F,T,3], T) as the three-channel entry points read them: detached, contiguous."""
+    N, F = face_vertices.shape[:2]
+    T = _texels(textures)
+    return face_vertices.detach().reshape(N, F, 9).contiguous(), textures.detach().reshape(N, F, T, 3).contiguous(), T
+
+
 def _near_far_dev(near, far, dev):
     """LASR stores 0-dim DEVICE tensors in rasterizer.near/far (mesh_net.py:306-311).  Returns a 2-float device tensor
     for the *_dev entry points (no host sync), or None when both are plain numbers."""
@@ -160,8 +173,7 @@ class SoftRasterizeFunction(Function):
             raise ValueError('textures must be [N,F,T,3], or [N,F,3,6] / [N,F,3,9] vertex attributes')
         IS = int(image_size)
         nf = _near_far_dev(near, far, dev)
-        tail = (float(eps), float(sigma_val), _DIST[dist_func], float(math.log(1. / dist_eps - 1.)), float(gamma_val),
-                _RGB[aggr_func_rgb], _ALPHA[aggr_func_alpha], _TEX[texture_type], 1 if fill_back else 0)
+        tail = _mode_scalars(eps, sigma_val, dist_func, dist_eps, gamma_val, aggr_func_rgb, aggr_func_alpha, texture_type, fill_back)
         ctx.geom, ctx.nf, ctx.tail, ctx.C = (N, F, T, IS), nf, tail, C
         ctx.near_far = (0.0, 0.0) if nf is not None else (_as_float(near), _as_float(far))
         ctx.in_shapes = (face_vertices.shape, textures.shape)
@@ -179,11 +191,8 @@ class SoftRasterizeFunction(Function):
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             ws = _workspace(dev, stream, h.lasr_sr_workspace_bytes(N, F, T, IS))
-            rc = h.lasr_sr_forward_opt(fv.data_ptr(), tx.data_ptr(), None, aggrs_info.data_ptr(), soft_colors.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), N, F, T, C, IS, *ctx.near_far,
-                                       nf.data_ptr() if nf is not None else None, *tail, (ctypes.c_float * C)(*bg[:C]),
-                                       forward_flags(), _options_ref(), stream)
-        _lib.check(rc, 'lasr_sr_forward')
+        _lib.call('lasr_sr_forward_opt', fv, tx, None, aggrs_info, soft_colors, ws, ws.numel(), N, F, T, C, IS, *ctx.near_far, nf, *tail,
+                  (ctypes.c_float * C)(*bg[:C]), forward_flags(), _options_ref(), on=dev)
         ctx.records = _new_records(dev, stream)
         ctx.save_for_backward(fv, tx, soft_colors, aggrs_info)
         ctx.mark_non_differentiable(aggrs_info)
@@ -204,7 +213,7 @@ class SoftRasterizeFunction(Function):
         grad_faces, grad_textures = grads[:N * F * 9].view(N, F, 9), grads[N * F * 9:].view(tx.shape)
         if vertex and (N == 0 or F == 0 or IS == 0):
             grads.zero_()                                                   # nothing is launched for an empty problem
-        g = grad_soft_colors.contiguous().float()
+        g = _lib.f32(grad_soft_colors)
         h = _lib.lib()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
@@ -213,12 +222,8 @@ class SoftRasterizeFunction(Function):
             reuse = N * F <= REUSE_RECORDS_MAX_FACES and ctx.records == (key, _records_of.get(key))
             if not reuse:
                 _new_records(dev, stream)                                   # this call's setup launch overwrites the workspace
-            rc = h.lasr_sr_backward_ex(fv.data_ptr(), tx.data_ptr(), soft_colors.data_ptr(), aggrs_info.data_ptr(),
-                                       grad_faces.data_ptr(), grad_textures.data_ptr(), g.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), N, F, T, C, IS, *ctx.near_far,
-                                       nf.data_ptr() if nf is not None else None, *tail,
-                                       (_lib.SR_GRADS_OVERWRITE if vertex else 0) | (_lib.SR_RECORDS_VALID if reuse else 0), stream)
-        _lib.check(rc, 'lasr_sr_backward')
+        _lib.call('lasr_sr_backward_ex', fv, tx, soft_colors, aggrs_info, grad_faces, grad_textures, g, ws, ws.numel(), N, F, T, C, IS,
+                  *ctx.near_far, nf, *tail, (_lib.SR_GRADS_OVERWRITE if vertex else 0) | (_lib.SR_RECORDS_VALID if reuse else 0), on=dev)
         fshape, tshape = ctx.in_shapes
         return (grad_faces.reshape(fshape), grad_textures.reshape(tshape),
                 None, None, None, None, None, None, None, None, None, None, None, None, None)
@@ -231,22 +236,16 @@ def _forward_f64(ctx, face_vertices, textures, image_size, background_color, nea
     soft_colors = background with alpha 1 (soft_rasterize.py:47-53), gradients accumulated into zeroed buffers (:88-89)."""
     dev = face_vertices.device
     N, F = face_vertices.shape[:2]
-    fv = face_vertices.detach().reshape(N, F, 9).contiguous()
-    T = _texels(textures)
-    tx = textures.detach().reshape(N, F, T, 3).contiguous()
+    fv, tx, T = _faces_texels(face_vertices, textures)
     IS = int(image_size)
-    scalars = (_as_float(near), _as_float(far), float(eps), float(sigma_val), _DIST[dist_func], float(math.log(1. / dist_eps - 1.)),
-               float(gamma_val), _RGB[aggr_func_rgb], _ALPHA[aggr_func_alpha], _TEX[texture_type], 1 if fill_back else 0)
+    scalars = (_as_float(near), _as_float(far)) + _mode_scalars(eps, sigma_val, dist_func, dist_eps, gamma_val, aggr_func_rgb,
+                                                                aggr_func_alpha, texture_type, fill_back)
     faces_info = torch.zeros(N, F, 27, dtype=torch.float64, device=dev)
     aggrs_info = torch.zeros(N, 2, IS, IS, dtype=torch.float64, device=dev)
     soft_colors = torch.ones(N, 4, IS, IS, dtype=torch.float64, device=dev)
     for k in range(3):
         soft_colors[:, k] = float(background_color[k])
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = _lib.lib().lasr_sr_forward_f64(fv.data_ptr(), tx.data_ptr(), faces_info.data_ptr(), aggrs_info.data_ptr(),
-                                            soft_colors.data_ptr(), None, 0, N, F, T, IS, *scalars, stream)
-    _lib.check(rc, 'lasr_sr_forward_f64')
+    _lib.call('lasr_sr_forward_f64', fv, tx, faces_info, aggrs_info, soft_colors, None, 0, N, F, T, IS, *scalars)
     ctx.f64, ctx.geom, ctx.scalars = True, (N, F, T, IS), scalars
     ctx.in_shapes = (face_vertices.shape, textures.shape)
     ctx.save_for_backward(fv, tx, soft_colors, aggrs_info, faces_info)
@@ -259,12 +258,8 @@ def _backward_f64(ctx, grad_soft_colors):
     N, F, T, IS = ctx.geom
     grad_faces, grad_textures = torch.zeros_like(fv), torch.zeros_like(tx)
     g = grad_soft_colors.contiguous().double()
-    with torch.cuda.device(fv.device):
-        stream = torch.cuda.current_stream(fv.device).cuda_stream
-        rc = _lib.lib().lasr_sr_backward_f64(fv.data_ptr(), tx.data_ptr(), soft_colors.data_ptr(), faces_info.data_ptr(),
-                                             aggrs_info.data_ptr(), grad_faces.data_ptr(), grad_textures.data_ptr(), g.data_ptr(),
-                                             None, 0, N, F, T, IS, *ctx.scalars, stream)
-    _lib.check(rc, 'lasr_sr_backward_f64')
+    _lib.call('lasr_sr_backward_f64', fv, tx, soft_colors, faces_info, aggrs_info, grad_faces, grad_textures, g, None, 0, N, F, T, IS,
+              *ctx.scalars)
     fshape, tshape = ctx.in_shapes
     return (grad_faces.reshape(fshape), grad_textures.reshape(tshape)) + (None,) * 13
 
@@ -292,26 +287,19 @@ def soft_rasterize_raw(face_vertices, textures, image_size, background_color, ne
     (soft_rasterize_cuda.cpp:59-76); the autograd Function hides aggrs_info."""
     dev = face_vertices.device
     N, F = face_vertices.shape[:2]
-    fv = face_vertices.detach().reshape(N, F, 9).contiguous()
-    T, IS = _texels(textures), int(image_size)
-    tx = textures.detach().reshape(N, F, T, 3).contiguous()
+    fv, tx, T = _faces_texels(face_vertices, textures)
+    IS = int(image_size)
     aggrs_info = torch.empty(N, 2, IS, IS, dtype=torch.float32, device=dev)
     soft_colors = torch.ones(N, 4, IS, IS, dtype=torch.float32, device=dev)
     for k in range(3):
         soft_colors[:, k] = float(background_color[k])
     faces_info = torch.zeros(N, F, 27, dtype=torch.float32, device=dev) if want_faces_info else None
-    scalars = (_as_float(near), _as_float(far), float(eps), float(sigma_val), _DIST[dist_func],
-               float(math.log(1. / dist_eps - 1.)), float(gamma_val), _RGB[aggr_func_rgb],
-               _ALPHA[aggr_func_alpha], _TEX[texture_type], 1 if fill_back else 0)
-    h = _lib.lib()
+    tail = _mode_scalars(eps, sigma_val, dist_func, dist_eps, gamma_val, aggr_func_rgb, aggr_func_alpha, texture_type, fill_back)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = _workspace(dev, stream, h.lasr_sr_workspace_bytes(N, F, T, IS))
-        # (lasr_sr_forward is this call with flags 0 and no options; the raw path takes the operator's settings as well)
-        rc = h.lasr_sr_forward_opt(fv.data_ptr(), tx.data_ptr(), faces_info.data_ptr() if want_faces_info else None,
-                                   aggrs_info.data_ptr(), soft_colors.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   N, F, T, 3, IS, scalars[0], scalars[1], None, *scalars[2:], None, forward_flags(),
-                                   _options_ref(), stream)
-    _lib.check(rc, 'lasr_sr_forward')
+        ws = _workspace(dev, stream, _lib.lib().lasr_sr_workspace_bytes(N, F, T, IS))
+    # (lasr_sr_forward is this call with flags 0 and no options; the raw path takes the operator's settings as well)
+    _lib.call('lasr_sr_forward_opt', fv, tx, faces_info, aggrs_info, soft_colors, ws, ws.numel(), N, F, T, 3, IS, _as_float(near),
+              _as_float(far), None, *tail, None, forward_flags(), _options_ref(), on=dev)
     _new_records(dev, stream)
     return (soft_colors, aggrs_info, faces_info) if want_faces_info else (soft_colors, aggrs_info)

@@ -29,9 +29,5 @@ def voxelization(faces, size, normalize=False):
     h = _lib.lib()
     voxels = torch.empty(B, size, size, size, dtype=torch.int32, device=faces.device)
     ws = torch.empty(max(int(h.lasr_voxelize_workspace_bytes(B, size)), 1), dtype=torch.uint8, device=faces.device)
-    fn = h.lasr_voxelize_f64 if faces.dtype == torch.float64 else h.lasr_voxelize
-    guard, st = _lib.stream_of(faces)
-    with guard:
-        rc = fn(faces.data_ptr(), voxels.data_ptr(), None, ws.data_ptr(), ws.numel(), B, F, size, st)
-    _lib.check(rc, 'lasr_voxelize')
+    _lib.call('lasr_voxelize_f64' if faces.dtype == torch.float64 else 'lasr_voxelize', faces, voxels, None, ws, ws.numel(), B, F, size)
     return voxels

@@ -124,20 +124,23 @@ def gaussian_spheres(ctl_ts, ctl_rs, log_ctl, Rmat, Tmat):
     return verts, faces, colors
 
 
-def _raster(h, fv, IS, near, far, stream):
+def hard_raster(fv, IS, near, far):
     """Hard-mode raster of fv [N,F,3,3] (NDC x, y, depth) -> aggrs_info [N,2,IS,IS] (depth, face index or -1)."""
     N, F = fv.shape[:2]
     dev = fv.device
     tex = torch.zeros(N, F, 1, 3, device=dev)
     aggrs = torch.empty(N, 2, IS, IS, device=dev)
     colors = torch.empty(N, 4, IS, IS, device=dev)
-    ws = torch.empty(max(h.lasr_sr_workspace_bytes(N, F, 1, IS), 1), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(_lib.lib().lasr_sr_workspace_bytes(N, F, 1, IS), 1), dtype=torch.uint8, device=dev)
     bg = (ctypes.c_float * 3)(0., 0., 0.)
-    rc = h.lasr_sr_forward_bg(fv.data_ptr(), tex.data_ptr(), None, aggrs.data_ptr(), colors.data_ptr(), ws.data_ptr(), ws.numel(),
-                              N, F, 1, 3, IS, float(near), float(far), None, 1e-3, 1e-12, 0, math.log(1. / 1e-4 - 1.), 1e-4, 0, 0,
-                              0, 1, bg, 0, stream)
-    _lib.check(rc, 'lasr_sr_forward_bg')
+    _lib.call('lasr_sr_forward_bg', fv, tex, None, aggrs, colors, ws, ws.numel(), N, F, 1, 3, IS, float(near), float(far), None, 1e-3,
+              1e-12, 0, math.log(1. / 1e-4 - 1.), 1e-4, 0, 0, 0, 1, bg, 0)
     return aggrs
+
+
+def _raster(h, fv, IS, near, far, stream):
+    """hard_raster under its earlier signature, for callers that still pass the handle and the current stream."""
+    return hard_raster(fv, IS, near, far)
 
 
 def _face_planes(lv, faces):
@@ -175,8 +178,6 @@ def shade(verts, faces, colors, K, IS, H, W, n_opaque=None, casters=None, smooth
     verts = verts.float().contiguous()
     colors = torch.as_tensor(colors, dtype=torch.float32, device=dev).expand(N, V, 3)
     K = torch.as_tensor(K, dtype=torch.float32, device=dev).reshape(N, 4)
-    h = _lib.lib()
-    stream = torch.cuda.current_stream(dev).cuda_stream
     x, y, z = verts.unbind(2)
     sx = 2 * (K[:, 0:1] * x / z + K[:, 2:3]) / IS - 1                         # u = fx x / z + px -> NDC of the square raster
     sy = 1 - 2 * (K[:, 1:2] * y / z + K[:, 3:4]) / IS                         # v down, NDC y up: row 0 is the top
@@ -214,18 +215,15 @@ def shade(verts, faces, colors, K, IS, H, W, n_opaque=None, casters=None, smooth
     maps = {}
     with torch.cuda.device(dev):
         cam = torch.stack([sx, sy, z], 2)[:, faces].contiguous()                # N,F,3,3
-        raster0 = _raster(h, cam[:, :F0].contiguous(), IS, NEAR, FAR, stream)
-        raster1 = _raster(h, cam[:, F0:].contiguous(), IS, NEAR, FAR, stream) if F0 < F else None
+        raster0 = hard_raster(cam[:, :F0].contiguous(), IS, NEAR, FAR)
+        raster1 = hard_raster(cam[:, F0:].contiguous(), IS, NEAR, FAR) if F0 < F else None
         lnd = torch.stack([(lv[..., 0] - ctr[:, :1]) / half[:, None], (lv[..., 1] - ctr[:, 1:]) / half[:, None],
                            lv[..., 2] - wlo[:, None] + off[:, None]], 2)[:, faces].contiguous()
         # one light raster for the whole chunk: near / far around every frame's offset depth range
-        shadow = _raster(h, lnd, SHADOW_MAP_SIZE, float(off.min()) * 0.5, float((off + 2 * rng).max()), stream)
+        shadow = hard_raster(lnd, SHADOW_MAP_SIZE, float(off.min()) * 0.5, float((off + 2 * rng).max()))
         params.shadow_bias = float(rng.max()) * 1e-5
-        rc = h.lasr_vis_shade(vert_rec.data_ptr(), faces4.data_ptr(), face_rec.data_ptr(), raster0.data_ptr(),
-                              raster1.data_ptr() if raster1 is not None else None, shadow.data_ptr(), shadow_xf.data_ptr(),
-                              packed.data_ptr() if packed is not None else None, out.data_ptr(), N, V, F, F0, IS,
-                              SHADOW_MAP_SIZE, H, W, ctypes.byref(params), stream)
-    _lib.check(rc, 'lasr_vis_shade')
+        _lib.call('lasr_vis_shade', vert_rec, faces4, face_rec, raster0, raster1, shadow, shadow_xf, packed, out, N, V, F, F0, IS,
+                  SHADOW_MAP_SIZE, H, W, ctypes.byref(params))
     rgb = out.view(torch.uint8).reshape(N, H, W, 4)[..., :3]
     if return_maps:
         maps = dict(vert_rec=vert_rec, faces=faces4, face_rec=face_rec, raster0=raster0, raster1=raster1, shadow=shadow,
