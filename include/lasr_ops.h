@@ -1040,6 +1040,65 @@ int lasr_track_splat_keys(const float* tracks, const unsigned char* state, unsig
 int lasr_track_splat_resolve(const unsigned* keys, const unsigned char* colors, const unsigned char* frames, unsigned char* out, int n,
                              int Q, int H, int W, void* hip_stream);
 
+/*
+ * ---- Reprojection scores of scripts/eval_reproj.py (lasr_amd/csrc/reproj.hip, lasr_amd/nnutils/reproj.py)
+ * This project's own addition: the reference has no counterpart and the DAVIS toolkit is not restated from code; the definitions
+ * below are the specification, and parity is to the float64 restatement in tests/reproj_restated.py and to closed forms only.
+ * Per frame the hard-mode raster of the predicted mesh is compared with what the loader was trained on: the annotation (region
+ * similarity J, boundary measure F), the forward optical flow (end-point error) and the frame's colours.  Conventions are those
+ * of lasr_track_anchor: verts [n,V,3] camera space, faces [F,3] int32 shared, K [n,4] = fx fy px py (16-byte aligned), raster
+ * [n,2,IS,IS] whose plane 1 names the nearest face; pixel (r, c) has the centre (c + 0.5, r + 0.5).
+ *   pred(r, c) = plane 1 names a face in [0, F) at (r, c), r < H, c < W;  gt(r, c) = gt[n,H,W] uint8 is non-zero.
+ *
+ * lasr_reproj_pixels, per frame of the n passed:
+ *   bits   uint64 [n,2,H,WW], WW = ceil(W/64): map 0 = pred, map 1 = gt; column c is bit c & 63 of word c >> 6, bits at or beyond
+ *          W are 0.  Written in full.
+ *   counts uint64 [n,12], ADDED to (the caller zeroes them): inter = |pred & gt|, union = |pred | gt|, n_pred, n_gt, n_pb, n_gb,
+ *          pm, gm (slots 4-7: lasr_reproj_boundary), n_flow, n_le1, n_le3, n_rgb.
+ *   sums   double [n,2] = (sum of epe, sum of sq), written.
+ *   A pixel with pred & gt whose face indexes vertices inside [0, V) is anchored at its centre by step 3 of lasr_track_anchor
+ *   (the same code, no snapping): c1, c2, c0 = 1 - c1 - c2, or no anchor.
+ *   Flow (verts_next [n,V,3] and K_next [n,4] = the mesh and intrinsics of each frame's successor, flow [n,H,W,3] fp32 =
+ *   (u, v, valid), occ [n,H,W] fp32; the three are NULL together, occ may be NULL on its own = no occlusion test): an anchored
+ *   pixel counts in n_flow when flow.valid != 0, occ < 10, flow.u and flow.v are finite, and P = V0 + c1 e1 + c2 e2 on the
+ *   successor's mesh has P.z > 0.  flow_pred = (fx' P.x/P.z + px' - (c + 0.5), fy' P.y/P.z + py' - (r + 0.5)), the expression of
+ *   lasr_track_project; (du, dv) = flow_pred - flow; epe = sqrt(du^2 + dv^2) in fp32 (a result that is not a number does not
+ *   count); n_le1 / n_le3 count epe <= 1 / <= 3.
+ *   Colour (frames uint8 [n,H,W,3], colors uint8 [n,V,3], NULL together): every anchored pixel counts in n_rgb; per channel k
+ *   d_k = (c0 C0k + c1 C1k + c2 C2k) - frame_k in fp32 on the 0-255 scale, evaluated as written, sq = d_0^2 + d_1^2 + d_2^2 in
+ *   fp32.  The counters of a group that is NULL stay untouched.
+ *   A wave owns 64 consecutive columns of one row: a ballot is the word of the map, the counts are popcounts, added up over the
+ *   sixteen waves (rows) of a workgroup and then one integer atomic per workgroup and counter.  epe and sq are summed in double: a
+ *   fixed tree across the wave, the sixteen waves of a workgroup in row order,
+ *   one partial per workgroup in `workspace` (lasr_reproj_workspace_bytes(n, H, W) bytes, 8-byte aligned; 0 for bad sizes), and
+ *   a second launch in which thread i of one workgroup per frame folds the partials i, i + 256, ... in order and the 256 results
+ *   fold across halves.  No floating-point atomics: the same bits on every run and for any split of the frames into calls.
+ *
+ * lasr_reproj_boundary: adds n_pb, n_gb, pm, gm to counts from bits; scratch_bits uint64 [n,2,H,WW] receives the boundary maps.
+ *   b(seg) = (seg ^ e) | (seg ^ s) | (seg ^ se) with e(r,c) = seg(r,c+1), s(r,c) = seg(r+1,c), se(r,c) = seg(r+1,c+1), 0 beyond
+ *   the image; then the last row is seg ^ e, the last column seg ^ s, the last pixel 0.  dil(m)(p) = some q with m(q) and
+ *   |p - q|^2 <= radius^2 in integers, clipped to the image: for the row offset dy every bit within |dx| <= floor(sqrt(radius^2 -
+ *   dy^2)).  n_pb = |b(pred)|, n_gb = |b(gt)|, pm = |b(pred) & dil(b(gt))|, gm = |b(gt) & dil(b(pred))|.  Two launches: the
+ *   boundary words (shifts and XORs with a carry bit from the next word and the next row); then one thread per (frame, row, word)
+ *   ORs the dilated words of the rows y + dy (own word: shift-OR by doubling; a neighbouring word reaches in from its extreme bit)
+ *   and adds the popcounts, one integer atomic per wave and counter.  A word whose own boundary bits are 0 is skipped.
+ *   Precision, recall and F are the host's (lasr_amd/nnutils/reproj.py).
+ *
+ * Checked on the host before any launch (LASR_E_BADARG): n >= 0, 1 <= H, W <= LASR_TRACK_MAX_SIZE; pixels: V >= 1, F >= 0,
+ *   H, W <= IS <= LASR_TRACK_MAX_SIZE, 3 V <= INT_MAX, F <= 2^24, an optional group given in part; boundary: 0 <= radius <=
+ *   LASR_REPROJ_MAX_RADIUS; then an empty problem (n == 0) is LASR_OK with nothing launched; then every pointer non-NULL (faces may
+ *   be NULL for F == 0; the optional groups as above).  Device contents are not read on the host.  These launches are not in the
+ *   lasr_prof_* kernel table.
+ */
+#define LASR_REPROJ_MAX_RADIUS 96
+size_t lasr_reproj_workspace_bytes(int n, int H, int W);
+int lasr_reproj_pixels(const float* verts, const float* verts_next, const int* faces, const float* K, const float* K_next,
+                       const float* raster, const unsigned char* gt, const float* flow, const float* occ, const unsigned char* frames,
+                       const unsigned char* colors, unsigned long long* bits, unsigned long long* counts, double* sums, void* workspace,
+                       int n, int V, int F, int IS, int H, int W, void* hip_stream);
+int lasr_reproj_boundary(const unsigned long long* bits, unsigned long long* scratch_bits, unsigned long long* counts, int n, int H,
+                         int W, int radius, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,7 @@ extern "C" {
  *      Still 13 (additions only; a binding written against 13 loads the library unchanged): lasr_rig_* of scripts/export_gltf.py,
  *      lasr_maskprop_hist, lasr_maskprop_unary, lasr_maskprop_meanfield of preprocess/propagate_mask.py,
  *      lasr_track_anchor, lasr_track_project, lasr_track_splat_keys, lasr_track_splat_resolve of scripts/export_tracks.py,
+ *      lasr_reproj_workspace_bytes, lasr_reproj_pixels, lasr_reproj_boundary of scripts/eval_reproj.py,
  *      lasr_sr_plan_forward (test hook beside lasr_sr_peek_choice and lasr_selftest_*: the forward plan of a call, host only). */
 #define LASR_ABI_VERSION 13
 int         lasr_abi_version(void);

@@ -131,6 +131,10 @@ SIGNATURES = {
     'lasr_track_project': (_i, [_p] * 7 + [_i] * 8 + [_p]),
     'lasr_track_splat_keys': (_i, [_p] * 3 + [_i] * 5 + [_p]),
     'lasr_track_splat_resolve': (_i, [_p] * 4 + [_i] * 4 + [_p]),
+    # lasr_amd/csrc/reproj.hip
+    'lasr_reproj_workspace_bytes': (_sz, [_i, _i, _i]),
+    'lasr_reproj_pixels': (_i, [_p] * 15 + [_i] * 6 + [_p]),
+    'lasr_reproj_boundary': (_i, [_p] * 3 + [_i] * 4 + [_p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -193,6 +197,7 @@ BAKE_MAX_RES, BAKE_MAX_SIZE, BAKE_MAX_POWER = 32, 8192, 16   # LASR_BAKE_MAX_RES
 RIG_MAX_BONES, RIG_MAX_INFLUENCES = 64, 8                    # LASR_RIG_MAX_BONES / LASR_RIG_MAX_INFLUENCES of include/lasr_ops.h
 MASKPROP_BINS, MASKPROP_MAX_SIZE, MASKPROP_MAX_RADIUS = 4096, 16384, 8   # LASR_MASKPROP_* of include/lasr_ops.h
 TRACK_MAX_SNAP, TRACK_MAX_WINDOW, TRACK_MAX_RADIUS, TRACK_MAX_SIZE, TRACK_SPLAT_ALPHA = 16, 2, 8, 8192, 192   # LASR_TRACK_* of include/lasr_ops.h
+REPROJ_MAX_RADIUS = 96                              # LASR_REPROJ_MAX_RADIUS of include/lasr_ops.h
 
 
 class SrOptions(ctypes.Structure):

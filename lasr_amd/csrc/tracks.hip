@@ -9,40 +9,9 @@
 
 #include "../../include/lasr_ops.h"
 #include "ops_common.h"
+#include "track_anchor.h"
 
 namespace lasr {
-
-struct TrackFace { float ax, ay, az, e1x, e1y, e1z, e2x, e2y, e2z, nx, ny, nz; };
-
-// Corner 0, the two EDGE vectors and their cross product of face (i0, i1, i2) in the vertex array v of one frame.
-__device__ __forceinline__ TrackFace track_face(const float* __restrict__ v, int i0, int i1, int i2)
-{
-    TrackFace t;
-    t.ax = v[i0 * 3]; t.ay = v[i0 * 3 + 1]; t.az = v[i0 * 3 + 2];
-    t.e1x = v[i1 * 3] - t.ax; t.e1y = v[i1 * 3 + 1] - t.ay; t.e1z = v[i1 * 3 + 2] - t.az;
-    t.e2x = v[i2 * 3] - t.ax; t.e2y = v[i2 * 3 + 1] - t.ay; t.e2z = v[i2 * 3 + 2] - t.az;
-    t.nx = t.e1y * t.e2z - t.e1z * t.e2y;
-    t.ny = t.e1z * t.e2x - t.e1x * t.e2z;
-    t.nz = t.e1x * t.e2y - t.e1y * t.e2x;
-    return t;
-}
-
-// P = c0 V0 + c1 V1 + c2 V2 written on the edges: V0 + c1 e1 + c2 e2 (c0 = 1 - c1 - c2).
-__device__ __forceinline__ void track_point(const TrackFace& t, float c1, float c2, float& px, float& py, float& pz)
-{
-    px = t.ax + (c1 * t.e1x + c2 * t.e2x);
-    py = t.ay + (c1 * t.e1y + c2 * t.e2y);
-    pz = t.az + (c1 * t.e1z + c2 * t.e2z);
-}
-
-__device__ __forceinline__ float track_clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
-
-// The face plane 1 of the raster names at (row, col), or -1 (also for a value outside [0, F)).
-__device__ __forceinline__ int track_named(const float* __restrict__ plane, int IS, int row, int col, int F)
-{
-    const float fo = plane[(size_t)row * IS + col];
-    return (fo >= 0.f && fo < (float)F) ? (int)fo : -1;
-}
 
 // One thread per query.  verts / K / raster hold the n frames t0 .. t0 + n - 1.
 __global__ __launch_bounds__(256) void track_anchor_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
@@ -84,20 +53,8 @@ __global__ __launch_bounds__(256) void track_anchor_kernel(const float* __restri
         if ((unsigned)i0 < (unsigned)V && (unsigned)i1 < (unsigned)V && (unsigned)i2 < (unsigned)V) {
             const TrackFace tf = track_face(verts + (size_t)t * V * 3, i0, i1, i2);
             const float4 k = K[t];
-            // Moeller-Trumbore along d = ((u - px)/fx, (v - py)/fy, 1) from the ray's point at V0's depth, O = V0.z d, so that
-            // tvec = O - V0 is of the size of the face and not of its distance (the barycentrics do not depend on the origin)
-            const float dx = (u - k.z) / k.x, dy = (v - k.w) / k.y, dz = 1.f;
-            const float pvx = dy * tf.e2z - dz * tf.e2y, pvy = dz * tf.e2x - dx * tf.e2z, pvz = dx * tf.e2y - dy * tf.e2x;
-            const float det = tf.e1x * pvx + tf.e1y * pvy + tf.e1z * pvz;
-            const float tx = dx * tf.az - tf.ax, ty = dy * tf.az - tf.ay, tz = 0.f;
-            const float qx = ty * tf.e1z - tz * tf.e1y, qy = tz * tf.e1x - tx * tf.e1z, qz = tx * tf.e1y - ty * tf.e1x;
-            const float b1 = (tx * pvx + ty * pvy + tz * pvz) / det;
-            const float b2 = (dx * qx + dy * qy + dz * qz) / det;
-            const float nn = tf.nx * tf.nx + tf.ny * tf.ny + tf.nz * tf.nz;
-            if (nn > 0.f && det != 0.f && fabsf(b1) < 3.4e38f && fabsf(b2) < 3.4e38f) {
-                const float a0 = track_clamp01(1.f - b1 - b2), a1 = track_clamp01(b1), a2 = track_clamp01(b2);
-                const float s = a0 + a1 + a2;                        // >= 1/3: the largest of three numbers that sum to 1
-                const float c1 = a1 / s, c2 = a2 / s;
+            float c1, c2;
+            if (track_barycentrics(tf, k, u, v, c1, c2)) {           // step 3 (track_anchor.h, shared with reproj.hip)
                 float px, py, pz;
                 track_point(tf, c1, c2, px, py, pz);
                 const float np = tf.nx * px + tf.ny * py + tf.nz * pz;
@@ -137,7 +94,8 @@ __global__ __launch_bounds__(256) void track_project_kernel(const float* __restr
             st = 4;
         } else {
             const float4 k = K[t];
-            const float u = k.x * px / pz + k.z, v = k.y * py / pz + k.w;
+            float u, v;
+            track_pinhole(k, px, py, pz, u, v);
             out = make_float2(u, v);
             if (!(u >= 0.f && u < (float)W && v >= 0.f && v < (float)H)) {
                 st = 3;
