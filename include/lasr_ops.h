@@ -1099,6 +1099,58 @@ int lasr_reproj_pixels(const float* verts, const float* verts_next, const int* f
 int lasr_reproj_boundary(const unsigned long long* bits, unsigned long long* scratch_bits, unsigned long long* counts, int n, int H,
                          int W, int radius, void* hip_stream);
 
+/*
+ * ---- Variational optical flow of preprocess/auto_gen.py --flow_method variational (lasr_amd/csrc/varflow.hip,
+ * lasr_amd/nnutils/varflow.py) ------------------------------------------------------------------------------
+ * This project's own addition: the reference estimates flow with a network (VCN) whose checkpoint is a download; this is the
+ * classical alternative without learned weights, a coarse-to-fine, warping, robust variational flow (Brox et al. 2004,
+ * simplified: brightness constancy only) solved by red-black SOR.  Nothing of the reference is restated here; the definition is
+ * tests/varflow_restated.py, whose operation order the kernels follow (-ffp-contract=off), and parity is to that file in float64
+ * and to closed forms only.  Images are fp32 [H,W,3] in 0..1 (uint8 / 255); inside the solver a flow field is PLANAR fp32 [2,H,W]
+ * = (u, v) in pixels with I1(p) ~ I2(p + (u, v)(p)); lasr_varflow_occ takes the public layout [H,W,2].  All arrays are dense and
+ * on the device.  "Clamped" = the tap index clamped to the image; the gradient of a field is 0.5 (a[x+1] - a[x-1]) and
+ * 0.5 (a[y+1] - a[y-1]) on clamped taps; bilinear(f, Y, X) = (f00 (1-tx) + f01 tx)(1-ty) + (f10 (1-tx) + f11 tx) ty on the taps
+ * floor and min(floor + 1, size - 1).
+ *
+ * lasr_varflow_reduce: one Burt-Adelson REDUCE of an image [H,W,3] to out [ceil(H/2), ceil(W/2), 3]:
+ *   out(y,x) = sum_i k_i (sum_j k_j in(clamp(2y+i), clamp(2x+j))), i, j = -2..2 in that order, k = (1, 4, 6, 4, 1) / 16.
+ *   Exactly one of img_u8 / in is given.  The uint8 form first writes level0 [H,W,3] = img_u8 / 255 (one more launch) and reduces
+ *   that; its out may be NULL (an image with a single level).  The fp32 form takes level0 = NULL.
+ * lasr_varflow_expand: uv_fine [2,h,w] = 2 bilinear(uv_coarse [2,hc,wc], y/2, x/2); hc = ceil(h/2), wc = ceil(w/2).
+ * lasr_varflow_tensor: X = x + u, Y = y + v, valid = 0 <= X <= W-1 and 0 <= Y <= H-1 (false for NaN).  At (Y, X) clamped to the
+ *   frame, per channel: I2w and the gradient of I2 sampled bilinearly; Ix, Iy = the mean of that and the gradient of I1 at p;
+ *   It = I2w - I1.  J [6,H,W] = (sum Ix^2, sum Ix Iy, sum Iy^2, sum Ix It, sum Iy It, sum It^2) over the channels in order, 0
+ *   where not valid.
+ * lasr_varflow_weights: psi [2,H,W]: psi_d = 0.5 / sqrt(max(r2, 0) + eps^2) with r2 = du^2 J11 + 2 du dv J12 + dv^2 J22 + 2 du J13
+ *   + 2 dv J23 + J33, and psi_s = 0.5 / sqrt(|grad(u+du)|^2 + |grad(v+dv)|^2 + eps^2); d [2,H,W] = (du, dv).
+ * lasr_varflow_sor: `iters` red-black iterations on d, in place; pixels with (x + y) even first, then odd:
+ *   du <- (1-w) du + w (sum_n w_n (u_n + du_n) - ws u - psi_d (J13 + J12 dv)) / (psi_d J11 + ws)
+ *   dv <- (1-w) dv + w (sum_n w_n (v_n + dv_n) - ws v - psi_d (J23 + J12 du)) / (psi_d J22 + ws)      with the new du,
+ *   over the 4-neighbours n = left, right, up, down in that order, w_n = alpha 0.5 (psi_s(p) + psi_s(n)) inside the image and 0
+ *   outside, ws = sum_n w_n.  One launch per iteration, d -> scratch -> d ... (scratch [2,H,W]; after an odd count one device copy
+ *   brings the result back to d): a workgroup owns 64 x 8 pixels, stages du, dv, u, v, psi_s of the tile and a halo of 2 in
+ *   16320 bytes of LDS, runs the red half-sweep on the tile and the ring at distance 1 and the black one on the tile; a thread
+ *   keeps the J planes and psi_d of its red and its black pixel in registers.  iters = n gives the bits of n calls with iters = 1.
+ * lasr_varflow_occ: f_ab, f_ba fp32 [H,W,2].  q = p + f_ab(p); outside the frame (or NaN): occ = 6.  Else
+ *   e = |f_ab(p) + bilinear(f_ba, q)|, occ = clamp((e - tau) / s, -6, 6), and an exact 0 is written as FLT_MIN (the loader reads 0
+ *   as padding).  Defaults tau 1, s 0.5.
+ * No entry point uses floating-point atomics: the same input gives the same bits on every run.
+ * Checked on the host before any launch (LASR_E_BADARG): LASR_VARFLOW_MIN_SIZE <= H, W <= LASR_VARFLOW_MAX_SIZE (so one plane has
+ *   fewer than 2^31 elements; expand: the fine size, and the coarse one equal to its half rounded up); reduce: exactly one
+ *   input form; eps, alpha, s > 0, 0 < omega < 2, tau >= 0, all finite; iters >= 0; every pointer non-NULL (reduce as above), an
+ *   output distinct from its input, d distinct from scratch.  Device contents are not read on the host.  These launches are not in
+ *   the lasr_prof_* kernel table.
+ */
+#define LASR_VARFLOW_MIN_SIZE 2
+#define LASR_VARFLOW_MAX_SIZE 16384
+int lasr_varflow_reduce(const unsigned char* img_u8, const float* in, float* level0, float* out, int H, int W, void* hip_stream);
+int lasr_varflow_expand(const float* uv_coarse, float* uv_fine, int hc, int wc, int h, int w, void* hip_stream);
+int lasr_varflow_tensor(const float* I1, const float* I2, const float* uv, float* J, int H, int W, void* hip_stream);
+int lasr_varflow_weights(const float* J, const float* uv, const float* d, float* psi, int H, int W, float eps, void* hip_stream);
+int lasr_varflow_sor(const float* J, const float* psi, const float* uv, float* d, float* scratch, int H, int W, float alpha, float omega,
+                     int iters, void* hip_stream);
+int lasr_varflow_occ(const float* f_ab, const float* f_ba, float* occ, int H, int W, float tau, float s, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

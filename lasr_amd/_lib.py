@@ -135,6 +135,13 @@ SIGNATURES = {
     'lasr_reproj_workspace_bytes': (_sz, [_i, _i, _i]),
     'lasr_reproj_pixels': (_i, [_p] * 15 + [_i] * 6 + [_p]),
     'lasr_reproj_boundary': (_i, [_p] * 3 + [_i] * 4 + [_p]),
+    # lasr_amd/csrc/varflow.hip
+    'lasr_varflow_reduce': (_i, [_p] * 4 + [_i] * 2 + [_p]),
+    'lasr_varflow_expand': (_i, [_p] * 2 + [_i] * 4 + [_p]),
+    'lasr_varflow_tensor': (_i, [_p] * 4 + [_i] * 2 + [_p]),
+    'lasr_varflow_weights': (_i, [_p] * 4 + [_i] * 2 + [_f, _p]),
+    'lasr_varflow_sor': (_i, [_p] * 5 + [_i] * 2 + [_f, _f, _i, _p]),
+    'lasr_varflow_occ': (_i, [_p] * 3 + [_i] * 2 + [_f, _f, _p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -198,6 +205,7 @@ RIG_MAX_BONES, RIG_MAX_INFLUENCES = 64, 8                    # LASR_RIG_MAX_BONE
 MASKPROP_BINS, MASKPROP_MAX_SIZE, MASKPROP_MAX_RADIUS = 4096, 16384, 8   # LASR_MASKPROP_* of include/lasr_ops.h
 TRACK_MAX_SNAP, TRACK_MAX_WINDOW, TRACK_MAX_RADIUS, TRACK_MAX_SIZE, TRACK_SPLAT_ALPHA = 16, 2, 8, 8192, 192   # LASR_TRACK_* of include/lasr_ops.h
 REPROJ_MAX_RADIUS = 96                              # LASR_REPROJ_MAX_RADIUS of include/lasr_ops.h
+VARFLOW_MIN_SIZE, VARFLOW_MAX_SIZE = 2, 16384       # LASR_VARFLOW_* of include/lasr_ops.h
 
 
 class SrOptions(ctypes.Structure):

@@ -9,6 +9,8 @@ computed; when the median of its norm inside the mask of i, each axis normalised
   FlowFW/flo-%05d.pfm, FlowFW/occ-%05d.pfm, FlowBW/flo-%05d.pfm, FlowBW/occ-%05d.pfm  (flow in pixels + a ones channel, rows
   flipped before write_pfm as the reference does), JPEGImages/%05d.jpg (quality 95), Annotations/%05d.png (0 / 1)
 and i moves to j; j always moves on.  Without --loadmodel the model keeps its (seeded) random weights: the reference's dry run.
+--flow_method variational replaces the network by the classical variational flow of lasr_amd/nnutils/varflow.py (DESIGN.md section
+4.16), which needs no checkpoint: no model is built, --loadmodel is refused, and occ-*.pfm holds its forward-backward consistency map.
 Images are read and written with PIL and resized with bilinear interpolation on pixel centres (cv2.INTER_LINEAR's convention;
 uint8 images are rounded back to uint8 as cv2 does).
 """
@@ -32,6 +34,28 @@ class EmptyMask(ValueError):
     pass
 
 
+# the tuning parameters of --flow_method variational (lasr_amd/nnutils/varflow.py: DEFAULTS), one flag each
+FLOW_TUNING = (('alpha', float, 0.03, 'weight of the smoothness term'),
+               ('eps', float, 1e-3, 'regulariser of the two robust penalties sqrt(s^2 + eps^2)'),
+               ('omega', float, 1.8, 'SOR relaxation factor, inside (0, 2)'),
+               ('NW', int, 5, 'warps per pyramid level'),
+               ('NO', int, 3, 'weight updates (lagged diffusivity) per warp'),
+               ('NI', int, 10, 'SOR iterations per weight update'))
+
+
+def add_flow_arguments(p):
+    """--flow_method and the vf_* tuning flags, shared with preprocess/propagate_mask.py."""
+    p.add_argument('--flow_method', choices=('vcn', 'variational'), default='vcn',
+                   help='vcn: the network (needs --loadmodel to be more than a dry run); variational: the classical flow, no checkpoint')
+    for name, kind, default, text in FLOW_TUNING:
+        p.add_argument('--vf_' + name, type=kind, default=default, help='variational: %s (default %s)' % (text, default))
+
+
+def check_flow_arguments(p, args):
+    if args.flow_method == 'variational' and args.loadmodel is not None:
+        p.error('--flow_method variational uses no network: --loadmodel %s would be ignored, drop it' % args.loadmodel)
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description='VCN optical flow and frame selection')
     p.add_argument('--datapath', default='/ssd/kitti_scene/training/', help='folder of the frames (.../JPEGImages/.../<seq>/)')
@@ -41,7 +65,10 @@ def parse_args(argv=None):
     p.add_argument('--fac', type=float, default=1, help='squeezes the coarsest search window along y')
     p.add_argument('--flow_threshold', type=float, default=0.05, help='median normalised flow below which a frame is skipped')
     p.add_argument('--outdir', default=None, help='output folder (default ./<seqname>)')
-    return p.parse_args(argv)
+    add_flow_arguments(p)
+    args = p.parse_args(argv)
+    check_flow_arguments(p, args)
+    return args
 
 
 def seqname_of(datapath):
@@ -117,6 +144,27 @@ def flow_inference(model, imgL_o, imgR_o, testres=1., device='cuda'):
     return np.concatenate((flow, np.ones(flow.shape[:2] + (1,), flow.dtype)), -1), occ
 
 
+def variational_flow_fn(args, make=None):
+    """flow_fn(imgL, imgR) of --flow_method variational: lasr_amd.nnutils.varflow.make_flow_fn with the vf_* flags.  --testres
+    scales the frames before the flow, as it does for the network (without the padding to multiples of 64, which only the network
+    needs); flow and occ come back at the frames' size, the flow in their pixels."""
+    if make is None:
+        from lasr_amd.nnutils import varflow
+        make = varflow.make_flow_fn
+    inner = make(**{name: getattr(args, 'vf_' + name) for name, _, _, _ in FLOW_TUNING})
+    testres = float(args.testres)
+    if testres == 1:
+        return inner
+
+    def flow_fn(imgL_o, imgR_o):
+        H, W = imgL_o.shape[:2]
+        h, w = max(2, int(round(H * testres))), max(2, int(round(W * testres)))
+        flow, occ = inner(resize(imgL_o, w, h), resize(imgR_o, w, h))
+        flow = np.stack([resize(flow[:, :, 0], W, H) * (W / w), resize(flow[:, :, 1], W, H) * (H / h)], -1).astype(np.float32)
+        return np.concatenate((flow, np.ones(flow.shape[:2] + (1,), flow.dtype)), -1), resize(occ, W, H)
+    return flow_fn
+
+
 def median_flow(flow, mask, path=''):
     """auto_gen.py:161-166: the median over the mask of |flow| with x / y divided by half the mask's width / height."""
     ys, xs = np.where(mask)
@@ -171,9 +219,13 @@ def run(args, flow_fn):
 
 def main(argv=None):
     args = parse_args(argv)
-    model = build_model(args)
+    if args.flow_method == 'variational':
+        flow_fn = variational_flow_fn(args)
+    else:
+        model = build_model(args)
+        flow_fn = lambda a, b: flow_inference(model, a, b, args.testres)   # noqa: E731
     try:
-        run(args, lambda a, b: flow_inference(model, a, b, args.testres))
+        run(args, flow_fn)
     except EmptyMask as e:
         sys.exit('auto_gen.py: %s' % e)
 

@@ -10,7 +10,9 @@ preprocess/auto_gen.py and written as %05d.png, one per frame of --datapath in s
 (the JPEGImages -> Annotations substitution of auto_gen.py, which runs next unchanged), in the reference's encoding: 128 in the
 red channel (mask.py:71-76).  A key PNG of any non-zero encoding is accepted.  maskprop.json next to the masks records the
 parameters, the per-frame areas and the round-trip IoU.  Without --loadmodel the flow network keeps its seeded random weights: the
-same dry run as auto_gen.py.  Quality on real footage is unverified; --roundtrip is the available check.
+same dry run as auto_gen.py.  --flow_method variational carries the mask along the classical variational flow instead
+(lasr_amd/nnutils/varflow.py; the vf_* flags of auto_gen.py): no checkpoint, no model, and --loadmodel is
+refused.  Quality on real footage is unverified; --roundtrip is the available check.
 """
 import argparse
 import glob
@@ -66,7 +68,9 @@ def parse_args(argv=None):
     p.add_argument('--force', action='store_true', help='write into an Annotations folder that already holds files')
     for name, kind, default, text in TUNING:
         p.add_argument('--' + name, type=kind, default=default, help='%s (default %s)' % (text, default))
+    auto_gen.add_flow_arguments(p)
     args = p.parse_args(argv)
+    auto_gen.check_flow_arguments(p, args)
     seen = [k for k, _ in args.key]
     if len(set(seen)) != len(seen):
         p.error('--key names frame %d twice' % [k for k in seen if seen.count(k) > 1][0])
@@ -161,10 +165,14 @@ def run(args, flow_fn, propagate=None, roundtrip=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    model = auto_gen.build_model(args)
+    if args.flow_method == 'variational':
+        flow_fn = auto_gen.variational_flow_fn(args)
+    else:
+        model = auto_gen.build_model(args)
+        flow_fn = lambda a, b: auto_gen.flow_inference(model, a, b, args.testres)   # noqa: E731
     try:
         from lasr_amd.nnutils.maskprop import EmptyPropagation
-        run(args, lambda a, b: auto_gen.flow_inference(model, a, b, args.testres))
+        run(args, flow_fn)
     except (EmptyPropagation, AnnotationsExist, ValueError) as e:
         sys.exit('propagate_mask.py: %s' % e)
 
