@@ -1151,6 +1151,66 @@ int lasr_varflow_sor(const float* J, const float* psi, const float* uv, float* d
                      int iters, void* hip_stream);
 int lasr_varflow_occ(const float* f_ab, const float* f_ba, float* occ, int H, int W, float tau, float s, void* hip_stream);
 
+/*
+ * ---- Motion segmentation of preprocess/auto_mask.py (lasr_amd/csrc/motionseg.hip, lasr_amd/nnutils/motionseg.py, DESIGN.md
+ * section 4.17) -------------------------------------------------------------------------------------------------------------------
+ * This project's own addition: the reference fills Annotations/ with a detector (preprocess/mask.py), which stays out of scope;
+ * nothing of it is restated here, and parity is to the float64 restatement in tests/motionseg_restated.py and to closed forms only.
+ * The four entry points score every pixel of one ordered frame pair a -> b by how badly its flow follows the dominant
+ * (camera-induced) motion; the key masks preprocess/propagate_mask.py starts from are made of those scores on the host.  Fields
+ * are fp32 [H,W], flows fp32 [H,W,2] = (x, y) in pixels, all dense and on the device.  Per-pixel arithmetic is fp32 in the
+ * restatement's operation order (-ffp-contract=off); everything summed over pixels is fp64.
+ *
+ * lasr_motionseg_conf: q = p + f_ab(p).  q outside [0,W-1] x [0,H-1] (or not finite): conf = 0; else
+ *   conf = exp(-|f_ab(p) + bilinear(f_ba, q)|^2 / (2 tau^2)) on the taps of lasr_maskprop_unary (upper taps clamped), and a result
+ *   that is not a number is 0.  Default tau 1.
+ * The motion model, on normalised coordinates in fp64, s = 0.5 max(H, W), X = (x - 0.5 (W-1)) / s, Y = (y - 0.5 (H-1)) / s:
+ *   u_m = t0 + t1 X + t2 Y + t6 X^2 + t7 XY,  v_m = t3 + t4 X + t5 Y + t6 XY + t7 Y^2   (the sums from left to right, X and Y
+ *   rounded to fp32).  model 0 = translation (t0, t3), 1 = affine (t0..t5), 2 = quadratic (all eight: the instantaneous flow of a
+ *   plane, or of a rotating camera).
+ * state, double [LASR_MOTIONSEG_STATE]: theta[8], sigma, med, n (the pixels with conf >= 0.5), status (0 ok, 1 degenerate).  The
+ *   caller starts from theta = 0, sigma = +inf.
+ * lasr_motionseg_moments: the sums of one IRLS iteration from `state`.  A pixel with conf not > 0 or a flow that is not finite is
+ *   SKIPPED (never multiplied by 0: 0 * NaN would poison every sum).  r^2 = (u - u_m)^2 + (v - v_m)^2; w = conf for sigma = inf,
+ *   else conf / (1 + r^2 / sigma^2)^2 (Geman-McClure).  LASR_MOTIONSEG_MOMENTS = 28 sums: sum w X^i Y^j for i + j <= 4 (15, by
+ *   degree and then by j: slot d (d + 1) / 2 + j), sum w u X^i Y^j and sum w v X^i Y^j for i + j <= 2 (6 + 6), sum w (u^2 + v^2);
+ *   monomials and products in fp64.  min(LASR_MOTIONSEG_BLOCKS, ceil(HW / 256)) workgroups of 256 threads; workgroup b owns the
+ *   pixels b 256 + lane, + 256 * the number of workgroups, ... (fixed by H and W); 28 fp64 accumulators per lane, folded across the
+ *   wave by shuffles, across the four waves through LDS in wave order, and written as row b of partials
+ *   [LASR_MOTIONSEG_BLOCKS, LASR_MOTIONSEG_MOMENTS]; workgroup 0 writes the rows of the workgroups that do not exist as zeros, so the
+ *   caller need not clear partials.  hist uint32 [LASR_MOTIONSEG_BINS] += the pixels with conf >= 0.5 by
+ *   min(floor(16 sqrt(r^2)), 1023): ADDED to what it holds (the caller zeroes it), LDS-private per workgroup and merged with
+ *   integer atomics, as lasr_maskprop_hist.
+ * lasr_motionseg_solve: one workgroup.  Folds the rows of partials in index order; assembles the 8 x 8 normal matrix
+ *   sum w (B_u B_u^T + B_v B_v^T) and the right-hand side sum w (u B_u + v B_v) from the 28 sums only; a parameter that is switched
+ *   off has its row and column replaced by the identity's and its right-hand side by 0; adds ridge trace(A) / 8 to the diagonal;
+ *   solves the STEP A d = b - A0 theta_in (A0: the matrix before the ridge) by Cholesky in fp64 and writes theta = theta_in + d,
+ *   so the fixed point is the un-ridged solution.  n = the total of hist.  A pivot not > 0, a step that is not finite or n = 0:
+ *   status = 1, theta, sigma and med stay.  Else med = (the first bin at which the cumulative count reaches ceil(n / 2) + 0.5) / 16,
+ *   sigma = max(k_sigma med, sigma_min), status = 0.  The scale is LAGGED: the histogram is of the residuals against theta_in.
+ *   H and W are checked only.  Defaults k_sigma 3, sigma_min 0.25, ridge 1e-9, 8 iterations.
+ * lasr_motionseg_evidence: e = conf clamp(r^2 / sigma^2 - kappa, -U, U) against state, 0 where the pixel is skipped; accumulate 0
+ *   writes evid, 1 adds to it.  Defaults kappa 4, U 6.
+ * One IRLS iteration is a memset of hist, moments and solve; theta, sigma and status never visit the host inside a pair.
+ * No entry point uses floating-point atomics: the same input gives the same bits on every run.
+ * Checked on the host before any launch (LASR_E_BADARG): 0 <= H, W <= LASR_MOTIONSEG_MAX_SIZE; model in {0, 1, 2}; tau, k_sigma,
+ *   sigma_min, kappa, U > 0 and ridge >= 0, all finite; accumulate in {0, 1}; then empty work (H == 0 or W == 0) is LASR_OK with
+ *   nothing launched; then every pointer non-NULL and every output distinct from the inputs (state is solve's input and output).
+ *   Device contents are not read on the host.  These launches are not in the lasr_prof_* kernel table.
+ */
+#define LASR_MOTIONSEG_MAX_SIZE 16384
+#define LASR_MOTIONSEG_BLOCKS 256
+#define LASR_MOTIONSEG_MOMENTS 28
+#define LASR_MOTIONSEG_BINS 1024
+#define LASR_MOTIONSEG_STATE 12
+int lasr_motionseg_conf(const float* f_ab, const float* f_ba, float* conf, int H, int W, float tau, void* hip_stream);
+int lasr_motionseg_moments(const float* flow, const float* conf, const double* state, double* partials, unsigned* hist, int H, int W,
+                           void* hip_stream);
+int lasr_motionseg_solve(const double* partials, const unsigned* hist, double* state, int H, int W, int model, float k_sigma,
+                         float sigma_min, float ridge, void* hip_stream);
+int lasr_motionseg_evidence(const float* flow, const float* conf, const double* state, float* evid, int H, int W, float kappa, float U,
+                            int accumulate, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

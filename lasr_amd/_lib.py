@@ -142,6 +142,11 @@ SIGNATURES = {
     'lasr_varflow_weights': (_i, [_p] * 4 + [_i] * 2 + [_f, _p]),
     'lasr_varflow_sor': (_i, [_p] * 5 + [_i] * 2 + [_f, _f, _i, _p]),
     'lasr_varflow_occ': (_i, [_p] * 3 + [_i] * 2 + [_f, _f, _p]),
+    # lasr_amd/csrc/motionseg.hip
+    'lasr_motionseg_conf': (_i, [_p] * 3 + [_i] * 2 + [_f, _p]),
+    'lasr_motionseg_moments': (_i, [_p] * 5 + [_i] * 2 + [_p]),
+    'lasr_motionseg_solve': (_i, [_p] * 3 + [_i] * 3 + [_f] * 3 + [_p]),
+    'lasr_motionseg_evidence': (_i, [_p] * 4 + [_i] * 2 + [_f, _f, _i, _p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -206,6 +211,7 @@ MASKPROP_BINS, MASKPROP_MAX_SIZE, MASKPROP_MAX_RADIUS = 4096, 16384, 8   # LASR_
 TRACK_MAX_SNAP, TRACK_MAX_WINDOW, TRACK_MAX_RADIUS, TRACK_MAX_SIZE, TRACK_SPLAT_ALPHA = 16, 2, 8, 8192, 192   # LASR_TRACK_* of include/lasr_ops.h
 REPROJ_MAX_RADIUS = 96                              # LASR_REPROJ_MAX_RADIUS of include/lasr_ops.h
 VARFLOW_MIN_SIZE, VARFLOW_MAX_SIZE = 2, 16384       # LASR_VARFLOW_* of include/lasr_ops.h
+MOTIONSEG_MAX_SIZE, MOTIONSEG_BLOCKS, MOTIONSEG_MOMENTS, MOTIONSEG_BINS, MOTIONSEG_STATE = 16384, 256, 28, 1024, 12   # LASR_MOTIONSEG_*
 
 
 class SrOptions(ctypes.Structure):
