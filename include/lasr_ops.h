@@ -894,6 +894,62 @@ int lasr_bake_resolve(const float* accum, const int* faces, const float* fallbac
                       int R, void* hip_stream);
 
 /*
+ * ---- Completing a baked atlas where no frame looked (lasr_amd/csrc/bake_fill.hip, nnutils/bake.py) --------
+ * This project's own addition, like the bake: the reference has no counterpart, nothing of it is restated here, and parity is to
+ * the float64 / float32 restatement in tests/bake_fill_restated.py and to closed forms only.  A texel with weight == 0 first takes
+ * the colour of its mirror image on the bilaterally symmetric rest shape (lasr_bake_mirror), then what is still unfilled is
+ * smoothed from its neighbours (lasr_bake_blend, one Jacobi iteration per call).  Neither kernel is in the lasr_prof_* table.
+ *
+ * lasr_bake_mirror:
+ *   rest_verts [V,3]     the rest mesh (rig.npz of extract.py --rig), symmetric about the plane x[axis] = 0
+ *   faces      [F,3]     int32; a face with an index outside [0, V) is no source, and its own texels are not filled
+ *   texels     [M]       int32, the texels to fill as i = f R R + j (the caller lists those with weight == 0); an entry outside
+ *                        [0, F R R) is skipped
+ *   textures   [F,R*R,3], weight [F,R*R]   what lasr_bake_resolve wrote; read only
+ *   out_textures [F,R*R,3]   only the three floats of every filled texel are written (the caller passes a copy of textures);
+ *                        must not overlap textures
+ *   src [M] int32, d2 [M] fp32   always written, see below
+ *   Per entry m with texel (f, j): p = c0 V0 + c1 V1 + c2 V2 at the centroid (c0, c1, c2) of texel j (as lasr_bake_accumulate), p'
+ *   = p with coordinate `axis` negated.  g = the face of smallest squared distance to p' among the faces with indices in [0, V)
+ *   (point_triangle.h: interior projection or the nearest clamped edge projection), the lowest face index among equal distances;
+ *   d2[m] = that distance (+inf when there is none), (b0, b1, b2) = the barycentrics of the closest point.  Refused, src[m] = -1 - reason:
+ *     reason 3 (LASR_BAKE_MIRROR_NO_FACE)   the entry is out of range, face f has an index outside [0, V), or no face is valid;
+ *     reason 0 (LASR_BAKE_MIRROR_FAR)       not d2 <= max_d2;
+ *     reason 1 (LASR_BAKE_MIRROR_NORMAL)    not n(f)' . n(g) > 0, with n = (V1 - V0) x (V2 - V0) unnormalised and n(f)' = n(f) with
+ *                                           coordinate `axis` negated (a zero-area f or g gives 0: refused);
+ *     reason 2 (LASR_BAKE_MIRROR_UNSEEN)    not weight[g, j'] > 0, with j' = surface_texel(b0', b1', R) (sr_device.h) of
+ *                                           b_k' = b_k (1 - 2^-20) + 2^-20 / 3: the closest point pulled a millionth of the face
+ *                                           towards its centroid, so that a point on an edge or a corner of g (b0 = 1, or b0 + b1
+ *                                           rounded above 1) names a texel that touches it.
+ *   Otherwise out_textures[f, j] = textures[g, j'] (the same bits) and src[m] = g R R + j'.  Only texels a frame saw are sources:
+ *   fills do not chain, and the result does not depend on any order.  One entry per lane, 256 per block; the faces pass through
+ *   LDS in tiles of LASR_BAKE_FILL_TILE; no atomics.
+ * lasr_bake_blend: one Jacobi iteration over the texel adjacency; in, out [F,R*R,3], fixed [F,R*R] uint8, nbr [F,3] int32.
+ *   Corner k of a face is weighed by c_k; face edge k is c_k = 0, from end p to end q = corners (1,2), (2,0), (0,1) for k = 0, 1, 2.
+ *   Texel j = iy R + ix is the lower triangle L(ix, iy) when ix + iy <= R-1, else the upper triangle U(cx, cy), cx = R-1-ix,
+ *   cy = R-1-iy.  L(ix, iy) has the neighbours n0 = U(ix-1, iy) if ix >= 1 else across face edge 0, n1 = U(ix, iy-1) if iy >= 1
+ *   else across face edge 1, n2 = U(ix, iy) if ix + iy <= R-2 else across face edge 2; U(cx, cy) has n0 = L(cx+1, cy),
+ *   n1 = L(cx, cy+1), n2 = L(cx, cy).  Along face edge k a border texel has the slot s counted from end p: R-1-iy (k = 0), ix
+ *   (k = 1), iy (k = 2); the texel of slot s is (ix, iy) = (0, R-1-s), (s, 0), (R-1-s, s).  nbr[f, k] = ((g 3 + k') 2 + same)
+ *   names the face g and its edge k' on the other side (slot s' = s when same = 1: end p of both edges is the same vertex; else
+ *   s' = R-1-s), or is negative: no neighbour.  A code that names a face outside [0, F) counts as negative.
+ *   fixed != 0: out = in.  Else out = (((0 + n0) + n1) + n2) / count per channel over the neighbours that exist, in that order,
+ *   fp32 without contraction; count == 0: out = in.
+ * Checked on the host before any launch (LASR_E_BADARG): V >= 1, F >= 0, 1 <= R <= LASR_BAKE_MAX_RES, 4 F R R <= INT_MAX (blend
+ *   also: 6 F + 5 <= INT_MAX, the range of an nbr code); M >= 0; axis in 0..2; max_d2 >= 0 and finite; then M == 0 or F == 0
+ *   (blend: F == 0) is LASR_OK with nothing launched; then every pointer non-NULL, out_textures != textures, in != out.  Device
+ *   contents are not read on the host.
+ */
+#define LASR_BAKE_FILL_TILE 256
+#define LASR_BAKE_MIRROR_FAR 0
+#define LASR_BAKE_MIRROR_NORMAL 1
+#define LASR_BAKE_MIRROR_UNSEEN 2
+#define LASR_BAKE_MIRROR_NO_FACE 3
+int lasr_bake_mirror(const float* rest_verts, const int* faces, const int* texels, const float* textures, const float* weight,
+                     float* out_textures, int* src, float* d2, int V, int F, int R, int M, int axis, float max_d2, void* hip_stream);
+int lasr_bake_blend(const float* in, float* out, const unsigned char* fixed, const int* nbr, int F, int R, void* hip_stream);
+
+/*
  * ---- Rigged glTF export of scripts/export_gltf.py (lasr_amd/csrc/rig.hip, lasr_amd/nnutils/rig.py) --------
  * This project's own addition: the reference has no exporter, nothing of it is restated here, and parity is to the float64
  * restatement in tests/rig_restated.py and to the project's own linear-blend skinning (lasr_lbs_forward) only.  The four entry

@@ -117,6 +117,9 @@ SIGNATURES = {
     # lasr_amd/csrc/bake.hip
     'lasr_bake_accumulate': (_i, [_p] * 7 + [_i] * 8 + [_p]),
     'lasr_bake_resolve': (_i, [_p] * 5 + [_i] * 3 + [_p]),
+    # lasr_amd/csrc/bake_fill.hip
+    'lasr_bake_mirror': (_i, [_p] * 8 + [_i] * 5 + [_f, _p]),
+    'lasr_bake_blend': (_i, [_p] * 4 + [_i] * 2 + [_p]),
     # lasr_amd/csrc/rig.hip
     'lasr_rig_pack': (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
     'lasr_rig_quats': (_i, [_p, _i, _i, _p, _p]),

@@ -7,6 +7,9 @@ that frame's mesh, and averaged with the weight |n . d|^power (lasr_bake_accumul
 Scenes are in camera space with OpenCV axes and pixel intrinsics fx fy px py of the H x W frame, as in lasr_amd/vis.py; the
 raster is the square of side IS = max(H, W) with the NDC mapping of vis.shade.  Frames are processed CHUNK_FRAMES at a time: one
 raster and one accumulate launch per chunk, one resolve launch at the end.
+
+complete_texture fills the texels no frame saw (opt-in; csrc/bake_fill.hip): mirror_fill copies the texel of the mirror image
+over the symmetry plane of the rest shape, blend_fill smooths what is still unfilled over the texel adjacency (face_neighbours).
 """
 import torch
 
@@ -99,6 +102,149 @@ def bake_texture(verts, faces, K, frames, masks=None, texture_res=8, power=2, fa
                   IS, H, W, power)
     _lib.call('lasr_bake_resolve', accum, faces32, fallback, textures, weight, V, F, R)
     return textures, weight
+
+
+# ---- completing the atlas where no frame looked (csrc/bake_fill.hip; DESIGN.md section 4.11, "Fill") -----------------------------
+# Own addition like the bake: parity is to the restatement in tests/bake_fill_restated.py and to closed forms only.
+SEEN, MIRRORED, BLENDED = 0, 1, 2                     # the codes of `source`
+MIRROR_REASONS = ('too far', 'normals disagree', 'source unseen', 'no valid face')   # src = -1 - reason (LASR_BAKE_MIRROR_*)
+
+
+def _atlas(name, faces, textures, other, other_name):
+    """Shared argument checks of the fills: faces integer [F,3], textures [F,R*R,3], `other` [F,R*R] -> (F, R)."""
+    if faces.ndimension() != 2 or faces.shape[1] != 3 or faces.is_floating_point():
+        raise ValueError('%s: faces must be integer [F, 3], got %s %s' % (name, faces.dtype, tuple(faces.shape)))
+    F = faces.shape[0]
+    if textures.ndimension() != 3 or textures.shape[0] != F or textures.shape[2] != 3 or not textures.is_floating_point():
+        raise ValueError('%s: textures must be floating [F = %d, R*R, 3], got %s %s' % (name, F, textures.dtype, tuple(textures.shape)))
+    RR = int(textures.shape[1])
+    R = int(round(RR ** 0.5))
+    if R * R != RR or not 1 <= R <= _lib.BAKE_MAX_RES:
+        raise ValueError('%s: textures hold %d texels per face, not R*R with R in 1..%d' % (name, RR, _lib.BAKE_MAX_RES))
+    if tuple(other.shape) != (F, RR):
+        raise ValueError('%s: %s must be [%d, %d] like the textures, got %s' % (name, other_name, F, RR, tuple(other.shape)))
+    if F * RR * 4 > 0x7fffffff:
+        raise ValueError('%s: %d faces x %d texels exceed the 32-bit texel index' % (name, F, RR))
+    return F, R
+
+
+def face_neighbours(faces, num_verts=None):
+    """faces [F,3] integer (device) -> nbr int32 [F,3]: nbr[f, k] = (g * 3 + k') * 2 + same names the face g and its edge k' that
+    share edge k of f (edge k lies opposite corner k and runs from corner (k+1)%3 to corner (k+2)%3; same = 1 when both edges start
+    at the same vertex), or -1: an edge with anything but exactly two incident faces, or a face with a repeated or out-of-range
+    index (negative, or >= num_verts where given).  Sort / unique on the device; a cold path."""
+    if not torch.is_tensor(faces):
+        raise TypeError('face_neighbours: faces must be a tensor')
+    _lib.need_cuda(faces)
+    if faces.ndimension() != 2 or faces.shape[1] != 3 or faces.is_floating_point():
+        raise ValueError('face_neighbours: faces must be integer [F, 3], got %s %s' % (faces.dtype, tuple(faces.shape)))
+    F = faces.shape[0]
+    if F * 6 + 5 > 0x7fffffff:
+        raise ValueError('face_neighbours: %d faces exceed the 32-bit neighbour code' % F)
+    f = faces.long()
+    good = (f >= 0).all(1) & (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])
+    if num_verts is not None:
+        good &= (f < int(num_verts)).all(1)
+    p, q = f[:, [1, 2, 0]].reshape(-1), f[:, [2, 0, 1]].reshape(-1)                # ends of edge id = f * 3 + k
+    ids = torch.arange(3 * F, device=f.device)
+    base = (int(f.max()) + 1) if F else 1
+    key = torch.where(good.repeat_interleave(3), torch.minimum(p, q) * base + torch.maximum(p, q), -1 - ids)
+    key, order = torch.sort(key, stable=True)
+    _, inverse, counts = torch.unique_consecutive(key, return_inverse=True, return_counts=True)
+    twice = counts[inverse] == 2
+    first = twice.clone()
+    first[1:] &= key[1:] != key[:-1]                                               # the first entry of each pair
+    a, b = order[first], order[torch.roll(first, 1)]                               # and the second, which follows it
+    same = (p[a] == p[b]).long()
+    nbr = torch.full((3 * F,), -1, dtype=torch.long, device=f.device)
+    nbr[a] = b * 2 + same
+    nbr[b] = a * 2 + same
+    return nbr.to(torch.int32).reshape(F, 3)
+
+
+def mirror_fill(rest_verts, faces, textures, weight, axis=0, tol=0.05):
+    """Texels with weight == 0 take the texel their mirror image falls on: rest_verts [V,3] is the rest shape (rig.npz of extract.py
+    --rig), symmetric about the plane x[axis] = 0; tol is the largest accepted distance between the mirrored sample point and
+    the surface as a fraction of the rest bounding-box diagonal.  -> (textures (a copy, filled), source uint8 [F,R*R]: 0 seen,
+    1 mirrored, 2 left for blend_fill, info: texels int32 [M], src int32 [M] (g R R + j' or -1 - reason of MIRROR_REASONS), d2
+    [M], max_d2)."""
+    for name, t in (('rest_verts', rest_verts), ('faces', faces), ('textures', textures), ('weight', weight)):
+        if not torch.is_tensor(t):
+            raise TypeError('mirror_fill: %s must be a tensor' % name)
+    _lib.need_cuda(rest_verts, faces, textures, weight)
+    if rest_verts.ndimension() != 2 or rest_verts.shape[1] != 3 or rest_verts.shape[0] < 1:
+        raise ValueError('mirror_fill: rest_verts must be [V >= 1, 3], got %s' % (tuple(rest_verts.shape),))
+    V = rest_verts.shape[0]
+    F, R = _atlas('mirror_fill', faces, textures, weight, 'weight')
+    axis, tol = int(axis), float(tol)
+    if axis not in (0, 1, 2):
+        raise ValueError('mirror_fill: axis must be 0, 1 or 2, got %d' % axis)
+    if not 0. <= tol < float('inf'):
+        raise ValueError('mirror_fill: tol must be a finite fraction >= 0, got %g' % tol)
+    rest = rest_verts.detach().float().contiguous()
+    faces32 = faces.to(torch.int32).contiguous()
+    textures = textures.detach().float().contiguous()
+    weight = weight.detach().float().contiguous()
+    unseen = ~(weight > 0)
+    texels = torch.nonzero(unseen.reshape(-1)).reshape(-1).to(torch.int32)
+    M = int(texels.shape[0])
+    diag = float((rest.max(0).values - rest.min(0).values).norm())
+    max_d2 = (tol * diag) ** 2
+    if not max_d2 < float('inf'):
+        raise ValueError('mirror_fill: rest_verts must be finite')
+    out = textures.clone()
+    src = torch.full((M,), -1 - len(MIRROR_REASONS), dtype=torch.int32, device=rest.device)
+    d2 = torch.full((M,), float('inf'), dtype=torch.float32, device=rest.device)
+    _lib.call('lasr_bake_mirror', rest, faces32, texels, textures, weight, out, src, d2, V, F, R, M, axis, max_d2, on=rest)
+    source = unseen.to(torch.uint8) * BLENDED
+    source.view(-1)[texels[src >= 0].long()] = MIRRORED
+    return out, source, dict(texels=texels, src=src, d2=d2, max_d2=max_d2)
+
+
+def blend_fill(textures, source, faces, iters=64):
+    """`iters` Jacobi iterations over the texel adjacency (face_neighbours): every texel with source == 2 becomes the mean of its
+    edge neighbours, seen and mirrored texels stay fixed.  Ping-pong between two buffers, one launch each (as
+    maskprop.meanfield); the input is not written.  -> textures [F,R*R,3]."""
+    for name, t in (('textures', textures), ('source', source), ('faces', faces)):
+        if not torch.is_tensor(t):
+            raise TypeError('blend_fill: %s must be a tensor' % name)
+    _lib.need_cuda(textures, source, faces)
+    F, R = _atlas('blend_fill', faces, textures, source, 'source')
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError('blend_fill: iters must be >= 0, got %d' % iters)
+    cur = textures.detach().float().contiguous()
+    if iters == 0 or F == 0:
+        return cur.clone()
+    fixed = (source != BLENDED).to(torch.uint8).contiguous()
+    nbr = face_neighbours(faces).contiguous()
+    bufs = [torch.empty_like(cur), torch.empty_like(cur)]
+    for k in range(iters):
+        dst = bufs[k & 1]
+        _lib.call('lasr_bake_blend', cur, dst, fixed, nbr, F, R)
+        cur = dst
+    return cur
+
+
+def complete_texture(faces, textures, weight, fill='mirror', rest_verts=None, axis=0, tol=0.05, iters=64):
+    """The atlas of bake_texture completed where weight == 0.  fill 'mirror': mirror_fill over rest_verts, then blend_fill on what
+    it left; 'blend': blend_fill alone.  -> (textures, source uint8 [F,R*R]: 0 seen, 1 mirrored, 2 blended, info of mirror_fill or
+    None)."""
+    if fill not in ('mirror', 'blend'):
+        raise ValueError("complete_texture: fill must be 'mirror' or 'blend', got %r" % (fill,))
+    info = None
+    if fill == 'mirror':
+        if rest_verts is None:
+            raise ValueError('complete_texture: the mirror fill needs rest_verts (rig.npz of extract.py --rig)')
+        textures, source, info = mirror_fill(rest_verts, faces, textures, weight, axis, tol)
+    else:
+        for name, t in (('faces', faces), ('textures', textures), ('weight', weight)):
+            if not torch.is_tensor(t):
+                raise TypeError('complete_texture: %s must be a tensor' % name)
+        _lib.need_cuda(faces, textures, weight)
+        _atlas('complete_texture', faces, textures, weight, 'weight')
+        source = (~(weight > 0)).to(torch.uint8) * BLENDED
+    return blend_fill(textures, source, faces, iters), source, info
 
 
 def render_baked(verts, faces, K, textures, H, W, background=(0., 0., 0.)):

@@ -4,12 +4,18 @@ no counterpart -- DESIGN.md section 4.11).
 
     python scripts/bake_texture.py --testdir log/camel-5/ --seqname camel \\
         [--texture_res 8] [--power 2] [--pose_frame 0] [--no_mask] [--outpath DIR/baked] [--preview out.gif]
+        [--fill none|blend|mirror] [--rig DIR/rig.npz] [--symidx 0] [--sym_tol 0.05] [--fill_iters 64]
 
 Reads what render_vis.py reads: the frames of configs/<seqname>.config, per frame id i <testdir>/pred<i>.ply (or .obj) in camera
 space and the intrinsics row of cam<i>.txt, and the silhouettes of the matching Annotations folder.  Every texel of the per-face
 surface textures is averaged over the frames that see it (lasr_amd/nnutils/bake.py, csrc/bake.hip); texels no frame sees take
 the mesh's vertex colours.  Writes <outpath>.obj / .mtl / .png (the mesh of --pose_frame with the atlas) and <outpath>_weight.npy,
 and with --preview a GIF of the baked mesh rendered back into every frame's camera beside the video frame.
+
+--fill (off by default; without it every output is what it was) completes the texels no frame saw, the far side of a monocular
+video above all: `mirror` copies the texel of the mirror image over the symmetry plane x[symidx] = 0 of the rest shape (rig.npz of
+extract.py --rig), `blend` smooths what is still unfilled from its neighbours (csrc/bake_fill.hip).  Also writes
+<outpath>_source.npy (per texel 0 seen, 1 mirrored, 2 blended) and prints `filled: mirrored X %, blended Y %`.
 """
 import argparse
 import os
@@ -32,7 +38,35 @@ def parse_args(argv=None):
     p.add_argument('--no_mask', dest='mask', action='store_false', help='do not restrict the samples to the silhouettes')
     p.add_argument('--outpath', default='', help='output path without extension (default: <testdir>/baked)')
     p.add_argument('--preview', default='', help='GIF to write: the baked mesh in every frame\'s camera, beside the frame')
+    p.add_argument('--fill', default='none', choices=('none', 'blend', 'mirror'),
+                   help='complete the texels no frame saw: blend = smooth them from their neighbours; mirror = first copy the '
+                        'mirror image over the symmetry plane of the rest shape (needs --rig), then blend what is left')
+    p.add_argument('--rig', default='', help='rig.npz of extract.py --rig, for its rest shape (default: <testdir>/rig.npz)')
+    p.add_argument('--symidx', default=0, type=int, help='the rest shape is symmetric about the plane x[symidx] = 0 (as optimize.py)')
+    p.add_argument('--sym_tol', default=0.05, type=float,
+                   help='--fill mirror: largest distance of a mirrored point from the surface, as a fraction of the rest '
+                        'bounding-box diagonal (a default nobody has measured on a real reconstruction)')
+    p.add_argument('--fill_iters', default=64, type=int,
+                   help='--fill: Jacobi iterations of the blend; the seam is feathered over about sqrt(iters) texels (a default '
+                        'nobody has measured on a real reconstruction)')
     return p.parse_args(argv)
+
+
+def load_rest_shape(path, face):
+    """rest_verts float32 [V,3] of rig.npz, refused (ValueError) when the file is missing or is not the rig of these meshes."""
+    if not os.path.exists(path):
+        raise ValueError('--fill mirror needs the rest shape: %s does not exist (write it with extract.py --rig)' % path)
+    with np.load(path) as npz:
+        if 'rest_verts' not in npz.files or 'faces' not in npz.files:
+            raise ValueError('%s holds no rest_verts / faces: it is not what extract.py --rig writes' % path)
+        rest, rf = np.asarray(npz['rest_verts'], np.float32), np.asarray(npz['faces'])
+    face = np.asarray(face)
+    if rf.shape != face.shape or (rf != face).any():
+        raise ValueError('the faces of %s differ from the topology of the pred<i> meshes: run extract.py --rig on the same '
+                         'checkpoint' % path)
+    if rest.ndim != 2 or rest.shape[1] != 3 or not np.isfinite(rest).all() or (face.size and face.max() >= rest.shape[0]):
+        raise ValueError('rest_verts of %s must be finite [V, 3] and hold every vertex the faces name (extract.py --rig)' % path)
+    return rest
 
 
 def check_topology(faces_list, frame_ids):
@@ -83,6 +117,15 @@ def main(argv=None):
         face = check_topology(faces, ids)
     except ValueError as e:
         raise SystemExit('bake_texture.py: %s' % e)
+    rest = None
+    if args.fill != 'none':
+        if args.symidx not in (0, 1, 2) or not 0 <= args.sym_tol < float('inf') or args.fill_iters < 0:
+            raise SystemExit('bake_texture.py: --symidx must be 0, 1 or 2, --sym_tol a finite fraction >= 0, --fill_iters >= 0')
+    if args.fill == 'mirror':
+        try:
+            rest = load_rest_shape(args.rig or os.path.join(args.testdir, 'rig.npz'), face)
+        except ValueError as e:
+            raise SystemExit('bake_texture.py: %s' % e)
     H, W = imgs[0].shape[:2]
     R = args.texture_res
     tv = torch.stack(verts).to(dev)
@@ -93,6 +136,11 @@ def main(argv=None):
     fallback = colors[args.pose_frame].to(dev).float() / 255.
     with torch.no_grad():
         textures, weight = bake.bake_texture(tv, tf, tK, frames, masks, texture_res=R, power=args.power, fallback=fallback)
+        source = None
+        if args.fill != 'none':                        # the .obj / .png and the preview carry the completed atlas
+            textures, source, _ = bake.complete_texture(tf, textures, weight, fill=args.fill,
+                                                        rest_verts=None if rest is None else torch.from_numpy(rest).to(dev),
+                                                        axis=args.symidx, tol=args.sym_tol, iters=args.fill_iters)
     out = args.outpath or os.path.join(args.testdir, 'baked')
     if os.path.dirname(out):
         os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -100,6 +148,11 @@ def main(argv=None):
     w = weight.cpu().numpy()
     np.save(out + '_weight.npy', w)
     print('baked %d faces x %d texels, seen %.1f %%' % (face.shape[0], R * R, 100. * float((w > 0).mean())))
+    if source is not None:
+        s = source.cpu().numpy()
+        np.save(out + '_source.npy', s)
+        print('filled: mirrored %.1f %%, blended %.1f %%' % (100. * float((s == bake.MIRRORED).mean()),
+                                                             100. * float((s == bake.BLENDED).mean())))
 
     if args.preview:
         pil = []                                       # native size, no resampling: the video frame left, the render right
