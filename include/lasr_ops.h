@@ -1267,6 +1267,55 @@ int lasr_motionseg_solve(const double* partials, const unsigned* hist, double* s
 int lasr_motionseg_evidence(const float* flow, const float* conf, const double* state, float* evid, int H, int W, float kappa, float U,
                             int accumulate, void* hip_stream);
 
+/*
+ * ---- Shape scores of scripts/eval_shape.py (lasr_amd/csrc/meshcheck.hip, lasr_amd/nnutils/meshcheck.py) ----
+ * This project's own addition: the reference has no counterpart, nothing of it is restated here, and parity is to the restatement
+ * in tests/meshcheck_restated.py and to closed forms only.  Per frame of a sequence of meshes with one topology: which pairs of
+ * faces pass through each other, the signed volume and the area.  verts [T,V,3] fp32, faces [F,3] int32 shared by the frames.
+ *
+ * Definition.  orient(a, b, c, d) = ((b - a) x (c - a)) . (d - a) in fp32 without contraction: u = b - a, w = c - a, the cross
+ *   components u_y w_z - u_z w_y, u_z w_x - u_x w_z, u_x w_y - u_y w_x, e = d - a, the dot (c_x e_x + c_y e_y) + c_z e_z.
+ *   An edge (p, q) PIERCES the triangle (a, b, c) iff orient(a, b, c, p) and orient(a, b, c, q) have strictly opposite signs and
+ *   orient(p, q, a, b), orient(p, q, b, c), orient(p, q, c, a) are all > 0 or all < 0.  Faces i < j are a CANDIDATE pair iff they
+ *   share no vertex index and their axis-aligned boxes overlap (closed comparisons on the fp32 inputs: no rounding).  A candidate
+ *   pair INTERSECTS iff one of the edges (a, b), (b, c), (c, a) of i pierces j or one of j's pierces i.  Every sign test is strict:
+ *   touching and coplanar overlap do not count.  Faces that share a vertex are never tested: a fold between neighbours goes unseen.
+ *   volume[t] = (sum_f term_f) / 6 with term = (a_x (b_y c_z - b_z c_y) + a_y (b_z c_x - b_x c_z)) + a_z (b_x c_y - b_y c_x),
+ *   positive for outward-facing faces; area[t] = sum_f 0.5 |(b - a) x (c - a)|; both in fp64 from the fp32 inputs.
+ *
+ * lasr_meshcheck_faces: one thread per (frame, face) writes the face's record into the workspace (nine coordinates, the box, the
+ *   three indices; structure of arrays, slot k of face f of frame t at ((t 18 + k) F + f)) and its fp64 volume and area terms; the
+ *   terms are folded per block of 256 faces (shuffles, then the four waves in order) and a second launch adds the block partials in
+ *   index order: volume [T], area [T] fp64.  No floating-point atomics.
+ * lasr_meshcheck_pairs: reads the records lasr_meshcheck_faces left in the same workspace.  The grid runs over (frame, tile I,
+ *   tile J >= I) with tiles of LASR_MESHCHECK_TILE faces; both tiles are staged in LDS, every thread keeps the box and the indices
+ *   of one face of tile I and walks tile J (the faces after its own in the diagonal tile); the candidates are compacted per wave
+ *   into a queue in LDS and tested 64 at a time.  Zeroes, then fills:
+ *     face_count [T,F] int32    the number of faces each face intersects
+ *     n_pairs    [T]   uint64   the number of intersecting pairs
+ *     cursor     [T]   uint32   scratch: counts the pairs again, modulo 2^32
+ *     pairs      [T,max_pairs,2] int32   the pairs (i, j), i < j, of a frame in no defined order, filled while cursor < max_pairs:
+ *                               complete iff n_pairs[t] <= max_pairs, else to be discarded (the counts stay exact); max_pairs = 0: may
+ *                               be NULL
+ *   Integer atomics only: the counts, and the list once sorted, are the same bits on every run.
+ * Precondition: every face index lies in [0, V) (the Python layer checks it on the device before it launches).  As a defence a face
+ *   that breaks it is not gathered: it gets an empty box and terms of 0, and takes part in nothing.
+ * Checked on the host before any launch (LASR_E_BADARG): 0 <= T <= LASR_MESHCHECK_MAX_FRAMES, V >= 0, 3 V <= INT_MAX,
+ *   0 <= F <= LASR_MESHCHECK_MAX_FACES (2^20: the tile-pair grid of a frame is then 2^23 + 2^11 blocks), T F <= INT_MAX,
+ *   max_pairs >= 0, 2 T max_pairs <= INT_MAX; then T == 0 or F == 0 is LASR_OK with nothing launched; then V >= 1, every pointer
+ *   non-NULL (pairs only when max_pairs > 0), no two outputs the same buffer and none of them the workspace or an input;
+ *   LASR_E_WORKSPACE when workspace_bytes < lasr_meshcheck_workspace_bytes(T, F), which is 0 for sizes outside these limits.
+ *   Device contents are not read on the host.  Neither kernel is in the lasr_prof_* table.
+ */
+#define LASR_MESHCHECK_TILE 256
+#define LASR_MESHCHECK_MAX_FACES 1048576
+#define LASR_MESHCHECK_MAX_FRAMES 65535
+size_t lasr_meshcheck_workspace_bytes(int T, int F);
+int lasr_meshcheck_faces(const float* verts, const int* faces, void* workspace, size_t workspace_bytes, double* volume, double* area,
+                         int T, int V, int F, void* hip_stream);
+int lasr_meshcheck_pairs(const void* workspace, size_t workspace_bytes, int* face_count, unsigned long long* n_pairs, unsigned* cursor,
+                         int* pairs, int T, int F, int max_pairs, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

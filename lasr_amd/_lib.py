@@ -150,6 +150,10 @@ SIGNATURES = {
     'lasr_motionseg_moments': (_i, [_p] * 5 + [_i] * 2 + [_p]),
     'lasr_motionseg_solve': (_i, [_p] * 3 + [_i] * 3 + [_f] * 3 + [_p]),
     'lasr_motionseg_evidence': (_i, [_p] * 4 + [_i] * 2 + [_f, _f, _i, _p]),
+    # lasr_amd/csrc/meshcheck.hip
+    'lasr_meshcheck_workspace_bytes': (_sz, [_i, _i]),
+    'lasr_meshcheck_faces': (_i, [_p, _p, _p, _sz, _p, _p] + [_i] * 3 + [_p]),
+    'lasr_meshcheck_pairs': (_i, [_p, _sz] + [_p] * 4 + [_i] * 3 + [_p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -215,6 +219,7 @@ TRACK_MAX_SNAP, TRACK_MAX_WINDOW, TRACK_MAX_RADIUS, TRACK_MAX_SIZE, TRACK_SPLAT_
 REPROJ_MAX_RADIUS = 96                              # LASR_REPROJ_MAX_RADIUS of include/lasr_ops.h
 VARFLOW_MIN_SIZE, VARFLOW_MAX_SIZE = 2, 16384       # LASR_VARFLOW_* of include/lasr_ops.h
 MOTIONSEG_MAX_SIZE, MOTIONSEG_BLOCKS, MOTIONSEG_MOMENTS, MOTIONSEG_BINS, MOTIONSEG_STATE = 16384, 256, 28, 1024, 12   # LASR_MOTIONSEG_*
+MESHCHECK_TILE, MESHCHECK_MAX_FACES, MESHCHECK_MAX_FRAMES = 256, 1 << 20, 65535   # LASR_MESHCHECK_* of include/lasr_ops.h
 
 
 class SrOptions(ctypes.Structure):
