@@ -1316,6 +1316,52 @@ int lasr_meshcheck_faces(const float* verts, const int* faces, void* workspace, 
 int lasr_meshcheck_pairs(const void* workspace, size_t workspace_bytes, int* face_count, unsigned long long* n_pairs, unsigned* cursor,
                          int* pairs, int T, int F, int max_pairs, void* hip_stream);
 
+/*
+ * ---- Structural similarity as the texture term of optimize.py --ptex_method ssim (lasr_amd/csrc/ssim.hip,
+ *      lasr_amd/nnutils/fused_ops.py: ssim_distance) ----
+ * This project's own addition: the reference has no counterpart (its texture term is an AlexNet feature distance that needs
+ * downloaded weights), nothing of it is restated here, and parity is to the restatement in tests/ssim_restated.py and to closed
+ * forms only.  SSIM of Wang et al. 2004 with the 11 x 11 Gaussian window of sigma 1.5 over the valid region, as a distance per image.
+ * a [M,3,H,W] fp32 (the observed images, no gradient), b [N,3,H,W] fp32 with N = M rep; image i of b is compared with image
+ * i / rep of a.  L is the data range (1 for images in [0, 1], 2 for [-1, 1]).
+ *
+ * Definition, in fp32 without contraction and with IEEE division.  g[k] = exp(-(k - 5)^2 / (2 1.5^2)), k = 0 .. 10, normalised to
+ *   sum 1 in fp64 and rounded once to fp32.  Ho = H - 10, Wo = W - 10.  The five planes a, b, a a, b b, a b (products first) are
+ *   blurred horizontally, then vertically; each pass is acc = 0; for k ascending: acc = acc + g[k] p[. + k].  With the results
+ *   mu_a, mu_b, E_aa, E_bb, E_ab: s_aa = E_aa - mu_a mu_a, s_bb and s_ab likewise; C1 = (0.01 L)^2, C2 = (0.03 L)^2;
+ *   A1 = 2 mu_a mu_b + C1, A2 = 2 s_ab + C2, B1 = (mu_a mu_a + mu_b mu_b) + C1, B2 = (s_aa + s_bb) + C2, den = B1 B2,
+ *   s = (A1 A2) / den.  d[i] = 1 - (sum of s over the 3 channels and the Ho Wo pixels) / (3 Ho Wo).
+ *   The sum: a block owns a LASR_SSIM_TILE_W x LASR_SSIM_TILE_H tile of one (image, channel); thread t (of 256) adds s at row t / 32
+ *   and at row t / 32 + 8 of column t % 32 (0 outside the map); the 64 lanes of a wave are folded by lane l += lane l + o for
+ *   o = 32, 16, ..., 1, the four waves as ((w0 + w1) + w2) + w3, all in fp32; a second launch adds the block sums of an image in
+ *   fp64 in the order channel, tile row, tile column, forms 1 - sum / (3 Ho Wo) in fp64 and rounds it to fp32.
+ *   The derivatives of s, with u = (2 mu_b) s:  P1 = ((2 mu_a) (A2 - A1)) / den - (u / B1 - u / B2)  (by mu_b, the mu terms of the
+ *   variances included), P2 = -(s / B2) (by E_bb), P3 = (2 A1) / den (by E_ab).  The gradient pushes them through the transposed
+ *   window over the planes padded with zeros: U_j(py, qx) = acc over k ascending of g[10 - k] P_j(py, qx - 10 + k), T_j(qy, qx) =
+ *   acc over k ascending of g[10 - k] U_j(qy - 10 + k, qx), v = T_1 + (2 b(q)) T_2, v = v + a(q) T_3,
+ *   grad_b(q) = fp32(-fp64(grad_d[i]) / (3 Ho Wo)) v.
+ *
+ * lasr_ssim_forward: d [N]; scratch: lasr_ssim_scratch_floats(M, rep, H, W) floats (the block sums).  partials NULL: nothing more.
+ *   partials [N,3,3,Ho,Wo] (image, channel, plane P1 P2 P3): the three derivative planes are written for lasr_ssim_backward.
+ *   Two launches (tiles, fold).
+ * lasr_ssim_backward: grad_b [N,3,H,W] is overwritten.  partials as the forward wrote them, or NULL: the planes are recomputed
+ *   from a and b in the same order, so both forms give the same bits.  One launch.
+ * No floating-point atomics: the same input gives the same bits on every run.  Both are launch-only (capturable into a graph).
+ * Checked on the host before any launch (LASR_E_BADARG): M >= 1, rep >= 1, 3 M rep <= 65535 (the grid's z extent),
+ *   LASR_SSIM_MIN_SIZE <= H, W <= LASR_SSIM_MAX_SIZE, L finite and > 0; then every pointer but partials non-NULL and no output the
+ *   same buffer as an input or another output.  lasr_ssim_scratch_floats is 0 for sizes outside these limits.  Device contents are
+ *   not read on the host.  These launches are not in the lasr_prof_* kernel table.
+ */
+#define LASR_SSIM_MIN_SIZE 11
+#define LASR_SSIM_MAX_SIZE 4096
+#define LASR_SSIM_TILE_W 32
+#define LASR_SSIM_TILE_H 16
+size_t lasr_ssim_scratch_floats(int M, int rep, int H, int W);
+int lasr_ssim_forward(const float* a, const float* b, float* d, float* partials, float* scratch, int M, int rep, int H, int W, float L,
+                      void* hip_stream);
+int lasr_ssim_backward(const float* a, const float* b, const float* partials, const float* grad_d, float* grad_b, int M, int rep,
+                       int H, int W, float L, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

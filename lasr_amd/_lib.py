@@ -154,6 +154,10 @@ SIGNATURES = {
     'lasr_meshcheck_workspace_bytes': (_sz, [_i, _i]),
     'lasr_meshcheck_faces': (_i, [_p, _p, _p, _sz, _p, _p] + [_i] * 3 + [_p]),
     'lasr_meshcheck_pairs': (_i, [_p, _sz] + [_p] * 4 + [_i] * 3 + [_p]),
+    # lasr_amd/csrc/ssim.hip
+    'lasr_ssim_scratch_floats': (_sz, [_i] * 4),
+    'lasr_ssim_forward': (_i, [_p] * 5 + [_i] * 4 + [_f, _p]),
+    'lasr_ssim_backward': (_i, [_p] * 5 + [_i] * 4 + [_f, _p]),
     # lasr_amd/csrc/glue.hip
     'lasr_geodesic_forward': (_i, [_p, _p, _p, _i, _p]),
     'lasr_geodesic_backward': (_i, [_p, _p, _p, _p, _p, _i, _p]),
@@ -220,6 +224,7 @@ REPROJ_MAX_RADIUS = 96                              # LASR_REPROJ_MAX_RADIUS of 
 VARFLOW_MIN_SIZE, VARFLOW_MAX_SIZE = 2, 16384       # LASR_VARFLOW_* of include/lasr_ops.h
 MOTIONSEG_MAX_SIZE, MOTIONSEG_BLOCKS, MOTIONSEG_MOMENTS, MOTIONSEG_BINS, MOTIONSEG_STATE = 16384, 256, 28, 1024, 12   # LASR_MOTIONSEG_*
 MESHCHECK_TILE, MESHCHECK_MAX_FACES, MESHCHECK_MAX_FRAMES = 256, 1 << 20, 65535   # LASR_MESHCHECK_* of include/lasr_ops.h
+SSIM_MIN_SIZE, SSIM_MAX_SIZE, SSIM_TILE_W, SSIM_TILE_H = 11, 4096, 32, 16         # LASR_SSIM_* of include/lasr_ops.h
 
 
 class SrOptions(ctypes.Structure):

@@ -564,6 +564,93 @@ def cosine_distance_layers(feats_obs, feats_rnd, repeat=1):
     return _CosDistMulti.apply(int(repeat), *feats_obs, *feats_rnd)
 
 
+# ---- structural similarity as a texture term (lasr_amd/csrc/ssim.hip; this project's own addition) ------
+# The backward reads the three derivative planes the forward saved (True) or recomputes the moments from a and b (False); both
+# give the same bits.  Saved by measurement (tools/ssim_bench.py): at spot3 stage 0 the forward costs the
+# same either way and the backward 75 us instead of 255 us, for 70 MB held between the two passes.
+SSIM_SAVE_PLANES = True
+
+
+def _ssim_check(obs, rnd, repeat):
+    if obs.dim() != 4 or rnd.dim() != 4 or obs.shape[1] != 3 or rnd.shape[1] != 3:
+        raise ValueError('ssim_distance: obs [M,3,H,W] and rnd [N,3,H,W], got %s and %s' % (tuple(obs.shape), tuple(rnd.shape)))
+    if repeat < 1 or obs.shape[0] < 1 or obs.shape[0] * repeat != rnd.shape[0]:
+        raise ValueError('ssim_distance: N = %d is not M = %d times repeat = %d' % (rnd.shape[0], obs.shape[0], repeat))
+    if 3 * rnd.shape[0] > 65535:
+        raise ValueError('ssim_distance: %d images, at most 21845 per call (the grid of lasr_ssim_forward)' % rnd.shape[0])
+    H, W = rnd.shape[2:]
+    if obs.shape[2:] != rnd.shape[2:] or not (_lib.SSIM_MIN_SIZE <= min(H, W) and max(H, W) <= _lib.SSIM_MAX_SIZE):
+        raise ValueError('ssim_distance: images of %s and %s; both sides the same, %d .. %d'
+                         % (tuple(obs.shape[2:]), tuple(rnd.shape[2:]), _lib.SSIM_MIN_SIZE, _lib.SSIM_MAX_SIZE))
+
+
+class _Ssim(Function):
+    @staticmethod
+    def forward(ctx, a, b, rep, L, save_planes):
+        _lib.need_cuda(a, b)
+        a, b = _lib.f32(a.detach(), b)
+        M, (N, _, H, W) = a.shape[0], b.shape
+        d = torch.empty(N, dtype=torch.float32, device=b.device)
+        scratch = torch.empty(_lib.lib().lasr_ssim_scratch_floats(M, rep, H, W), dtype=torch.float32, device=b.device)
+        planes = torch.empty(N, 3, 3, H - 10, W - 10, dtype=torch.float32, device=b.device) if save_planes else None
+        _lib.call('lasr_ssim_forward', a, b, d, planes, scratch, M, rep, H, W, L)
+        ctx.save_for_backward(a, b, planes)
+        ctx.rep, ctx.L = rep, L
+        return d
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, planes = ctx.saved_tensors
+        M, (_, _, H, W) = a.shape[0], b.shape
+        g = _lib.f32(g)
+        gb = torch.empty_like(b)
+        _lib.call('lasr_ssim_backward', a, b, planes, g, gb, M, ctx.rep, H, W, ctx.L)
+        return None, gb, None, None, None
+
+
+def ssim_distance(obs, rnd, repeat=1, data_range=1.0, save_planes=None):
+    """1 - mean over channels and pixels of the structural similarity (Wang et al. 2004: 11 x 11 Gaussian window of sigma 1.5, valid
+    region only) between obs[i // repeat] and rnd[i]: obs [N/repeat,3,H,W] (no gradient), rnd [N,3,H,W] -> [N].  data_range: 1 for
+    images in [0, 1], 2 for [-1, 1].  This project's own addition (the reference has no counterpart); the definition is
+    tests/ssim_restated.py.  Launches only (two forward, one backward): no host synchronisation, capturable into a HIP graph.
+    save_planes: None = SSIM_SAVE_PLANES."""
+    _lib.need_cuda(obs, rnd)
+    repeat, data_range = int(repeat), float(data_range)
+    _ssim_check(obs, rnd, repeat)
+    if not (0. < data_range < float('inf')):
+        raise ValueError('ssim_distance: data_range %r is not a positive finite number' % data_range)
+    need_planes = rnd.requires_grad and torch.is_grad_enabled() and (SSIM_SAVE_PLANES if save_planes is None else bool(save_planes))
+    return _Ssim.apply(obs, rnd, repeat, data_range, need_planes)
+
+
+def _ssim_window(dtype, device):
+    k = torch.arange(11, dtype=torch.float64)
+    g = torch.exp(-(k - 5.) ** 2 / (2. * 1.5 ** 2))
+    return (g / g.sum()).to(device=device, dtype=dtype)
+
+
+def ssim_distance_torch(obs, rnd, repeat=1, data_range=1.0):
+    """ssim_distance composed from torch operators (the five planes through two grouped conv2d, one per direction): any device and
+    floating dtype, differentiable in both arguments.  Used for CPU tensors and when obs requires a gradient; the comparator of
+    tools/ssim_bench.py.  Same definition, torch's own summation order."""
+    import torch.nn.functional as F
+    repeat, data_range = int(repeat), float(data_range)
+    _ssim_check(obs, rnd, repeat)
+    if not (0. < data_range < float('inf')):
+        raise ValueError('ssim_distance: data_range %r is not a positive finite number' % data_range)
+    a = obs.to(rnd.dtype).repeat_interleave(repeat, 0) if repeat > 1 else obs.to(rnd.dtype)
+    b = rnd
+    g = _ssim_window(b.dtype, b.device)
+    x = torch.cat([a, b, a * a, b * b, a * b], 1)                                  # [N,15,H,W]
+    x = F.conv2d(x, g.view(1, 1, 1, 11).expand(15, 1, 1, 11), groups=15)
+    x = F.conv2d(x, g.view(1, 1, 11, 1).expand(15, 1, 11, 1), groups=15)
+    mua, mub, eaa, ebb, eab = x.split(3, 1)
+    C1, C2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    saa, sbb, sab = eaa - mua * mua, ebb - mub * mub, eab - mua * mub
+    s = ((2 * mua * mub + C1) * (2 * sab + C2)) / ((mua * mua + mub * mub + C1) * (saa + sbb + C2))
+    return 1. - s.mean((1, 2, 3))
+
+
 # ---- small-tensor glue of LASR.forward (lasr_amd/csrc/glue.hip): one launch where the reference runs a chain of tiny ops --------
 class _Geodesic(Function):
     @staticmethod

@@ -386,6 +386,38 @@ class PerceptualDistance(nn.Module):
         return d
 
 
+class StructuralDistance(nn.Module):
+    """optimize.py --ptex_method ssim: the texture term without a network, hence without weights to download.  This project's own
+    addition (the reference has no counterpart): 1 - SSIM (Wang et al. 2004: 11 x 11 Gaussian window of sigma 1.5, valid region
+    only), averaged over `scales` levels of an average-pooled pyramid -- a plain mean, not MS-SSIM's exponent-weighted product.
+    No parameters and no buffers: a checkpoint is the same with and without it.  use_kernel False: the torch composition on every
+    device (the tests compare the two)."""
+
+    def __init__(self, scales=3, use_kernel=True):
+        super().__init__()
+        if int(scales) < 1:
+            raise ValueError('StructuralDistance: scales = %r, at least 1' % (scales,))
+        self.scales, self.use_kernel = int(scales), bool(use_kernel)
+
+    def forward_pair(self, a, b, repeat=1, unit_range=False):
+        """Distance between a[i // repeat] and b[i] -> [N], the signature and output of PerceptualDistance.forward_pair.
+        unit_range: the images are in [0, 1] (data range 1), else in [-1, 1] (data range 2)."""
+        L = 1. if unit_range else 2.
+        total = None
+        for j in range(self.scales):
+            if min(b.shape[-2:]) < 11 or min(a.shape[-2:]) < 11:
+                raise ValueError('StructuralDistance: scale %d of %d is %d x %d, below the 11 x 11 window (fewer --ssim_scales or a '
+                                 'larger --img_size)' % (j, self.scales, b.shape[-2], b.shape[-1]))
+            if self.use_kernel and b.is_cuda and not a.requires_grad:
+                d = fused_ops.ssim_distance(a, b, repeat, L)
+            else:
+                d = fused_ops.ssim_distance_torch(a, b, repeat, L)
+            total = d if total is None else total + d
+            if j + 1 < self.scales:
+                a, b = F.avg_pool2d(a, 2), F.avg_pool2d(b, 2)
+        return total / float(self.scales)
+
+
 def normalize_tensor(x, eps=1e-10):
     """PerceptualSimilarity/util/util.py:71-74."""
     return x / (x.pow(2).sum(1, keepdim=True).sqrt() + eps)
@@ -759,7 +791,9 @@ class LASR(MeshNet):
             # hypotheses: its features are computed once per image
             # (the [0,1] -> [-1,1] map of :436-441 is folded into the network's input normalisation: unit_range)
             percept = self.ptex_loss.forward_pair(obspair, rt[7], repeat=H, unit_range=True)
-            tmp = torch.add(tmp, percept.view(2, -1).sum(0).view(n2, H), alpha=0.005)
+            # --ptex_method ssim: ssim_wt (0.125; the two distances sum to 0.25 of the L1 term) in place of AlexNet's 0.005
+            ptex_wt = float(getattr(opts, 'ssim_wt', 0.125)) if isinstance(self.ptex_loss, StructuralDistance) else 0.005
+            tmp = torch.add(tmp, percept.view(2, -1).sum(0).view(n2, H), alpha=ptex_wt)
         self.texture_loss_sub = 0.25 * tmp
         terms.append((self.texture_loss_sub, 1., G_TEX))
 

@@ -102,14 +102,32 @@ class LASRTrainer:
         m.triangle_loss_fn_sr = loss_utils.LaplacianLoss(mean_v[0].cpu(), faces[0].cpu()).to(self.device)
         m.arap_loss_fn = loss_utils.ARAPLoss(mean_v[0].cpu(), faces[0].cpu()).to(self.device)
         m.flatten_loss = loss_utils.FlattenLoss(faces[0].cpu()).to(self.device)
-        m.ptex_loss = mesh_net.PerceptualDistance().to(self.device) if self.opts.perceptual else None
-        if m.ptex_loss is not None:
+        # --ptex_method: which texture term beside L1.  'alexnet' (default): the reference's feature distance; 'ssim': structural
+        # similarity, this project's own addition, which needs no weights (mesh_net.StructuralDistance).  Refused here, when the
+        # trainer is built, also under --noperceptual: a mistyped method must not pass because the term happens to be off.
+        method = getattr(self.opts, 'ptex_method', 'alexnet')
+        if method not in ('alexnet', 'ssim'):
+            raise ValueError("--ptex_method %r: 'alexnet' or 'ssim'" % (method,))
+        if method == 'ssim' and getattr(self.opts, 'alexnet_weights', ''):
+            raise ValueError('--alexnet_weights %s with --ptex_method ssim: the structural term has no network, the weights would '
+                             'be ignored; drop one of the two flags' % self.opts.alexnet_weights)
+        if not self.opts.perceptual:
+            m.ptex_loss = None
+        elif method == 'ssim':
+            m.ptex_loss = mesh_net.StructuralDistance(scales=getattr(self.opts, 'ssim_scales', 3)).to(self.device)
+            size = self.opts.img_size >> (m.ptex_loss.scales - 1)
+            if size < 11:
+                raise ValueError('--ssim_scales %d at --img_size %d: the coarsest scale is %d x %d, below the 11 x 11 window'
+                                 % (m.ptex_loss.scales, self.opts.img_size, size, size))
+        else:
+            m.ptex_loss = mesh_net.PerceptualDistance().to(self.device)
             if getattr(self.opts, 'alexnet_weights', ''):
                 m.ptex_loss.load_weights(self.opts.alexnet_weights)
                 m.ptex_loss.to(self.device)
             elif self.rank == 0:
                 print('[lasr_amd] perceptual term: AlexNet features are RANDOM (frozen); the reference uses ImageNet weights -- '
-                      'pass --alexnet_weights <local alexnet state_dict> or --noperceptual', file=sys.stderr)
+                      'pass --alexnet_weights <local alexnet state_dict>, --ptex_method ssim (a structural-similarity term that '
+                      'needs no weights) or --noperceptual', file=sys.stderr)
 
     # ---- data -------------------------------------------------------------------------------
     def init_dataset(self):

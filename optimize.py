@@ -46,7 +46,13 @@ DEFAULTS = dict(
     # monitor: once per epoch a 3 x 3 contact sheet of the reference's tensorboard images (monitor_dir/epoch-%04d.png), every step
     # the loss and gradient-norm scalars into monitor_dir/scalars.csv, all composed on the device (lasr_amd/nnutils/monitor.py);
     # monitor_dir '' = <checkpoint_dir>/<name>/monitor
-    monitor=False, monitor_dir='')
+    monitor=False, monitor_dir='',
+    # ptex_method: the texture term beside L1.  'alexnet' = the reference's AlexNet feature distance (weight 0.005; random features
+    # without --alexnet_weights); 'ssim' = 1 - structural similarity (Wang et al. 2004, 11 x 11 window, valid region), the mean over
+    # ssim_scales levels of an average-pooled pyramid, on the ssim.hip kernels: no weights needed.  ssim_wt 0.125 is derived, not
+    # measured: the term is the sum of two distances (the object on black and on white), so 2 x 0.125 = 0.25 of the L1 term's
+    # weight, the 0.8 : 0.2 ratio of L1 to D-SSIM of 3D Gaussian splatting.  --noperceptual switches either term off.
+    ptex_method='alexnet', ssim_wt=0.125, ssim_scales=3)
 
 
 def parse_flags(argv, defaults=DEFAULTS):

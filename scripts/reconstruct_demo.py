@@ -67,6 +67,9 @@ def main(argv=None):
     ap.add_argument('--obj', default='', help='render this .obj instead of the built-in blobby sphere (render_syn.py --obj)')
     ap.add_argument('--model', default='', help="render_syn.py --model (placement preset, e.g. 'spot')")
     ap.add_argument('--surface_tex', action='store_true', help='render_syn.py --surface_tex')
+    ap.add_argument('--ptex_method', default='alexnet', choices=['alexnet', 'ssim'],
+                    help='optimize.py --ptex_method for both stages: the AlexNet feature distance (default) or structural similarity')
+    ap.add_argument('--noperceptual', action='store_true', help='optimize.py --noperceptual for both stages: no texture term beside L1')
     args = ap.parse_args(argv)
     root = tempfile.mkdtemp(prefix='lasr_demo_')
     name = 'syn-blob%df' % args.nframes
@@ -77,7 +80,8 @@ def main(argv=None):
     log = os.path.join(root, 'log')
     common = ['--checkpoint_dir', log, '--dataname', name, '--data_root', root, '--sil_path', 'none', '--ngpu', '1',
               '--batch_size', '1', '--opt_tex', 'yes', '--nouse_gtpose', '--subdivide', '3', '--img_size', str(args.img_size)] + \
-        (['--nouse_graph'] if args.no_graph else ['--use_graph']) + (['--deterministic'] if args.deterministic else [])
+        (['--nouse_graph'] if args.no_graph else ['--use_graph']) + (['--deterministic'] if args.deterministic else []) + \
+        ['--ptex_method', args.ptex_method] + (['--noperceptual'] if args.noperceptual else [])
     # scripts/spot3.sh:24-25
     tr0, steps0, dt0 = run_stage(['--name', 'demo-0', '--only_mean_sym', '--n_bones', '21', '--n_hypo', str(args.n_hypo),
                                   '--num_epochs', str(args.epochs0)] + common)
