@@ -6,9 +6,9 @@ them), the forward optical flow (end-point error of the rendered flow) and the f
 include/lasr_ops.h states the arithmetic of the three entry points (csrc/reproj.hip); the anchoring of a pixel on the surface is
 the code of lasr_track_anchor.
 
-Scenes are those of lasr_amd/nnutils/bake.py: camera space with OpenCV axes, pixel intrinsics fx fy px py of the H x W frame, the
-hard-mode raster of side IS = max(H, W).  Frames are walked CHUNK_FRAMES at a time: one raster, the pixel pass with its reduce
-launch and the two boundary launches per chunk.  The successor of a chunk's last frame is the first frame of the next chunk, and
+Scenes are the posed sequences of lasr_amd/nnutils/posed.py, which states the conventions and holds the raster of side IS =
+max(H, W).  Frames are walked CHUNK_FRAMES at a time (posed.py's default): one raster, the pixel pass with its reduce launch and
+the two boundary launches per chunk.  The successor of a chunk's last frame is the first frame of the next chunk, and
 every frame is scored on its own, so the result does not depend on the chunk size.
 """
 import math
@@ -17,9 +17,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import bake
+from . import posed
 
-CHUNK_FRAMES = bake.CHUNK_FRAMES
+CHUNK_FRAMES = posed.CHUNK_FRAMES
 COUNTS = ('inter', 'union', 'n_pred', 'n_gt', 'n_pb', 'n_gb', 'pm', 'gm', 'n_flow', 'n_le1', 'n_le3', 'n_rgb')
 DEFAULT_BOUND_TH = 0.008
 
@@ -80,29 +80,17 @@ def evaluate(verts, faces, K, masks, flows=None, occs=None, frames=None, colors=
     -> dict of per-frame numpy arrays: the twelve COUNTS (int64), J, precision, recall, F, epe, pck1, pck3, psnr (float64; NaN
     where a denominator is 0, so epe of the last frame is NaN) and radius; and on the device 'counts' int64 [T,12], 'sums'
     float64 [T,2], 'bits' and 'boundary_bits' int64 [T,2,H,WW] (maps pred, gt; unpack_bits reads them)."""
-    named = (('verts', verts), ('faces', faces), ('K', K), ('masks', masks), ('flows', flows), ('occs', occs), ('frames', frames),
-             ('colors', colors), ('raster', raster))
+    named = (('masks', masks), ('flows', flows), ('occs', occs), ('frames', frames), ('colors', colors), ('raster', raster))
     for name, t in named:
         if t is not None and not torch.is_tensor(t):
             raise TypeError('reproj.evaluate: %s must be a tensor' % name)
     _lib.need_cuda(*(t for _, t in named))
-    dev = verts.device
-    if verts.ndimension() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
-        raise ValueError('reproj.evaluate: verts must be [T, V >= 1, 3], got %s' % (tuple(verts.shape),))
-    T, V = verts.shape[:2]
-    if faces.ndimension() != 2 or faces.shape[1] != 3 or faces.is_floating_point():
-        raise ValueError('reproj.evaluate: faces must be integer [F, 3], got %s %s' % (faces.dtype, tuple(faces.shape)))
-    F = faces.shape[0]
-    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
-        raise ValueError('reproj.evaluate: faces must index the %d vertices' % V)
-    if K.numel() != T * 4:
-        raise ValueError('reproj.evaluate: K must be [T = %d, 4] (fx fy px py), got %s' % (T, tuple(K.shape)))
+    H, W = masks.shape[1:3] if masks.ndimension() == 3 else (1, 1)        # masks of another rank are refused below, by name
+    seq = posed.sequence('reproj.evaluate', verts, faces, K, H, W, _lib.TRACK_MAX_SIZE)
+    dev, verts, faces32, K = seq.device, seq.verts, seq.faces32, seq.K
+    T, V, F, IS, H, W = seq.T, seq.V, seq.F, seq.IS, seq.H, seq.W
     if masks.ndimension() != 3 or masks.shape[0] != T:
         raise ValueError('reproj.evaluate: masks must be [T = %d, H, W], got %s' % (T, tuple(masks.shape)))
-    H, W = int(masks.shape[1]), int(masks.shape[2])
-    IS = max(H, W)
-    if not (1 <= H and 1 <= W and IS <= _lib.TRACK_MAX_SIZE):
-        raise ValueError('reproj.evaluate: frames of %d x %d: each side must be 1..%d' % (H, W, _lib.TRACK_MAX_SIZE))
     radius = radius_of(bound_th, H, W)
     if occs is not None and flows is None:
         raise ValueError('reproj.evaluate: occs comes with flows')
@@ -121,9 +109,6 @@ def evaluate(verts, faces, K, masks, flows=None, occs=None, frames=None, colors=
     if raster is not None and (tuple(raster.shape) != (T, 2, IS, IS) or raster.dtype != torch.float32):
         raise ValueError('reproj.evaluate: raster must be float32 [%d, 2, %d, %d], got %s %s' % (T, IS, IS, raster.dtype, tuple(raster.shape)))
 
-    verts = verts.detach().float().contiguous()
-    faces32 = faces.to(torch.int32).contiguous()
-    K = K.detach().float().reshape(T, 4).contiguous()
     gt = (masks != 0).to(torch.uint8).contiguous()
     if flows is not None:
         flows = flows.detach().float().contiguous()
@@ -135,11 +120,10 @@ def evaluate(verts, faces, K, masks, flows=None, occs=None, frames=None, colors=
     sums = torch.zeros(T, 2, dtype=torch.float64, device=dev)
     bits = torch.zeros(T, 2, H, WW, dtype=torch.int64, device=dev)
     bbits = torch.zeros(T, 2, H, WW, dtype=torch.int64, device=dev)
-    for i in range(0, T, CHUNK_FRAMES):
-        j = min(i + CHUNK_FRAMES, T)
+    for i, j, v, k, r in seq.chunks(CHUNK_FRAMES, raster=raster is None):
         n = j - i
-        v, k = verts[i:j], K[i:j]
-        r = raster[i:j].contiguous() if raster is not None else bake.face_index_raster(v, faces32, k, IS)
+        if raster is not None:
+            r = raster[i:j].contiguous()
         vn = kn = fl = oc = None
         if flows is not None:
             if j < T:                                                 # the successor of the chunk's last frame opens the next chunk

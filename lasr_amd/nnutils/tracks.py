@@ -4,18 +4,18 @@ This is the project's own addition: the reference only transfers annotated keypo
 (frame position, row, column) is anchored on the surface of frame t's mesh (face + barycentrics, lasr_track_anchor) and carried
 through every frame with a visibility decision (lasr_track_project, csrc/tracks.hip); include/lasr_ops.h states the arithmetic.
 
-Scenes are those of lasr_amd/nnutils/bake.py: camera space with OpenCV axes, pixel intrinsics fx fy px py of the H x W frame, the
-hard-mode raster of side IS = max(H, W).  Frames are walked CHUNK_FRAMES at a time, twice: the anchoring walk rasterises only the
-chunks that hold a query frame (one chunk for the default query set), the projection walk every chunk.  The rasters are NOT kept
+Scenes are the posed sequences of lasr_amd/nnutils/posed.py, which states the conventions and holds the raster of side IS =
+max(H, W).  Frames are walked CHUNK_FRAMES at a time (posed.py's default), twice: the anchoring walk rasterises only the chunks
+that hold a query frame (one chunk for the default query set), the projection walk every chunk.  The rasters are NOT kept
 between the two walks: a raster is 8 IS^2 bytes a frame (2.6 GB for 90 frames at 1080p), and keeping them would save the one
 raster launch of the query chunk.
 """
 import torch
 
 from .. import _lib
-from . import bake
+from . import posed
 
-CHUNK_FRAMES = bake.CHUNK_FRAMES
+CHUNK_FRAMES = posed.CHUNK_FRAMES
 STATE_NONE, STATE_VISIBLE, STATE_HIDDEN, STATE_OUTSIDE, STATE_BEHIND = 0, 1, 2, 3, 4
 
 
@@ -42,9 +42,8 @@ def frame_raster(verts, faces, K, t, H, W):
     T = verts.shape[0]
     if not 0 <= int(t) < T:
         raise ValueError('frame_raster: frame position %d is outside the %d frames' % (int(t), T))
-    v = verts[int(t):int(t) + 1].detach().float().contiguous()
-    k = K.detach().float().reshape(T, 4)[int(t):int(t) + 1].contiguous()
-    return bake.face_index_raster(v, faces.to(torch.int32).contiguous(), k, max(int(H), int(W)))[0]
+    one = posed.Posed(verts[int(t):int(t) + 1], faces, K.reshape(T, 4)[int(t):int(t) + 1], H, W)
+    return posed.face_index_raster(one.verts, one.faces32, one.K, one.IS)[0]
 
 
 def track_points(verts, faces, K, queries, H, W, snap_radius=0, window=1):
@@ -54,28 +53,15 @@ def track_points(verts, faces, K, queries, H, W, snap_radius=0, window=1):
     2 hidden, 3 outside the frame, 4 behind the camera (track NaN), 0 no anchor (track NaN).  anchors is a dict: 'face' [Q] int32
     (-1: none), 'bary' [Q,3] float32 (c0, c1, c2), 'facing' [Q] float32 and 'snapped' [Q,2] float32 (v, u), the position the
     anchor was computed at (moved to a covered pixel's centre when snap_radius > 0 found one for a query on an empty pixel)."""
-    for name, t in (('verts', verts), ('faces', faces), ('K', K), ('queries', queries)):
-        if not torch.is_tensor(t):
-            raise TypeError('track_points: %s must be a tensor' % name)
-    _lib.need_cuda(verts, faces, K, queries)
-    dev = verts.device
-    H, W, snap_radius, window = int(H), int(W), int(snap_radius), int(window)
-    if verts.ndimension() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
-        raise ValueError('track_points: verts must be [T, V >= 1, 3], got %s' % (tuple(verts.shape),))
-    T, V = verts.shape[:2]
-    if faces.ndimension() != 2 or faces.shape[1] != 3 or faces.is_floating_point():
-        raise ValueError('track_points: faces must be integer [F, 3], got %s %s' % (faces.dtype, tuple(faces.shape)))
-    F = faces.shape[0]
-    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
-        raise ValueError('track_points: faces must index the %d vertices' % V)
-    if K.numel() != T * 4:
-        raise ValueError('track_points: K must be [T = %d, 4] (fx fy px py), got %s' % (T, tuple(K.shape)))
+    if not torch.is_tensor(queries):
+        raise TypeError('track_points: queries must be a tensor')
+    _lib.need_cuda(queries)
+    snap_radius, window = int(snap_radius), int(window)
+    seq = posed.sequence('track_points', verts, faces, K, H, W, _lib.TRACK_MAX_SIZE)
+    dev, faces32, T, V, F, IS, H, W = seq.device, seq.faces32, seq.T, seq.V, seq.F, seq.IS, seq.H, seq.W
     if queries.ndimension() != 2 or queries.shape[1] != 3 or not queries.is_floating_point():
         raise ValueError('track_points: queries must be floating point [Q, 3] (t, v, u), got %s %s' % (queries.dtype, tuple(queries.shape)))
     Q = queries.shape[0]
-    IS = max(H, W)
-    if not (1 <= H and 1 <= W and IS <= _lib.TRACK_MAX_SIZE):
-        raise ValueError('track_points: frames of %d x %d: each side must be 1..%d' % (H, W, _lib.TRACK_MAX_SIZE))
     if not 0 <= snap_radius <= _lib.TRACK_MAX_SNAP:
         raise ValueError('track_points: snap_radius must be 0..%d, got %d' % (_lib.TRACK_MAX_SNAP, snap_radius))
     if not 0 <= window <= _lib.TRACK_MAX_WINDOW:
@@ -86,27 +72,16 @@ def track_points(verts, faces, K, queries, H, W, snap_radius=0, window=1):
         if not bool(((qt == qt.round()) & (qt >= 0) & (qt < T)).all()):
             raise ValueError('track_points: the frame position of every query must be a whole number in 0..%d' % (T - 1))
 
-    verts = verts.detach().float().contiguous()
-    faces32 = faces.to(torch.int32).contiguous()
-    K = K.detach().float().reshape(T, 4).contiguous()
     rec = torch.zeros(Q, 4, dtype=torch.float32, device=dev)
     rec.view(torch.int32)[:, 0] = -1                                 # no anchor until the anchoring walk writes one
     snapped = queries[:, 1:3].clone()
     frame_major = torch.empty(T, Q, 2, dtype=torch.float32, device=dev)
     state_major = torch.empty(T, Q, dtype=torch.uint8, device=dev)
     if Q and T:
-        chunks = set((queries[:, 0].long() // CHUNK_FRAMES).unique().tolist())
-        for i in range(0, T, CHUNK_FRAMES):                          # anchoring walk
-            if i // CHUNK_FRAMES not in chunks:
-                continue
-            j = min(i + CHUNK_FRAMES, T)
-            v, k = verts[i:j], K[i:j]
-            raster = bake.face_index_raster(v, faces32, k, IS)
+        held = set((queries[:, 0].long() // CHUNK_FRAMES).unique().tolist())
+        for i, j, v, k, raster in seq.chunks(CHUNK_FRAMES, only=held):          # anchoring walk
             _lib.call('lasr_track_anchor', v, faces32, k, raster, queries, rec, snapped, i, j - i, Q, V, F, IS, H, W, snap_radius)
-        for i in range(0, T, CHUNK_FRAMES):                          # projection walk
-            j = min(i + CHUNK_FRAMES, T)
-            v, k = verts[i:j], K[i:j]
-            raster = bake.face_index_raster(v, faces32, k, IS)
+        for i, j, v, k, raster in seq.chunks(CHUNK_FRAMES):                     # projection walk
             _lib.call('lasr_track_project', v, faces32, k, raster, rec, frame_major[i:j], state_major[i:j], j - i, Q, V, F, IS, H, W,
                       window)
     c1, c2 = rec[:, 1], rec[:, 2]

@@ -11,7 +11,6 @@ is used, and the turntable's [R | T] replaces the identity pose.  Rendering: las
 rasteriser); DESIGN.md section 4.4.
 """
 import argparse
-import glob
 import os
 import sys
 
@@ -20,6 +19,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+from lasr_amd.recon_io import frame_id, frame_list, load_mesh   # noqa: E402,F401  (frame_list and load_mesh: imported from here too)
 
 
 def parse_args(argv=None):
@@ -39,30 +39,6 @@ def parse_args(argv=None):
                    help='draw the bone ellipsoids (gauss<i>.ply) under a translucent surface')
     p.add_argument('--freeze', dest='freeze', action='store_true', help='turn the first frame\'s mesh on a 150-frame turntable')
     return p.parse_args(argv)
-
-
-def frame_list(seqname):
-    """Frame paths of the sequence, as the video loader selects them (lasr_amd/dataloader/vid.py)."""
-    from lasr_amd.dataloader.vid import read_config
-    cfg = read_config(seqname)
-    names = sorted(glob.glob('%s/*' % cfg['datapath']))
-    if cfg['end_frame'] > 0:
-        names = names[:cfg['end_frame']]
-    return names[cfg['init_frame']:][::cfg['dframe']]
-
-
-def load_mesh(testdir, fr):
-    """pred<fr>.ply (with its colours) or pred<fr>.obj (grey 102) -> verts [V,3] float32, faces [F,3] long, colours uint8 [V,3]."""
-    from lasr_amd.ext_utils.ply import read_ply
-    ply = os.path.join(testdir, 'pred%d.ply' % fr)
-    if os.path.exists(ply):
-        m = read_ply(ply)
-        v, f = torch.from_numpy(m['verts']).float(), torch.from_numpy(m['faces'])
-        c = m['colors'] if m['colors'] is not None else np.full((len(v), 3), 102, np.uint8)
-        return v, f, torch.from_numpy(c.astype(np.uint8))
-    from lasr_amd.soft_renderer.functional import load_obj
-    v, f = load_obj(os.path.join(testdir, 'pred%d.obj' % fr))
-    return v.float().cpu(), f.long().cpu(), torch.full((v.shape[0], 3), 102, dtype=torch.uint8)
 
 
 def resize(img, size):
@@ -136,7 +112,7 @@ def main(argv=None):
         raise SystemExit('render_vis.py: no frames for sequence %s' % args.seqname)
     imgs, meshes, cams, bones = [], [], [], []
     for name in names:
-        fr = int(os.path.basename(name).split('.')[-2])
+        fr = frame_id(name)
         print('%s/%d' % (args.seqname, fr))
         imgs.append(np.asarray(Image.open(name).convert('RGB')))
         try:

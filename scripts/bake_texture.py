@@ -26,6 +26,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from lasr_amd import recon_io                                                          # noqa: E402
+from lasr_amd.recon_io import check_topology, annotation_path as silhouette_path      # noqa: E402,F401  (imported from here too)
 
 
 def parse_args(argv=None):
@@ -69,54 +71,25 @@ def load_rest_shape(path, face):
     return rest
 
 
-def check_topology(faces_list, frame_ids):
-    """Every pred<i> must share the faces of the first, as scripts/eval_badja.py:load_meshes requires."""
-    first = np.asarray(faces_list[0])
-    for fr, f in zip(frame_ids[1:], faces_list[1:]):
-        f = np.asarray(f)
-        if f.shape != first.shape or (f != first).any():
-            raise ValueError('pred%d does not share the topology of pred%d' % (fr, frame_ids[0]))
-    return first
-
-
-def silhouette_path(frame_path):
-    """.../JPEGImages/<res>/<seq>/00000.jpg -> .../Annotations/<res>/<seq>/00000.png (the layout of lasr_amd/dataloader/vid.py)."""
-    return frame_path.replace('JPEGImages', 'Annotations').replace('.jpg', '.png')
-
-
 def main(argv=None):
     args = parse_args(argv)
     from PIL import Image
-    import render_vis
     from lasr_amd.nnutils import bake
     from lasr_amd.soft_renderer.functional import save_obj
     dev = torch.device('cuda', 0)
-    names = render_vis.frame_list(args.seqname)
+    names = recon_io.frame_list(args.seqname)
     if not names:
         raise SystemExit('bake_texture.py: no frames for sequence %s' % args.seqname)
     if not 0 <= args.pose_frame < len(names):
         raise SystemExit('bake_texture.py: --pose_frame %d is outside the %d frames' % (args.pose_frame, len(names)))
     if args.texture_res < 2:
         raise SystemExit('bake_texture.py: --texture_res must be at least 2 (the atlas writer needs it)')
-    imgs, sils, verts, faces, colors, cams, ids = [], [], [], [], [], [], []
-    for name in names:
-        fr = int(os.path.basename(name).split('.')[-2])
-        imgs.append(np.asarray(Image.open(name).convert('RGB')))
-        try:
-            v, f, c = render_vis.load_mesh(args.testdir, fr)
-            cams.append(np.loadtxt(os.path.join(args.testdir, 'cam%d.txt' % fr)))
-        except (OSError, ValueError) as e:
-            raise SystemExit('bake_texture.py: no mesh for frame %d in %s (%s)' % (fr, args.testdir, e))
-        verts.append(v), faces.append(f.numpy()), colors.append(c), ids.append(fr)
-        if args.mask:
-            try:
-                sils.append(np.asarray(Image.open(silhouette_path(name)).convert('L')))
-            except OSError as e:
-                raise SystemExit('bake_texture.py: no silhouette for %s (%s); pass --no_mask to bake without' % (name, e))
     try:
-        face = check_topology(faces, ids)
-    except ValueError as e:
+        rec = recon_io.read(args.testdir, names, annotations='L' if args.mask else None,
+                            no_annotation='no silhouette for %(name)s (%(e)s); pass --no_mask to bake without')
+    except recon_io.ReadError as e:
         raise SystemExit('bake_texture.py: %s' % e)
+    imgs, face = rec.imgs, rec.face
     rest = None
     if args.fill != 'none':
         if args.symidx not in (0, 1, 2) or not 0 <= args.sym_tol < float('inf') or args.fill_iters < 0:
@@ -128,12 +101,12 @@ def main(argv=None):
             raise SystemExit('bake_texture.py: %s' % e)
     H, W = imgs[0].shape[:2]
     R = args.texture_res
-    tv = torch.stack(verts).to(dev)
+    tv = torch.from_numpy(np.stack(rec.verts)).to(dev)
     tf = torch.from_numpy(face).to(dev)
-    tK = torch.tensor(np.stack([c[3] for c in cams]), dtype=torch.float32, device=dev)
+    tK = torch.from_numpy(rec.K).to(dev)
     frames = torch.from_numpy(np.stack(imgs)).to(dev)
-    masks = torch.from_numpy(np.stack(sils)).to(dev) if args.mask else None
-    fallback = colors[args.pose_frame].to(dev).float() / 255.
+    masks = torch.from_numpy(np.stack(rec.masks)).to(dev) if args.mask else None
+    fallback = torch.from_numpy(rec.colors[args.pose_frame]).to(dev).float() / 255.
     with torch.no_grad():
         textures, weight = bake.bake_texture(tv, tf, tK, frames, masks, texture_res=R, power=args.power, fallback=fallback)
         source = None
@@ -144,7 +117,7 @@ def main(argv=None):
     out = args.outpath or os.path.join(args.testdir, 'baked')
     if os.path.dirname(out):
         os.makedirs(os.path.dirname(out), exist_ok=True)
-    save_obj(out + '.obj', verts[args.pose_frame], torch.from_numpy(face), textures, R, 'surface')
+    save_obj(out + '.obj', torch.from_numpy(rec.verts[args.pose_frame]), torch.from_numpy(face), textures, R, 'surface')
     w = weight.cpu().numpy()
     np.save(out + '_weight.npy', w)
     print('baked %d faces x %d texels, seen %.1f %%' % (face.shape[0], R * R, 100. * float((w > 0).mean())))

@@ -25,6 +25,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from lasr_amd import recon_io                                    # noqa: E402
+from lasr_amd.recon_io import annotation_path, check_topology    # noqa: E402,F401  (imported from here too)
 
 PER_FRAME = ('J', 'F', 'precision', 'recall', 'epe', 'pck1', 'pck3', 'psnr')
 COUNTS = ('inter', 'union', 'n_pred', 'n_gt', 'n_pb', 'n_gb', 'pm', 'gm', 'n_flow', 'n_le1', 'n_le3', 'n_rgb')
@@ -44,27 +46,12 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
-def annotation_path(name):
-    """The loader's substitution (lasr_amd/dataloader/vid.py)."""
-    return name.replace('JPEGImages', 'Annotations').replace('.jpg', '.png')
-
-
 def flow_paths(name, dframe):
     """(flo, occ) of the forward flow that starts at frame `name`, as the loader names them."""
     seqname = name.split('/')[-2]
     sub = '%s/flo-' % seqname if dframe == 1 else '%s_%02d/flo-' % (seqname, dframe)
     flo = name.replace('JPEGImages', 'FlowFW').replace('.jpg', '.pfm').replace('.png', '.pfm').replace('%s/' % seqname, sub)
     return flo, flo.replace('flo-', 'occ-')
-
-
-def check_topology(faces_list, frame_ids):
-    """Every pred<i> must share the faces of the first, as scripts/export_tracks.py requires."""
-    first = np.asarray(faces_list[0])
-    for fr, f in zip(frame_ids[1:], faces_list[1:]):
-        f = np.asarray(f)
-        if f.shape != first.shape or (f != first).any():
-            raise ValueError('pred%d does not share the topology of pred%d' % (fr, frame_ids[0]))
-    return first
 
 
 def check_size(what, shape, H, W):
@@ -151,34 +138,21 @@ def main(argv=None, evaluate=None):
     """evaluate: a stand-in for lasr_amd.nnutils.reproj.evaluate taking and returning numpy arrays (the tests without a device
     inject the float64 restatement); by default the tensors go to the GPU."""
     args = parse_args(argv)
-    from PIL import Image
-    import render_vis
     from lasr_amd.dataloader.vid import read_config
     try:
-        names = render_vis.frame_list(args.seqname)
+        names = recon_io.frame_list(args.seqname)
         dframe = read_config(args.seqname)['dframe']
     except FileNotFoundError as e:
         raise SystemExit('eval_reproj.py: no config for sequence %s (%s)' % (args.seqname, e))
     if not names:
         raise SystemExit('eval_reproj.py: no frames for sequence %s' % args.seqname)
-    imgs, masks, verts, faces, cols, cams, ids, has_colours = [], [], [], [], [], [], [], True
-    for name in names:
-        fr = int(os.path.basename(name).split('.')[-2])
-        imgs.append(np.asarray(Image.open(name).convert('RGB')))
-        try:
-            v, f, c = render_vis.load_mesh(args.testdir, fr)
-            cams.append(np.loadtxt(os.path.join(args.testdir, 'cam%d.txt' % fr)))
-        except (OSError, ValueError) as e:
-            raise SystemExit('eval_reproj.py: no mesh for frame %d in %s (%s)' % (fr, args.testdir, e))
-        has_colours &= os.path.exists(os.path.join(args.testdir, 'pred%d.ply' % fr))       # the .obj fallback's grey is not scored
-        try:
-            masks.append(np.asarray(Image.open(annotation_path(name))))
-        except OSError as e:
-            raise SystemExit('eval_reproj.py: no annotation for frame %d (%s)' % (fr, e))
-        verts.append(v.numpy()), faces.append(f.numpy()), cols.append(c.numpy()), ids.append(fr)
+    try:
+        rec = recon_io.read(args.testdir, names, annotations=True)
+    except recon_io.ReadError as e:
+        raise SystemExit('eval_reproj.py: %s' % e)
+    imgs, masks, ids, has_colours = rec.imgs, rec.masks, rec.ids, rec.has_colours      # the .obj fallback's grey is not scored
     H, W = imgs[0].shape[:2]
     try:
-        face = check_topology(faces, ids)
         for name, img, m in zip(names, imgs, masks):
             check_size(name, img.shape, H, W)
             check_size(annotation_path(name), m.shape, H, W)
@@ -188,8 +162,8 @@ def main(argv=None, evaluate=None):
     masks = np.stack([(m.reshape(H, W, -1) != 0).any(-1) for m in masks]).astype(np.uint8)
     if not found:
         print('no FlowFW maps for %s: scored on silhouettes%s alone' % (args.seqname, ' and colours' if has_colours else ''))
-    data = dict(verts=np.stack(verts).astype(np.float32), faces=face, K=np.stack([c[3] for c in cams]).astype(np.float32), masks=masks,
-                flows=flows, occs=occs, frames=np.stack(imgs) if has_colours else None, colors=np.stack(cols) if has_colours else None)
+    data = dict(verts=np.stack(rec.verts), faces=rec.face, K=rec.K, masks=masks, flows=flows, occs=occs,
+                frames=np.stack(imgs) if has_colours else None, colors=np.stack(rec.colors) if has_colours else None)
     try:
         if evaluate is None:
             res, boundary = _evaluate_on_device(data, args.bound_th, bool(args.vis))

@@ -26,8 +26,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from eval_reproj import _fmt, check_topology   # noqa: E402  (the same shared-topology check)
+from lasr_amd import recon_io                   # noqa: E402
+from lasr_amd.recon_io import check_topology    # noqa: E402,F401  (imported from here too)
 
 PER_FRAME_INT = ('n_pairs', 'n_faces')
 PER_FRAME_FLOAT = ('ratio', 'volume', 'area', 'jitter')
@@ -70,6 +70,10 @@ def summarise(res, frame_ids, params):
                 n_inverted=int(np.sum(per['inverted'])), n_truncated=int(np.sum(per['truncated'])))
 
 
+def _fmt(x, spec='%.4f'):
+    return 'n/a' if x is None else spec % x
+
+
 def summary_line(doc):
     m = doc['means']
     return 'shape: %d frames, %s intersecting pairs and %s of the faces involved per frame, volume %s, area %s, jitter %s, %d inverted' % (
@@ -107,27 +111,19 @@ def main(argv=None, evaluate=None):
     """evaluate: a stand-in for lasr_amd.nnutils.meshcheck.evaluate taking and returning numpy arrays (the tests without a device
     inject the float64 restatement); by default the tensors go to the GPU."""
     args = parse_args(argv)
-    import render_vis
     try:
-        names = render_vis.frame_list(args.seqname)
+        names = recon_io.frame_list(args.seqname)
     except FileNotFoundError as e:
         raise SystemExit('eval_shape.py: no config for sequence %s (%s)' % (args.seqname, e))
     if not names:
         raise SystemExit('eval_shape.py: no frames for sequence %s' % args.seqname)
     if args.max_pairs < 0:
         raise SystemExit('eval_shape.py: --max_pairs must be at least 0')
-    verts, faces, ids = [], [], []
-    for name in names:
-        fr = int(os.path.basename(name).split('.')[-2])
-        try:
-            v, f, _ = render_vis.load_mesh(args.testdir, fr)
-        except (OSError, ValueError) as e:
-            raise SystemExit('eval_shape.py: no mesh for frame %d in %s (%s)' % (fr, args.testdir, e))
-        verts.append(v.numpy()), faces.append(f.numpy()), ids.append(fr)
     try:
-        face = check_topology(faces, ids)
-        check_finite(verts, ids)
-        verts = np.stack(verts).astype(np.float32)
+        rec = recon_io.read(args.testdir, names, frames=False, cams=False)
+        face, ids = rec.face, rec.ids
+        check_finite(rec.verts, ids)
+        verts = np.stack(rec.verts)
         res = (evaluate or _evaluate_on_device)(verts, face, args.max_pairs)
     except ValueError as e:
         raise SystemExit('eval_shape.py: %s' % e)

@@ -23,6 +23,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from lasr_amd import recon_io                   # noqa: E402
+from lasr_amd.recon_io import check_topology    # noqa: E402,F401  (imported from here too)
 
 
 def parse_args(argv=None):
@@ -38,16 +40,6 @@ def parse_args(argv=None):
     p.add_argument('--preview', default='', help='GIF to write: the frames with the visible points drawn')
     p.add_argument('--radius', default=2, type=int, help='radius in pixels of the points of the preview')
     return p.parse_args(argv)
-
-
-def check_topology(faces_list, frame_ids):
-    """Every pred<i> must share the faces of the first, as scripts/bake_texture.py requires."""
-    first = np.asarray(faces_list[0])
-    for fr, f in zip(frame_ids[1:], faces_list[1:]):
-        f = np.asarray(f)
-        if f.shape != first.shape or (f != first).any():
-            raise ValueError('pred%d does not share the topology of pred%d' % (fr, frame_ids[0]))
-    return first
 
 
 def check_queries(q, T):
@@ -80,33 +72,23 @@ def query_colours(queries, H, W):
 def main(argv=None):
     args = parse_args(argv)
     from PIL import Image
-    import render_vis
     from lasr_amd.nnutils import tracks as tk
     dev = torch.device('cuda', 0)
-    names = render_vis.frame_list(args.seqname)
+    names = recon_io.frame_list(args.seqname)
     if not names:
         raise SystemExit('export_tracks.py: no frames for sequence %s' % args.seqname)
     T = len(names)
     if not 0 <= args.query_frame < T:
         raise SystemExit('export_tracks.py: --query_frame %d is outside the %d frames' % (args.query_frame, T))
-    imgs, verts, faces, cams, ids = [], [], [], [], []
-    for name in names:
-        fr = int(os.path.basename(name).split('.')[-2])
-        imgs.append(np.asarray(Image.open(name).convert('RGB')))
-        try:
-            v, f, _ = render_vis.load_mesh(args.testdir, fr)
-            cams.append(np.loadtxt(os.path.join(args.testdir, 'cam%d.txt' % fr)))
-        except (OSError, ValueError) as e:
-            raise SystemExit('export_tracks.py: no mesh for frame %d in %s (%s)' % (fr, args.testdir, e))
-        verts.append(v), faces.append(f.numpy()), ids.append(fr)
     try:
-        face = check_topology(faces, ids)
-    except ValueError as e:
+        rec = recon_io.read(args.testdir, names)
+    except recon_io.ReadError as e:
         raise SystemExit('export_tracks.py: %s' % e)
+    imgs, ids = rec.imgs, rec.ids
     H, W = imgs[0].shape[:2]
-    tv = torch.stack(verts).to(dev)
-    tf = torch.from_numpy(face).to(dev)
-    tK = torch.tensor(np.stack([c[3] for c in cams]), dtype=torch.float32, device=dev)
+    tv = torch.from_numpy(np.stack(rec.verts)).to(dev)
+    tf = torch.from_numpy(rec.face).to(dev)
+    tK = torch.from_numpy(rec.K).to(dev)
     with torch.no_grad():
         if args.queries:
             try:
