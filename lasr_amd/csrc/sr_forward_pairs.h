@@ -32,11 +32,13 @@
 //            inside and the 90-instruction three-projection branch ran at 27 % live lanes (tools/pair_stats.py);
 //   merge    partial states (alpha product, running maximum, rescaled sums) are folded into their pixel's state.
 //
-// What changes against the one-wave kernel is the ORDER in which a pixel's fragments meet its state (inside fragments first,
-// then outside fragments in index order, a stolen run merged at the end of each chunk): alpha product and depth softmax are
-// symmetric in the fragments, only the rounding sequence moves (image within ~1e-6 of the reference-order kernels; the running
-// maximum is exact).  Every (pixel, face) pair itself goes through the same instruction sequence as in forward_face
-// (K.cu:370-453).
+// What changes against the one-wave kernel is the ORDER in which a pixel's fragments meet its state: chunk by chunk, and a round's
+// list is DEALT over its chunks (chunk c of nch holds the list positions c, c + nch, ...: see chunk_pos below), so a pixel meets
+// the faces of residue 0 first, then those of residue 1, ...; within a chunk inside fragments first, then outside fragments in
+// index order, a stolen run merged at the end of the chunk; with two teams, the odd chunks' state merged at the very end.  Alpha
+// product and depth softmax are symmetric in the fragments, only the rounding sequence moves (image within ~1e-6 of the
+// reference-order kernels; the running maximum is exact).  Every (pixel, face) pair itself goes through the same instruction
+// sequence as in forward_face (K.cu:370-453).
 #pragma once
 
 namespace lasr {
@@ -46,6 +48,24 @@ constexpr int PW_LIST = 1024;         // tile list entries per round (u16 ids re
 constexpr int PW_TILE = 16;
 
 typedef unsigned long long u64_t;
+
+// ---- which list entries a chunk holds.  A round's `count` entries go into nch = ceil(count / 64) chunks, DEALT round-robin: chunk c
+// holds the list positions c, c + nch, c + 2 nch, ... -- count / nch of them, one more in the first count % nch chunks.  The list is
+// in face order and face order is spatially coherent (subdivided icospheres), so 64 CONSECUTIVE entries cover one corner of the
+// tile: a few lanes hold most of the chunk's pairs and both per-lane loops run as long as their fullest lane.  Dealt, every chunk
+// is a sample of the whole list and its pairs spread over the tile (tools/pair_stats.py: walk iterations -8.9 %, classification
+// -5.7 % on the bench frames).  Bit e of every mask is still lane e's entry, and a chunk's entries are still in ascending face order.
+// LASR_PW_DEAL=0 (a measurement build, make variant) keeps 64 consecutive entries per chunk.
+#ifndef LASR_PW_DEAL
+#define LASR_PW_DEAL 1
+#endif
+__host__ __device__ constexpr int chunk_count(int count) { return (count + PW_CAP - 1) / PW_CAP; }
+__host__ __device__ constexpr int chunk_size(int count, int nch, int c) { return c < nch ? count / nch + (c < count % nch ? 1 : 0) : 0; }
+__host__ __device__ constexpr int chunk_pos(int nch, int c, int l) { return c + l * nch; }
+static_assert(chunk_count(0) == 0 && chunk_count(1) == 1 && chunk_count(64) == 1 && chunk_count(65) == 2 && chunk_count(PW_LIST) == PW_LIST / PW_CAP, "chunks per round");
+static_assert(chunk_size(65, 2, 0) == 33 && chunk_size(65, 2, 1) == 32 && chunk_size(65, 2, 2) == 0, "sizes differ by at most one; a trip past the last chunk is empty");
+static_assert(chunk_size(128, 2, 1) == 64 && chunk_size(129, 3, 0) == 43 && chunk_size(129, 3, 2) == 43 && chunk_size(PW_LIST, 16, 15) == PW_CAP, "no chunk beyond 64 entries");
+static_assert(chunk_pos(3, 2, 0) == 2 && chunk_pos(3, 2, 42) == 128 && chunk_pos(2, 0, 32) == 64, "chunk c: positions c, c + nch, ...; the last one is the list's last");
 
 // ---- the staged record (floats; 14 quads + the attributes)
 //   q0  inv0..3      q1  inv4..7      q2  inv8, flags, rect lo, edge table
@@ -410,6 +430,8 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
     // A chunk of fewer than 64 entries leaves the slot as it was: a valid table from an earlier chunk (indices 0..2), or, before the
     // first full chunk, whatever the LDS held -- then the index could be 3 and the 0 / 1 factors were read past sel[23].  The word
     // starts as an empty table (every index 0), and sel is padded, so the rider's reads stay in its own blocks.  Its result is discarded.
+    // (Dealt chunks are partial whenever the round's count is no multiple of 64 -- 100 entries are 50 + 50 -- so most tiles never
+    // stage the slot at all: the rider then reads this word and whatever else the slot held, all of it inside rec[team].)
     if (tid < SPLIT) L.rec[tid][63 * RS + PR_ETBL] = 0.f;
     // level 0: the groups of 64 consecutive faces whose union rect meets the 16x16 tile (every wave evaluates the same test)
     const int G = groups_of(A.F);
@@ -501,13 +523,25 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
         __syncthreads();
 
         float* const Lrec = L.rec[team];
-        for (int cb = 0; cb < count; cb += SPLIT * PW_CAP) {       // team t takes the chunks t, t + SPLIT, ...: same trip count, same barriers
-            const int c0 = cb + team * PW_CAP;
-            const int n = max(0, min(PW_CAP, count - c0));
+        // the round's chunks (chunk_count / chunk_size / chunk_pos above); quotient and remainder once per round, in scalar registers
+        const int cnt = __builtin_amdgcn_readfirstlane(count);
+        const int nch = chunk_count(cnt);
+#if LASR_PW_DEAL
+        const int n_lo = nch ? cnt / nch : 0, n_rem = nch ? cnt % nch : 0;
+#endif
+        for (int cb = 0; cb < nch; cb += SPLIT) {       // team t takes the chunks t, t + SPLIT, ...: same trip count, same barriers
+            const int c = cb + team;                    // (a trip past the last chunk runs with n = 0)
+#if LASR_PW_DEAL
+            const int n = c < nch ? n_lo + (c < n_rem ? 1 : 0) : 0;            // chunk_size(cnt, nch, c)
+            const int lpos = c + lane * nch;                                   // chunk_pos(nch, c, lane)
+#else
+            const int n = max(0, min(PW_CAP, cnt - c * PW_CAP));
+            const int lpos = c * PW_CAP + lane;
+#endif
             // ---- stage: lane = entry, every wave a quarter of the record's source quads (all loads of a chunk in flight at once)
             int cm = 0, rm = 0;                       // the entry's rect as a 16-bit column mask and row mask of the tile
             if (lane < n) {
-                const int fn = base + (int)L.list[c0 + lane];
+                const int fn = base + (int)L.list[lpos];
                 {
                     const short4 q = rects[fn];       // x0, x1, row0, row1 (empty: 32767, -1, 32767, -1)
                     const int a0 = max((int)q.x - tX0, 0), a1 = min((int)q.y - tX0, PW_TILE - 1);

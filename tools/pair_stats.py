@@ -1,15 +1,16 @@
 # Counts of (pixel, face) pairs on the bench workload (numpy model of the rect / inside / conservative-far tests): candidates, walked
 # pairs, and the wave iterations of the pair-walk kernel's two per-lane loops (classification and walk) -- unbalanced, rank-paired
 # (the kernel), in quads, synchronised over a tile, dense.
-#   python tools/pair_stats.py
-import numpy as np, sys, math
+#   python tools/pair_stats.py [frame ...]      (default: frames 0, 37, 101, 200 of the bench cycle)
+# The last block sets the kernel's chunks -- a tile's list DEALT round-robin over them -- beside 64 consecutive entries per chunk.
+import numpy as np, sys, math, collections
 import os; sys.path.insert(0,os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lasr_amd import synth
 import bench
 NU=bench.NU; IS=256
 v,f,tex=synth.blobby_mesh(NU)
 n_cycle=bench.N_FRAMES_CYCLE
-frames=[0,37,101,200]
+frames=[int(a) for a in sys.argv[1:]] or [0,37,101,200]
 pv=synth.frame_vertices(v,n_cycle,first=0,count=256)
 m=synth.LASR_MODES
 thr=math.log(1./m['dist_eps']-1.)*m['sigma_val']
@@ -24,6 +25,22 @@ def tri_dist2(px,py,a,b,c):
         d=p1-p0; t=((px-p0[0])*d[0]+(py-p0[1])*d[1])/max(d@d,1e-30); t=np.clip(t,0,1)
         qx=p0[0]+t*d[0]-px; qy=p0[1]+t*d[1]-py; return qx*qx+qy*qy
     return np.minimum(np.minimum(seg(a,b),seg(b,c)),seg(c,a))
+DEAL=collections.defaultdict(int)
+def chunk_counts(ch,tx,ty,T=16):
+    # per pixel of tile (tx, ty): inside pairs, outside-but-near pairs and rect candidates among the chunk's entries
+    ci=np.zeros((T,T),np.int32); co=np.zeros((T,T),np.int32); cc=np.zeros((T,T),np.int32)
+    for k in ch:
+        ix,rows,inside,near=per_face[k]
+        mx=(ix>=tx*T)&(ix<tx*T+T); my=(rows>=ty*T)&(rows<ty*T+T)
+        sub=np.ix_(rows[my]-ty*T,ix[mx]-tx*T)
+        ci[sub]+=inside[np.ix_(my,mx)]; co[sub]+=near[np.ix_(my,mx)]; cc[sub]+=1
+    return ci,co,cc
+def paired_max(k,movable):
+    # the fullest lane after rank r and rank 63 - r (heaviest first, ties by lane) have evened out: the heavier partner hands over
+    # half of the difference, at most what of its work can move
+    order=np.argsort(-k,kind='stable'); ks=k[order]; ms=movable[order]
+    mv=np.minimum((ks[:32]-ks[:31:-1])//2,ms[:32])
+    return int(max((ks[:32]-mv).max(),(ks[:31:-1]+mv).max()))
 for fr in frames:
     fv=pv[fr][f]  # F,3,3
     F=fv.shape[0]
@@ -66,6 +83,18 @@ for fr in frames:
                 ix,rows,inside,near=pf
                 if ix[-1]<tx*T or ix[0]>=tx*T+T or rows.min()>=ty*T+T or rows.max()<ty*T: continue
                 ent.append(k)
+            if ent: DEAL['tiles']+=1; DEAL['entries']+=len(ent); DEAL['chunks']+=-(-len(ent)//64)
+            # the same list DEALT round-robin over its chunks (the kernel: chunk c of nch holds positions c, c + nch, ...) against 64
+            # consecutive entries per chunk (LASR_PW_DEAL=0): iterations of the two per-lane loops, rank-paired as the kernel pairs them
+            # (the walk moves outside pairs only), with no balance, and dense (pairs / 64)
+            nch=-(-len(ent)//64)
+            for mode,chunks in (('consecutive',[ent[c0:c0+64] for c0 in range(0,len(ent),64)]),('dealt',[ent[c::nch] for c in range(nch)])):
+                for ch in chunks:
+                    ci,co,cc=chunk_counts(ch,tx,ty)
+                    for w in range(4):
+                        kk=(ci+co)[w::4].reshape(-1); ko=co[w::4].reshape(-1); cand=cc[w::4].reshape(-1)
+                        DEAL[mode,'walk rank']+=paired_max(kk,ko); DEAL[mode,'walk none']+=kk.max(); DEAL[mode,'walk dense']+=math.ceil(kk.sum()/64)
+                        DEAL[mode,'class rank']+=paired_max(cand,cand); DEAL[mode,'class none']+=cand.max(); DEAL[mode,'class dense']+=math.ceil(cand.sum()/64)
             for c0 in range(0,len(ent),64):
                 ch=ent[c0:c0+64]
                 ci=np.zeros((T,T),np.int32); co=np.zeros((T,T),np.int32); cc=np.zeros((T,T),np.int32)
@@ -121,3 +150,10 @@ Ts=np.array([r[0] for _,rows in st for r in rows])
 print('chunk-waves',len(Ts),'mean T',Ts.mean(),'pct',np.percentile(Ts,[50,75,90,95,99,100]))
 for q in (256,384,512,768,1024): print('T>',q,(Ts>q).mean(), 'pairs share',Ts[Ts>q].sum()/Ts.sum())
 nz=Ts[Ts>0]; print('nonzero',len(nz),'batches dense',np.ceil(nz/64).sum(),'ideal',nz.sum()/64)
+nf=len(frames)
+print('chunk composition, wave-iterations per frame (frames %s): %.1f busy tiles, %.1f list entries, %.1f chunks per frame'%(frames,DEAL['tiles']/nf,DEAL['entries']/nf,DEAL['chunks']/nf))
+print('%-34s %12s %12s %8s'%('','consecutive','dealt','change'))
+for key,label in (('walk rank','walk, rank-paired (the kernel)'),('walk none','walk, no balance'),('walk dense','walk, dense'),
+                  ('class rank','classification, rank-paired'),('class none','classification, no balance'),('class dense','classification, dense')):
+    a,b=DEAL['consecutive',key]/nf,DEAL['dealt',key]/nf
+    print('%-34s %12.1f %12.1f %+7.1f%%'%(label,a,b,100.*(b-a)/a))
