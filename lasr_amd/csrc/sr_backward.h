@@ -45,13 +45,21 @@ constexpr bool BWD_FM = true;
 constexpr int QCAP = 128;   // ring entries per wave (power of two, >= 2 * 64)
 constexpr int BWD_THREADS = 64;   // one wave per workgroup (see backward_impl)
 
-// (Register budget of the six- / nine-channel instantiations: 90 / 106 VGPRs = 5 / 4 waves per SIMD.  Asking for one wave more,
+// (Register budget of the six- / nine-channel instantiations: 91 / 107 VGPRs = 5 / 4 waves per SIMD.  Asking for one wave more,
 // amdgpu_waves_per_eu(6 / 5), gives 78 / 88 VGPRs without a spill and a 28-50 % SLOWER kernel -- the schedule that fits re-derives
 // instead of keeping -- profiles/r05_backward_ab.txt.  Not requested.)
-template <bool LASR_FAST, int NCH>
+// WIDE: the pixel planes through 64-bit per-lane addresses (see the plane bases below), for calls whose plane offsets do not fit
+// 32 bits (the host's decision, RasterArgs::plane_off32).  An instantiation of its own rather than a second loop inside the kernel:
+// with both loops in one kernel the six-channel instantiation needs 101 VGPRs instead of 91 -- a resident wave.
+template <bool LASR_FAST, int NCH, bool WIDE = false>
 __global__ __launch_bounds__(BWD_THREADS)
 #if LASR_BWD_WPE8
 __attribute__((amdgpu_waves_per_eu(LASR_FAST && NCH == 3 ? 8 : 1, LASR_FAST && NCH == 3 ? 8 : 8)))      // measurement build
+#else
+// Three channels: seven waves per SIMD and no more.  Without its per-lane plane addresses the kernel fits 64 VGPRs, and a schedule
+// made for eight waves issues stage 2's plane loads one or two at a time, each followed by its wait (measured at 256 frames:
+// 1.108 ms against 1.008 ms); aimed at seven it issues the eight loads of the gradient block back to back as before (71 VGPRs).
+__attribute__((amdgpu_waves_per_eu(LASR_FAST && NCH == 3 && !WIDE ? 6 : 1, LASR_FAST && NCH == 3 && !WIDE ? 7 : 8)))
 #endif
 void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
                                                           const float* __restrict__ aggrs,
@@ -187,16 +195,16 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
         const float zlo = fminf(fminf(z0, z1), z2), zhi = fmaxf(fmaxf(z0, z1), z2);
         depth_safe = zlo > 0.f && zlo * (1.f - 1e-4f) > A.near && zhi * (1.f + 1e-4f) < A.far;
     }
-    // (the ten pixel planes a face reads go through plain 64-bit addressed loads: buffer descriptors with the plane offset as a
-    // scalar -- one 32-bit byte offset per pixel instead of an address computation per load -- were measured 1.5 % SLOWER,
-    // profiles/r04_opt_ab.txt; a scalar base pointer per plane with one 32-bit per-lane offset is a form the compiler takes for the
-    // two aggregate planes only and steps the other eight from a 64-bit per-lane address, profiles/experiments/README.md)
-    auto ld_plane = [&](const float* base, int nplanes, int plane, int pn_) -> float {
-#if defined(LASR_BWD_ABL) && LASR_BWD_ABL == 3       // measurement build: everything but the pixel-plane loads
-        return 0.25f + 1e-3f * (float)(pn_ & 255) + 0.01f * (float)plane;
-#endif
-        return base[((size_t)bn * nplanes + plane) * P + pn_];
-    };
+    // The pixel planes a face reads (gcolors and colors: NCH + 1 planes each, aggrs: 2) go through ONE wave-uniform base pointer per
+    // (image, tensor) in an SGPR pair and a 32-bit per-lane byte offset: 4 * pn, formed once per batch and stepped by the plane stride
+    // with one 32-bit add per plane (gcolors and colors share it).  The loads come out as `global_load_dword v, voffset, s[base:base+1]`;
+    // before, each had a 64-bit per-lane address of its own (v_mad_u64_u32, v_lshlrev_b64 and a v_lshl_add_u64 per load).  Each base
+    // is made opaque once it is formed (plane_base): otherwise the compiler folds the tensors' bases back into per-lane addresses.
+    // A base per (image, PLANE) -- no add at all -- is slower at three channels: twenty more SGPRs to form in every wave's prologue
+    // for 3.6 batches per face (profiles/r13_plane_address_ab.txt).  The host decides whether the offsets fit 32 bits (sr_common.h:
+    // plane_offsets_fit32); beyond that the 64-bit addresses are kept (WIDE).
+    constexpr int GC = 0, CO = 1, AG = 2;
+    const unsigned P4 = (unsigned)P * 4u;        // (narrow form only: there 4 (NCH + 1) P < 2^32)
 
     // lane -> (row, col) inside the bbox, advanced incrementally (one division per face)
     int r = 0, c = 0;
@@ -211,6 +219,20 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
 #endif
 
     int head = 0, tail = 0, base = 0;            // wave-uniform ring state
+    gplane_t pb[3];
+    if (!WIDE) {
+        pb[GC] = plane_base(gcolors, (size_t)bn * (NCH + 1), P);
+        pb[CO] = plane_base(colors, (size_t)bn * (NCH + 1), P);
+        pb[AG] = plane_base(aggrs, (size_t)bn * 2, P);
+    }
+    // which: GC / CO / AG, the tensor's base; off_ = 4 * pn_ (the batch's one byte offset)
+    auto ld_plane = [&](const float* tensor, int which, int nplanes, int plane, int pn_, unsigned off_) -> float {
+#if defined(LASR_BWD_ABL) && LASR_BWD_ABL == 3       // measurement build: everything but the pixel-plane loads
+        return 0.25f + 1e-3f * (float)(pn_ & 255) + 0.01f * (float)plane;
+#endif
+        if (WIDE) return tensor[((size_t)bn * nplanes + plane) * P + pn_];
+        return ld_plane_at(pb[which], off_ + (unsigned)plane * P4);
+    };
     while (true) {
         if (base < npx) {
             // ---------------- stage 1
@@ -254,6 +276,7 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
         if (!active) continue;
         const int xi = packed & 0xffff, row = packed >> 16;
         const int pn = row * IS + xi;
+        unsigned po = (unsigned)pn << 2;
         const float xp = centre_x(xi), yp = centre_y(row);
 
         float w0, w1, w2;
@@ -280,10 +303,10 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
 #endif
 
         // alpha path (K.cu:583-593); hard alpha: the reference still adds g_alpha into C
-        float Ca = ld_plane(gcolors, NCH + 1, NCH, pn);
+        float Ca = ld_plane(gcolors, GC, NCH + 1, NCH, pn, po);
         if (m.alpha == 1) Ca = div_<FM>(Ca, (float)A.F);
         else if (m.alpha == 2) {
-            const float a_out = ld_plane(colors, NCH + 1, NCH, pn);
+            const float a_out = ld_plane(colors, CO, NCH + 1, NCH, pn, po);
             Ca *= div_<FM>(1 - a_out, fmaxf(1 - D, 1e-6f));
         }
         float C = Ca;
@@ -305,11 +328,16 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
         }
 
         float gz0 = 0, gz1 = 0, gz2 = 0;
+        // (the offset re-enters a block of loads as an opaque value: instruction selection works block by block, and only an offset
+        // whose 32 -> 64 bit extension it sees in the loads' own block becomes the load's voffset.  Emits nothing.)
+        auto reenter = [&]() { if (!WIDE) asm volatile("" : "+v"(po)); };
         if (m.rgb == 0) {
-            if ((float)fn == ld_plane(aggrs, 2, 1, pn)) {       // K.cu:603
+            reenter();
+            if ((float)fn == ld_plane(aggrs, AG, 2, 1, pn, po)) {       // K.cu:603
+                reenter();
                 float g[NCH];
 #pragma unroll
-                for (int k = 0; k < NCH; k++) g[k] = ld_plane(gcolors, NCH + 1, k, pn);
+                for (int k = 0; k < NCH; k++) g[k] = ld_plane(gcolors, GC, NCH + 1, k, pn, po);
                 if (vertex_tex) {
 #pragma unroll
                     for (int k = 0; k < NCH; k++) {
@@ -324,13 +352,14 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
                 }
             }
         } else if (front || m.double_side) {                                 // K.cu:611-640
-            const float ssum = ld_plane(aggrs, 2, 0, pn);
-            const float smax = ld_plane(aggrs, 2, 1, pn);
+            reenter();
+            const float ssum = ld_plane(aggrs, AG, 2, 0, pn, po);
+            const float smax = ld_plane(aggrs, AG, 2, 1, pn, po);
             const float zn = div_<FM>(A.far - zp, A.far - A.near);
             const float sm = div_<FM>(D * exp_<FM>(div_<FM>(zn - smax, A.gamma)), ssum);
             float g[NCH];
 #pragma unroll
-            for (int k = 0; k < NCH; k++) g[k] = ld_plane(gcolors, NCH + 1, k, pn);
+            for (int k = 0; k < NCH; k++) g[k] = ld_plane(gcolors, GC, NCH + 1, k, pn, po);
             if (vertex_tex) {
 #pragma unroll
                 for (int k = 0; k < NCH; k++) {
@@ -346,7 +375,7 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
             float Crgb = 0.f;
 #pragma unroll
             for (int k = 0; k < NCH; k++)
-                Crgb += g[k] * (sample_colour(tex, w0, w1, w2, A.res, k, m.tex, lim, NCH) - ld_plane(colors, NCH + 1, k, pn));
+                Crgb += g[k] * (sample_colour(tex, w0, w1, w2, A.res, k, m.tex, lim, NCH) - ld_plane(colors, CO, NCH + 1, k, pn, po));
             Crgb *= sm;
             C += div_<FM>(Crgb, D);
             const float Cz = div_<FM>(div_<FM>(Crgb, A.gamma), A.near - A.far) * zp * zp;

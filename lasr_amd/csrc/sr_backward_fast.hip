@@ -11,12 +11,13 @@ namespace lasr {
 void launch_backward_fast(int nch, dim3 grid, hipStream_t st, const RasterArgs& A, const float* colors, const float* aggrs,
                           const float* gcolors, float* gfaces, float* gtex)
 {
-    if (nch == 9)
-        hipLaunchKernelGGL((sr_backward_kernel<true, 9>), grid, dim3(BWD_THREADS), 0, st, A, colors, aggrs, gcolors, gfaces, gtex);
-    else if (nch == 6)
-        hipLaunchKernelGGL((sr_backward_kernel<true, 6>), grid, dim3(BWD_THREADS), 0, st, A, colors, aggrs, gcolors, gfaces, gtex);
-    else
-        hipLaunchKernelGGL((sr_backward_kernel<true, 3>), grid, dim3(BWD_THREADS), 0, st, A, colors, aggrs, gcolors, gfaces, gtex);
+    // (A.plane_off32: the plan's decision whether the pixel planes' byte offsets fit 32 bits, sr_common.h)
+#define LASR_LAUNCH_BWD(NCH, WIDE) \
+    hipLaunchKernelGGL((sr_backward_kernel<true, NCH, WIDE>), grid, dim3(BWD_THREADS), 0, st, A, colors, aggrs, gcolors, gfaces, gtex)
+    if (nch == 9) { if (A.plane_off32) LASR_LAUNCH_BWD(9, false); else LASR_LAUNCH_BWD(9, true); }
+    else if (nch == 6) { if (A.plane_off32) LASR_LAUNCH_BWD(6, false); else LASR_LAUNCH_BWD(6, true); }
+    else { if (A.plane_off32) LASR_LAUNCH_BWD(3, false); else LASR_LAUNCH_BWD(3, true); }
+#undef LASR_LAUNCH_BWD
 }
 
 }  // namespace lasr

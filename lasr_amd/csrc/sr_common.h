@@ -30,7 +30,19 @@ struct RasterArgs {
     // ... and of a wave's (image, face) split: gw / F as a multiplication and a shift (face_div below)
     unsigned fdiv_m;
     int fdiv_s;
+    // ... and whether the backward reads its pixel planes through scalar bases and 32-bit byte offsets (plane_offsets_fit32 below)
+    int plane_off32;
 };
+
+// The backward kernel (sr_backward.h) reads the pixel planes of an image through one wave-uniform base pointer per (image, tensor)
+// and a 32-bit per-lane byte offset that spans the tensor's nch + 1 planes of 4 IS^2 bytes.  That holds while the span stays below
+// 2^32 bytes (image sides up to 16383 / 12385 / 10362 at three / six / nine channels); beyond it the launcher takes the
+// instantiation that keeps 64-bit per-lane addresses.
+inline unsigned long long plane_offset_span(int nch, int IS)
+{
+    return (unsigned long long)(nch + 1) * (unsigned long long)IS * (unsigned long long)IS * 4ull;
+}
+inline int plane_offsets_fit32(int nch, int IS) { return plane_offset_span(nch, IS) < (1ull << 32); }
 
 // n / F for 0 <= n < 2^25 -- the wave index of the backward pass; check_common admits N F <= (2^31 - 1) / 64 = 2^25 - 1 -- by an exact
 // magic multiplier instead of the integer-division expansion (v_rcp_iflag and a chain of s_mul_hi / s_cselect in every wave).

@@ -66,6 +66,21 @@ constexpr int R_BB = 0, R_FLAGS = 2, R_INV = 3, R_HK2 = 12, R_FACE = 16, R_DEN =
 typedef const float __attribute__((address_space(4)))* cptr_t;
 __device__ __forceinline__ cptr_t as_const(const float* p) { return (cptr_t)(unsigned long long)p; }
 
+// Plane `plane` of a [.., plane, P] fp32 tensor, wave-uniform, as a base pointer that stays in an SGPR pair: the empty statement
+// emits nothing and hides how the pointer was formed, so the compiler cannot fold the bases of several tensors and the lanes' offsets
+// into per-lane 64-bit addresses.  A lane then reads with a 32-bit byte offset: global_load_dword v, voffset, s[base:base+1].
+typedef const char __attribute__((address_space(1)))* gplane_t;
+__device__ __forceinline__ gplane_t plane_base(const float* tensor, size_t plane, int P)
+{
+    unsigned long long u = (unsigned long long)(tensor + plane * (size_t)P);
+    asm volatile("" : "+s"(u));
+    return (gplane_t)u;
+}
+__device__ __forceinline__ float ld_plane_at(gplane_t base, unsigned byte_offset)
+{
+    return *(const float __attribute__((address_space(1)))*)(base + byte_offset);
+}
+
 struct Modes {
     int dist, rgb, alpha, tex, double_side;
 };

@@ -789,6 +789,7 @@ static RasterArgs make_args(const SrCall& c, char* base, const SrLayout& L, cons
     A.cx_a = 2.f * A.inv_is; A.cx_b = (float)(1 - c.IS) * A.inv_is; A.cy_b = (float)(c.IS - 1) * A.inv_is;
     { const float thr_pad = A.thr * 1.05f; A.far_t = -sqrtf(thr_pad); }
     { const FaceDiv d = face_div_of(c.F); A.fdiv_m = d.m; A.fdiv_s = d.s; }
+    A.plane_off32 = plane_offsets_fit32(c.nch, c.IS);
     A.m = Modes{c.m.dist, c.m.rgb, c.m.alpha, c.m.tex, c.m.double_side ? 1 : 0};
     A.overwrite_grads = 0;
     A.use_bg = c.background != nullptr;
@@ -1032,8 +1033,11 @@ static int backward_impl(const SrCall& c, const float* faces, const float* textu
         ProfScope ps(K_SR_BACKWARD, c.stream);
         if (c.nch > 3 || is_lasr_fast(A.m))
             launch_backward_fast(c.nch, grid, c.stream, A, soft_colors, aggrs_info, grad_soft_colors, grad_faces, grad_textures);
-        else
+        else if (A.plane_off32)
             hipLaunchKernelGGL((sr_backward_kernel<false, 3>), grid, dim3(BWD_THREADS), 0, c.stream, A, soft_colors, aggrs_info,
+                               grad_soft_colors, grad_faces, grad_textures);
+        else                                     // image sides from 16384: the pixel planes through 64-bit addresses (sr_common.h)
+            hipLaunchKernelGGL((sr_backward_kernel<false, 3, true>), grid, dim3(BWD_THREADS), 0, c.stream, A, soft_colors, aggrs_info,
                                grad_soft_colors, grad_faces, grad_textures);
     }
     return launch_ok();

@@ -25,7 +25,7 @@ for m in re.finditer(r'\.group_segment_fixed_size:\s+(\d+)(?:.*\n)*?\s+\.name:\s
         break
 P
 done
-for k in 'sr_backward_kernelILb1ELi3E' 'sr_backward_kernelILb1ELi9E'; do
+for k in 'sr_backward_kernelILb1ELi3ELb0E' 'sr_backward_kernelILb1ELi9ELb0E'; do
   python3 - "$T/sr_backward_fast.s" "$k" <<'P'
 import re, sys
 t = open(sys.argv[1]).read()
