@@ -114,11 +114,13 @@ class _RenderTables(Function):
         ctx.wt, ctx.geom = float(wt), (I, H, P)
         ctx.from_imgs, ctx.want_pair = bool(from_imgs), bool(want_pair)
         bg, vis = bg.view(torch.bool), vis.view(torch.bool)
-        ctx.mark_non_differentiable(flow, bg, fmap, vis)
+        data = (flow, bg, fmap, vis)
+        if from_imgs:
+            data = data + (obspair,)
+        ctx.mark_non_differentiable(*data)                 # one call: torch keeps only the last one's arguments
         ctx.set_materialize_grads(False)
         out = (tabs[0], tabs[1], tabs[2], flow, bg, fmap, vis) + ((pair,) if want_pair else ())
         if from_imgs:
-            ctx.mark_non_differentiable(obspair)
             out = out + (obspair,)
         return out
 
