@@ -1208,6 +1208,38 @@ int lasr_varflow_sor(const float* J, const float* psi, const float* uv, float* d
 int lasr_varflow_occ(const float* f_ab, const float* f_ba, float* occ, int H, int W, float tau, float s, void* hip_stream);
 
 /*
+ * ---- Gradient constancy for the variational optical flow (--vf_gamma; lasr_amd/csrc/robustflow.hip, preprocess/robust_flow.py,
+ * DESIGN.md section 4.16) ---------------------------------------------------------------------------------------------------------
+ * This project's own addition, as the flow above: Brox et al. 2004 keep the image gradient as well as the brightness along the flow,
+ * grad I2(p + w) = grad I1(p), which an additive change of the lighting leaves untouched; Bruhn & Weickert 2005 give the two data
+ * terms their own robust penalties.  The definition is tests/robustflow_restated.py, whose operation order the kernels follow
+ * (-ffp-contract=off); layouts, "clamped", gradient and bilinear are those of the section above, and pyramid, expansion, solver and
+ * consistency map are its entry points, unchanged.
+ *
+ * lasr_rflow_derivs: level [H,W,3] -> record [H,W,3,6], LASR_RFLOW_RECORD = 18 floats (72 bytes) per pixel: per channel
+ *   (I, Ix, Iy, Ixx, Ixy, Iyy) with Ix, Iy = gradient(I); Ixx, Ixy = gradient(Ix); Iyy = the y part of gradient(Iy): the clamped
+ *   central difference applied twice, so the border clamps twice.  A workgroup owns 32 x 8 pixels and stages them and a halo of 2
+ *   in LDS.  A level's record is constant over its warps: one call per level and frame.
+ * lasr_rflow_tensor: R1, R2 the records of I1 and I2, uv [2,H,W] -> Jb [6,H,W], Jg [6,H,W].  valid and the bilinear taps at
+ *   p + uv are those of lasr_varflow_tensor, and Jb holds its very values.  Per channel, with s(.) the bilinear sample of a plane
+ *   of R2: Ixx = 0.5 (s(I2xx) + I1xx), likewise Ixy and Iyy; Ixt = s(I2x) - I1x, Iyt = s(I2y) - I1y;
+ *   Jg = the sum over the channels in order of (Ixx^2 + Ixy^2, Ixx Ixy + Ixy Iyy, Ixy^2 + Iyy^2, Ixx Ixt + Ixy Iyt,
+ *   Ixy Ixt + Iyy Iyt, Ixt^2 + Iyt^2): the outer products of the rows (Ixx, Ixy, Ixt) and (Ixy, Iyy, Iyt).  Both are 0 where not valid.
+ * lasr_rflow_weights: psi_b = 0.5 / sqrt(max(r2(Jb, d), 0) + eps^2) and psi_g likewise from Jg, r2 as in lasr_varflow_weights;
+ *   J [6,H,W] = (beta psi_b) Jb + (gamma psi_g) Jg, psi [2,H,W] = (1, psi_s) with psi_s of lasr_varflow_weights: what
+ *   lasr_varflow_sor takes.
+ * No entry point uses floating-point atomics: the same input gives the same bits on every run.
+ * Checked on the host before any launch (LASR_E_BADARG): LASR_VARFLOW_MIN_SIZE <= H, W <= LASR_VARFLOW_MAX_SIZE; eps > 0, beta >= 0,
+ *   gamma >= 0, not both 0, all finite; every pointer non-NULL; record distinct from level, Jb from Jg, J from Jb, Jg and psi.
+ *   Device contents are not read on the host.  These launches are not in the lasr_prof_* kernel table.
+ */
+#define LASR_RFLOW_RECORD 18
+int lasr_rflow_derivs(const float* level, float* record, int H, int W, void* hip_stream);
+int lasr_rflow_tensor(const float* R1, const float* R2, const float* uv, float* Jb, float* Jg, int H, int W, void* hip_stream);
+int lasr_rflow_weights(const float* Jb, const float* Jg, const float* uv, const float* d, float* J, float* psi, int H, int W, float eps,
+                       float beta, float gamma, void* hip_stream);
+
+/*
  * ---- Motion segmentation of preprocess/auto_mask.py (lasr_amd/csrc/motionseg.hip, lasr_amd/nnutils/motionseg.py, DESIGN.md
  * section 4.17) -------------------------------------------------------------------------------------------------------------------
  * This project's own addition: the reference fills Annotations/ with a detector (preprocess/mask.py), which stays out of scope;

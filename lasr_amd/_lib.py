@@ -145,6 +145,10 @@ SIGNATURES = {
     'lasr_varflow_weights': (_i, [_p] * 4 + [_i] * 2 + [_f, _p]),
     'lasr_varflow_sor': (_i, [_p] * 5 + [_i] * 2 + [_f, _f, _i, _p]),
     'lasr_varflow_occ': (_i, [_p] * 3 + [_i] * 2 + [_f, _f, _p]),
+    # lasr_amd/csrc/robustflow.hip
+    'lasr_rflow_derivs': (_i, [_p] * 2 + [_i] * 2 + [_p]),
+    'lasr_rflow_tensor': (_i, [_p] * 5 + [_i] * 2 + [_p]),
+    'lasr_rflow_weights': (_i, [_p] * 6 + [_i] * 2 + [_f, _f, _f, _p]),
     # lasr_amd/csrc/motionseg.hip
     'lasr_motionseg_conf': (_i, [_p] * 3 + [_i] * 2 + [_f, _p]),
     'lasr_motionseg_moments': (_i, [_p] * 5 + [_i] * 2 + [_p]),
@@ -222,6 +226,7 @@ MASKPROP_BINS, MASKPROP_MAX_SIZE, MASKPROP_MAX_RADIUS = 4096, 16384, 8   # LASR_
 TRACK_MAX_SNAP, TRACK_MAX_WINDOW, TRACK_MAX_RADIUS, TRACK_MAX_SIZE, TRACK_SPLAT_ALPHA = 16, 2, 8, 8192, 192   # LASR_TRACK_* of include/lasr_ops.h
 REPROJ_MAX_RADIUS = 96                              # LASR_REPROJ_MAX_RADIUS of include/lasr_ops.h
 VARFLOW_MIN_SIZE, VARFLOW_MAX_SIZE = 2, 16384       # LASR_VARFLOW_* of include/lasr_ops.h
+RFLOW_RECORD = 18                                   # LASR_RFLOW_RECORD of include/lasr_ops.h
 MOTIONSEG_MAX_SIZE, MOTIONSEG_BLOCKS, MOTIONSEG_MOMENTS, MOTIONSEG_BINS, MOTIONSEG_STATE = 16384, 256, 28, 1024, 12   # LASR_MOTIONSEG_*
 MESHCHECK_TILE, MESHCHECK_MAX_FACES, MESHCHECK_MAX_FRAMES = 256, 1 << 20, 65535   # LASR_MESHCHECK_* of include/lasr_ops.h
 SSIM_MIN_SIZE, SSIM_MAX_SIZE, SSIM_TILE_W, SSIM_TILE_H = 11, 4096, 32, 16         # LASR_SSIM_* of include/lasr_ops.h

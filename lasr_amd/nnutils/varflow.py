@@ -212,11 +212,11 @@ def flow_pair(imgA, imgB, **over):
     return f_ab, occlusion(f_ab, f_ba), f_ba, occlusion(f_ba, f_ab)
 
 
-def make_flow_fn(device='cuda', **over):
+def make_flow_fn(device='cuda', pair=None, **over):
     """-> flow_fn(imgA, imgB) as auto_gen.run and maskprop.propagate take it: numpy uint8 [H,W,3] (or [H,W]) in, (flow [H,W,3]
     float32 with a ones channel, occ [H,W] float32) out, both numpy.  The first call of a pair computes both directions (the
     consistency map needs them); the reverse call is served from a cache of that one pair.  flow_fn.stats counts pairs computed
-    and calls served from the cache."""
+    and calls served from the cache.  pair(imgA, imgB, **over) stands in for flow_pair (preprocess/robust_flow.py passes its own)."""
     params(**over)
     cache = {}
     stats = dict(computed=0, cached=0)
@@ -238,7 +238,7 @@ def make_flow_fn(device='cuda', **over):
             stats['cached'] += 1
             return cache.pop(k)
         dev = torch.device(device)
-        out = flow_pair(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev), **over)
+        out = (pair or flow_pair)(torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev), **over)
         f_ab, occ_ab, f_ba, occ_ba = (t.cpu().numpy() for t in out)
         stats['computed'] += 1
         cache.clear()

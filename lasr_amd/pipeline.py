@@ -91,6 +91,10 @@ CAVEATS = collections.OrderedDict([
                        'unverified; --roundtrip is the available check.'),
     ('variational', 'Optical flow without a checkpoint (--flow_method variational): quality on real footage is unverified; large '
                     'displacements and textureless regions are its known limits.'),
+    ('gradient_constancy', 'Gradient-constancy term of the variational flow (-- --vf_gamma, preprocess/robust_flow.py): its weight '
+                           'is derived on relit closed-form fixtures, not on footage, and quality on real footage is unverified.  '
+                           'One flow takes 1.11 (640 x 800) to 1.13 (1080p) times as long with it as without, so the default '
+                           'limits of the masks and flow steps, which carry a factor of 4, hold.'),
     ('vcn_dry', 'No VCN checkpoint was given and the network was chosen: its weights are random, the flows are a dry run.'),
     ('ssim', 'Texture term --ptex_method ssim (no AlexNet weights): its weight is derived, not measured, and quality on real '
              'footage is unverified.'),
@@ -392,12 +396,28 @@ def plan(args):
     return steps
 
 
+def passed_gamma(tokens):
+    """The value of the last --vf_gamma among a script's handed-through tokens (`--vf_gamma 5` or `--vf_gamma=5`); 0 without one or
+    with one the script itself will refuse."""
+    val = 0.
+    for i, tok in enumerate(tokens):
+        if tok == '--vf_gamma' or tok.startswith('--vf_gamma='):
+            text = tok.partition('=')[2] if '=' in tok else (tokens[i + 1] if i + 1 < len(tokens) else '')
+            try:
+                val = float(text)
+            except ValueError:
+                val = 0.
+    return val
+
+
 def describe(args):
     """What report() needs to know about the run and cannot read from the files the steps leave: stored as reconstruct/run.json."""
     route = mask_route(args)
     stages = [stage_flags(args, s) for s in args.stages]
     used = [] if route == 'given' else [route]
     used.append('variational' if args.flow_method == 'variational' else ('vcn_dry' if not args.loadmodel else None))
+    if args.flow_method == 'variational' and passed_gamma(getattr(args, 'passthrough', {}).get('auto_gen', [])) > 0:
+        used.append('gradient_constancy')
     used += ['ssim' if f.get('ptex_method', 'alexnet') == 'ssim' else ('alexnet_random' if not f.get('alexnet_weights') else None)
              for f in stages[:1]]
     used += [None if args.encoder_weights else 'encoder_random', 'one_gpu', 'eval_reproj', 'eval_shape',

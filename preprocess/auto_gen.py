@@ -11,11 +11,14 @@ computed; when the median of its norm inside the mask of i, each axis normalised
 and i moves to j; j always moves on.  Without --loadmodel the model keeps its (seeded) random weights: the reference's dry run.
 --flow_method variational replaces the network by the classical variational flow of lasr_amd/nnutils/varflow.py (DESIGN.md section
 4.16), which needs no checkpoint: no model is built, --loadmodel is refused, and occ-*.pfm holds its forward-backward consistency map.
+With it, --vf_gamma 5 adds the gradient-constancy term of preprocess/robust_flow.py for footage whose lighting changes (default 0:
+brightness constancy alone, as before; the value is derived on relit fixtures, not on footage).
 Images are read and written with PIL and resized with bilinear interpolation on pixel centres (cv2.INTER_LINEAR's convention;
 uint8 images are rounded back to uint8 as cv2 does).
 """
 import argparse
 import glob
+import math
 import os
 import sys
 import time
@@ -41,19 +44,29 @@ FLOW_TUNING = (('alpha', float, 0.03, 'weight of the smoothness term'),
                ('NW', int, 5, 'warps per pyramid level'),
                ('NO', int, 3, 'weight updates (lagged diffusivity) per warp'),
                ('NI', int, 10, 'SOR iterations per weight update'))
+# the two data terms of --flow_method variational: with --vf_gamma > 0 the flow is preprocess/robust_flow.py's, for footage whose
+# lighting changes (5 is the value derived on relit closed-form fixtures, not on footage)
+FLOW_ROBUST = (('gamma', float, 0., 'weight of the gradient-constancy term; 0: brightness constancy alone, 5: the derived value'),
+               ('beta', float, 1., 'weight of the brightness-constancy term once --vf_gamma > 0'))
 
 
 def add_flow_arguments(p):
-    """--flow_method and the vf_* tuning flags, shared with preprocess/propagate_mask.py."""
+    """--flow_method and the vf_* tuning flags, shared with preprocess/propagate_mask.py and preprocess/auto_mask.py."""
     p.add_argument('--flow_method', choices=('vcn', 'variational'), default='vcn',
                    help='vcn: the network (needs --loadmodel to be more than a dry run); variational: the classical flow, no checkpoint')
-    for name, kind, default, text in FLOW_TUNING:
+    for name, kind, default, text in FLOW_TUNING + FLOW_ROBUST:
         p.add_argument('--vf_' + name, type=kind, default=default, help='variational: %s (default %s)' % (text, default))
 
 
 def check_flow_arguments(p, args):
     if args.flow_method == 'variational' and args.loadmodel is not None:
         p.error('--flow_method variational uses no network: --loadmodel %s would be ignored, drop it' % args.loadmodel)
+    for name, _, _, _ in FLOW_ROBUST:
+        v = getattr(args, 'vf_' + name)
+        if not (math.isfinite(v) and v >= 0):
+            p.error('--vf_%s must be finite and not negative, got %s' % (name, v))
+    if args.vf_gamma == 0 and args.vf_beta == 0:
+        p.error('--vf_gamma and --vf_beta are both 0: the flow would have no data term')
 
 
 def parse_args(argv=None):
@@ -147,11 +160,22 @@ def flow_inference(model, imgL_o, imgR_o, testres=1., device='cuda'):
 def variational_flow_fn(args, make=None):
     """flow_fn(imgL, imgR) of --flow_method variational: lasr_amd.nnutils.varflow.make_flow_fn with the vf_* flags.  --testres
     scales the frames before the flow, as it does for the network (without the padding to multiples of 64, which only the network
-    needs); flow and occ come back at the frames' size, the flow in their pixels."""
-    if make is None:
-        from lasr_amd.nnutils import varflow
-        make = varflow.make_flow_fn
-    inner = make(**{name: getattr(args, 'vf_' + name) for name, _, _, _ in FLOW_TUNING})
+    needs); flow and occ come back at the frames' size, the flow in their pixels.  With --vf_gamma > 0 the flow is
+    preprocess/robust_flow.py's (brightness and gradient constancy), built with gamma= and beta= beside the same flags."""
+    tuning = {name: getattr(args, 'vf_' + name) for name, _, _, _ in FLOW_TUNING}
+    if getattr(args, 'vf_gamma', 0.) > 0:
+        if make is None:
+            here = os.path.dirname(os.path.abspath(__file__))
+            if here not in sys.path:
+                sys.path.insert(0, here)
+            import robust_flow                                                     # (beside this file)
+            make = robust_flow.make_flow_fn
+        inner = make(gamma=args.vf_gamma, beta=args.vf_beta, **tuning)
+    else:
+        if make is None:
+            from lasr_amd.nnutils import varflow
+            make = varflow.make_flow_fn
+        inner = make(**tuning)
     testres = float(args.testres)
     if testres == 1:
         return inner

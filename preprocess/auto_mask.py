@@ -91,6 +91,9 @@ def propagate_argv(args, key_paths):
         argv += ['--' + name, str(getattr(args, name))]
     for name, _, _, _ in auto_gen.FLOW_TUNING:
         argv += ['--vf_' + name, str(getattr(args, 'vf_' + name))]
+    for name, _, default, _ in auto_gen.FLOW_ROBUST:                               # (a default run prints the line it always printed)
+        if getattr(args, 'vf_' + name) != default:
+            argv += ['--vf_' + name, str(getattr(args, 'vf_' + name))]
     for flag in ('roundtrip', 'force'):
         if getattr(args, flag):
             argv.append('--' + flag)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What does the variational optical flow cost?  (lasr_amd/nnutils/varflow.py, csrc/varflow.hip)
 
-    python tools/varflow_bench.py [--sizes 1080x1920,480x854] [--iters 20] [--runs 3] [--json out.json]
+    python tools/varflow_bench.py [--sizes 1080x1920,480x854] [--iters 20] [--runs 3] [--gamma 5 [--beta 1]] [--json out.json]
 
 On a seeded synthetic pair (a band-limited texture translated by (0.011 W, 0.004 H), default parameters: 5 warps x 3 weight
 updates x 10 SOR iterations per level) these are timed, warm-up excluded, each as the median over --iters calls with device
@@ -12,6 +12,11 @@ events, and the whole measurement --runs times, the variants alternating inside 
               checkerboard); its edge weights are computed once per ten iterations, not per iteration as the kernel does, which
               favours it
   tensor, weights   the two other per-warp kernels on the finest level
+With --gamma > 0 the flow with the gradient-constancy term (preprocess/robust_flow.py, csrc/robustflow.hip) is timed beside it in
+the same alternation, on the same pair:
+  rflow       one robust_flow.flow(gamma, beta): as flow, plus a derivative record per level and frame
+  rf_derivs, rf_tensor, rf_weights   its three kernels on the finest level (derivs once per level and frame, tensor per warp,
+              weights per weight update); rflow_over_flow is the ratio of the two medians
 The torch composition's result is compared with the kernel's before anything is timed.  Per SOR iteration the script also reports
 the bytes one sweep must move at the least (13 floats per pixel: du, dv, u, v, psi_s, five J planes and psi_d read, du and dv
 written) over the measured time, to set against the HBM rate.  No test asserts a time.
@@ -27,7 +32,9 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'preprocess'))
 from lasr_amd.nnutils import varflow   # noqa: E402
+import robust_flow                     # noqa: E402
 
 
 def make_pair(H, W, dev, seed=0):
@@ -87,7 +94,7 @@ def timed(fn, iters):
     return {'median_ms': statistics.median(ms), 'min_ms': min(ms), 'max_ms': max(ms)}
 
 
-def bench_size(H, W, iters, runs, dev):
+def bench_size(H, W, iters, runs, dev, gamma=0., beta=1.):
     p = varflow.params()
     A, B, shift = make_pair(H, W, dev)
     I1, I2 = varflow.pyramid(A)[0], varflow.pyramid(B)[0]
@@ -107,6 +114,12 @@ def bench_size(H, W, iters, runs, dev):
 
     variants = {'flow': lambda: varflow.flow(A, B), 'sor_x10': sor_x10, 'torch_x10': torch_x10,
                 'tensor': lambda: varflow.tensor(I1, I2, uv), 'weights': lambda: varflow.weights(J, uv, d0, p['eps'])}
+    if gamma > 0:
+        R1, R2 = robust_flow.derivs(I1), robust_flow.derivs(I2)
+        Jb, Jg = robust_flow.tensor(R1, R2, uv)
+        variants.update({'rflow': lambda: robust_flow.flow(A, B, gamma, beta), 'rf_derivs': lambda: robust_flow.derivs(I1),
+                         'rf_tensor': lambda: robust_flow.tensor(R1, R2, uv),
+                         'rf_weights': lambda: robust_flow.weights(Jb, Jg, uv, d0, p['eps'], beta, gamma)})
     native, composed = sor_x10().clone(), torch_x10()
     f = uv.permute(1, 2, 0)
     inner = f[H // 8:-H // 8, W // 8:-W // 8]
@@ -130,6 +143,8 @@ def bench_size(H, W, iters, runs, dev):
     res['torch_iteration_ms'] = res['torch_x10']['median_ms'] / 10
     res['sor_floor_bytes'] = 13 * 4 * H * W
     res['sor_floor_gb_per_s'] = res['sor_floor_bytes'] / (it_ms * 1e-3) / 1e9
+    if gamma > 0:
+        res.update(gamma=gamma, beta=beta, rflow_over_flow=res['rflow']['median_ms'] / res['flow']['median_ms'])
     return res
 
 
@@ -138,6 +153,8 @@ def main(argv=None):
     ap.add_argument('--sizes', default='1080x1920,480x854')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--runs', type=int, default=3)
+    ap.add_argument('--gamma', type=float, default=0., help='> 0: time the flow with the gradient-constancy term beside the plain one')
+    ap.add_argument('--beta', type=float, default=1.)
     ap.add_argument('--json', default='')
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -146,7 +163,7 @@ def main(argv=None):
     out = {'device': torch.cuda.get_device_name(0), 'iters': args.iters, 'sizes': []}
     for s in args.sizes.split(','):
         H, W = (int(v) for v in s.split('x'))
-        out['sizes'].append(bench_size(H, W, args.iters, args.runs, dev))
+        out['sizes'].append(bench_size(H, W, args.iters, args.runs, dev, args.gamma, args.beta))
         torch.cuda.empty_cache()
     print(json.dumps(out))
     if args.json:
