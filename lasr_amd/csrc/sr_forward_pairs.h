@@ -379,18 +379,76 @@ __device__ __forceinline__ u64_t upper_bits(u64_t hm, int moved)
     return p >= 63 ? 0ull : (hm >> (p + 1)) << (p + 1);
 }
 
+// A tile that no face's pixel rect overlaps (ORDER_EMPTY in the launch's order table, sr_raster.hip: sr_order_kernel): its list
+// would be empty, so every pixel ends as it starts and every output bit is a function of the launch's scalars.  ONE wave writes the
+// whole 16x16 tile; the values are formed with the expressions of pairs_tile_body's set-up and finalise (same operations on the
+// same operands: the parent's bits).  With a background argument, a tile wholly inside an image whose side is a multiple of 4
+// and 16-byte aligned tensors, lane l stores the pixel quad l & 3 of row l >> 2: one 16-byte store instruction per plane, NCH + 3
+// per tile.  Everything else -- ragged edge tiles, other sides, tensors aligned to 4 bytes only, no background argument (the
+// background is then what the caller left in soft_colors) -- goes pixel by pixel, four rows per trip as a wave of the tile path.
+template <int NCH>
+__device__ __forceinline__ void store_empty_tile(const RasterArgs& A, float* __restrict__ aggrs, float* __restrict__ colors, int bn, int tx, int ty, int lane)
+{
+    const int IS = A.IS, P = IS * IS;
+    const int x0 = tx * PW_TILE, y0 = ty * PW_TILE;
+    const float ssum = expf(A.eps / A.gamma), smax = A.eps;
+    const float one = 1.f;
+    const float alpha = (float)(1. - (double)one);
+    float* __restrict__ cimg = colors + (size_t)bn * (NCH + 1) * P;
+    float* __restrict__ aimg = aggrs + (size_t)bn * 2 * P;
+    const bool quads = A.use_bg && x0 + PW_TILE <= IS && y0 + PW_TILE <= IS && (IS & 3) == 0 &&
+                       ((((size_t)colors | (size_t)aggrs) & 15) == 0);           // (P is then a multiple of 16: every plane starts aligned)
+    if (quads) {
+        const int pn = (y0 + (lane >> 2)) * IS + x0 + 4 * (lane & 3);
+#pragma unroll
+        for (int k = 0; k < NCH; k++) {
+            const float c = (A.bg[k] * ssum) / ssum;
+            *(float4*)(cimg + (size_t)k * P + pn) = make_float4(c, c, c, c);
+        }
+        *(float4*)(cimg + (size_t)NCH * P + pn) = make_float4(alpha, alpha, alpha, alpha);
+        *(float4*)(aimg + pn) = make_float4(ssum, ssum, ssum, ssum);
+        *(float4*)(aimg + (size_t)P + pn) = make_float4(smax, smax, smax, smax);
+        return;
+    }
+    for (int r = 0; r < 4; r++) {
+        const int px = x0 + (lane & 15), py = y0 + r + 4 * (lane >> 4);
+        if (px >= IS || py >= IS) continue;
+        const int pn = py * IS + px;
+#pragma unroll
+        for (int k = 0; k < NCH; k++) {
+            const float bg = A.use_bg ? A.bg[k] : cimg[(size_t)k * P + pn];
+            cimg[(size_t)k * P + pn] = (bg * ssum) / ssum;
+        }
+        cimg[(size_t)NCH * P + pn] = alpha;
+        aimg[pn] = ssum;
+        aimg[(size_t)P + pn] = smax;
+    }
+}
+
 template <int NCH, int SPLIT>
 __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict__ aggrs, float* __restrict__ colors, PairLds<NCH, SPLIT>& L)
 {
     constexpr int RS = PairLds<NCH, SPLIT>::RS;
     constexpr int NW = 4 * SPLIT;                       // waves per tile
 
-    const Modes m = Modes{2, 1, 2, 1, 1};               // LASR's configuration: euclidean, softmax, prod, vertex, double-sided
-    if (A.near_far_dev) { A.near = A.near_far_dev[0]; A.far = A.near_far_dev[1]; }
     const int IS = A.IS, P = IS * IS;
     const int tiles_x = (IS + PW_TILE - 1) / PW_TILE;
     int bn, tx, ty;
-    tile_of_block(blockIdx.x, gridDim.x, tiles_x, bn, tx, ty, A.order);      // this launch's own order when the host built one (16x16 tiles)
+    bool empty;
+    tile_of_block(blockIdx.x, gridDim.x, tiles_x, bn, tx, ty, A.order, &empty);      // this launch's own order when the host built one (16x16 tiles)
+    // (not the one-team kernel of six channels: with any code behind this branch -- inlined or called, 16-byte stores or not -- the
+    // compiler's register budget for it goes from 95 to 97 VGPRs, five resident waves per SIMD to four, and a forced budget spills;
+    // its empty tiles keep the tile path, which gives the same bits)
+    constexpr bool STORE_ONLY = !(NCH == 6 && SPLIT == 1);
+    if (STORE_ONLY && empty) {                          // wave-uniform over the workgroup: nobody is left waiting at a barrier
+#if defined(LASR_PW_ABL) && LASR_PW_ABL == 5        // measurement build (wrong output): what the empty tiles cost at all
+        return;
+#endif
+        if (threadIdx.x < 64) store_empty_tile<NCH>(A, aggrs, colors, bn, tx, ty, (int)threadIdx.x);
+        return;
+    }
+    const Modes m = Modes{2, 1, 2, 1, 1};               // LASR's configuration: euclidean, softmax, prod, vertex, double-sided
+    if (A.near_far_dev) { A.near = A.near_far_dev[0]; A.far = A.near_far_dev[1]; }
     const int tid = threadIdx.x, wave_all = tid >> 6, lane = tid & 63;
     const int team = SPLIT > 1 ? wave_all >> 2 : 0, wave = wave_all & 3;        // wave: within its team (the pixel rows it owns)
 #ifndef LASR_PW_ROWS

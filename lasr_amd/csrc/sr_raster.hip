@@ -175,8 +175,12 @@ __global__ __launch_bounds__(512) void sr_tile_weight_kernel(const short4* __res
     }
 }
 
+// An entry whose key is 0 -- no face's pixel rect overlaps the tile: every output of the tile is a function of the launch's scalars
+// -- carries `empty_flag` (ORDER_EMPTY for the launches of the pair walk, whose workgroups then only store, sr_forward_pairs.h:
+// store_empty_tile; 0 for the 8x8-tile kernels, which keep the plain table).  Bit 31 is free: N < 32768.  tile_of_block masks it.
+constexpr unsigned ORDER_EMPTY = 0x80000000u;
 __global__ __launch_bounds__(ORDER_THREADS) void sr_order_kernel(const unsigned char* __restrict__ keys, int N, int t8,
-                                                                 int* __restrict__ order, int* __restrict__ busy)
+                                                                 int* __restrict__ order, int* __restrict__ busy, unsigned empty_flag)
 {
     extern __shared__ unsigned char s_key[];
     __shared__ unsigned s_hist[256], s_base[256], s_wave[4];
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(ORDER_THREADS) void sr_order_kernel(const unsigned 
         if (key == 0) pos = first + bits_below_lane(empty);
         if (key >= 0) {
             const int img = div_small(e_first + e, tiles, inv_tiles), t = e_first + e - img * tiles, ty = div_small(t, t8, inv_t8);
-            out[pos] = (img << 16) | (ty << 8) | (t - ty * t8);
+            out[pos] = (int)((unsigned)((img << 16) | (ty << 8) | (t - ty * t8)) | (key == 0 ? empty_flag : 0u));
         }
     }
 }
@@ -332,11 +336,14 @@ __device__ __forceinline__ void forward_face(const RasterArgs& A, const Modes m,
 // border tiles fill the tail of the launch.  With few frames per launch the crowded tiles' serial walks are the critical
 // path (0.2 ms for ONE frame); starting them last cost up to 40 % of a 16-frame launch.  Any order is correct; odd tile
 // counts or frame counts that do not divide over the XCDs keep the plain row-major order.
-__device__ __forceinline__ void tile_of_block(int b, int total, int tiles_x, int& bn, int& tx, int& ty, const int* __restrict__ order = nullptr)
+__device__ __forceinline__ void tile_of_block(int b, int total, int tiles_x, int& bn, int& tx, int& ty, const int* __restrict__ order = nullptr,
+                                              bool* empty = nullptr)
 {
+    if (empty) *empty = false;                      // (only the launch's own order knows: ORDER_EMPTY, masked for every reader)
     if (order) {                                    // the launch's own order (sr_order_kernel): image << 16 | tile row << 8 | tile column
         const int e = __builtin_amdgcn_readfirstlane(order[(b & 7) * (total >> 3) + (b >> 3)]);
-        bn = e >> 16; ty = (e >> 8) & 255; tx = e & 255;
+        bn = (e >> 16) & 0x7fff; ty = (e >> 8) & 255; tx = e & 255;
+        if (empty) *empty = e < 0;
         return;
     }
     const int tiles = tiles_x * tiles_x;
@@ -991,11 +998,12 @@ static int forward_impl(const SrCall& c, const float* faces, const float* textur
         int* order = (int*)(base + L.order);
         unsigned char* keys = (unsigned char*)(base + L.keys(tileso));
         int* busy = P.choice_source == LASR_SR_CHOICE_NONEMPTY_TILES ? choice : nullptr;
+        const bool pair_walk = P.form == LASR_SR_FORM_PAIRS_ONE_TEAM || P.form == LASR_SR_FORM_PAIRS_TWO_TEAMS;
         ProfScope po(K_SR_ORDER, st);
         hipLaunchKernelGGL(sr_tile_weight_kernel, dim3((unsigned)c.N), dim3(512), (size_t)(P.tso + 1) * (P.tso + 1) * sizeof(int), st,
                            A.rects, c.F, P.tso, keys, busy, P.tile_shift);
         hipLaunchKernelGGL(sr_order_kernel, dim3(8 * P.order_groups), dim3(ORDER_THREADS), align_up((size_t)(tileso / 8 / P.order_groups), 16), st,
-                           keys, c.N, P.tso, order, busy);
+                           keys, c.N, P.tso, order, busy, pair_walk ? ORDER_EMPTY : 0u);
         A.order = order;
     }
     if (P.both) { A.choice = choice; A.choice_max = P.choice_max; }
