@@ -360,6 +360,15 @@ def call(name, *args, on=None):
         check(rc, name)
 
 
+def pointers(tensors):
+    """ctypes array of the tensors' device addresses, for the entry points that take one pointer per layer or term.  The array
+    keeps the tensors themselves in `.tensors`: they stay alive as long as it does, and a harness that moves a call's tensor
+    arguments (tests/guarded.py) sees them where a bare array of addresses would hide them."""
+    arr = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+    arr.tensors = tuple(tensors)
+    return arr
+
+
 def f32(*tensors):
     """.contiguous().float() of each tensor (None stays None): one value for one argument, a tuple for several."""
     out = tuple(None if t is None else t.contiguous().float() for t in tensors)

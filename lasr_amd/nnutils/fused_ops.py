@@ -536,8 +536,8 @@ class _CosDistMulti(Function):
         dev = fb[0].device
         d = torch.empty(N, dtype=torch.float32, device=dev)
         scratch = torch.empty(_lib.lib().lasr_cosdist_multi_scratch_floats(Ps, L, N), dtype=torch.float32, device=dev)
-        pa = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fa])
-        pb = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fb])
+        pa = _lib.pointers(fa)
+        pb = _lib.pointers(fb)
         _lib.call('lasr_cosdist_multi_forward', pa, pb, Cs, Ps, L, d, scratch, N, rep, on=dev)
         ctx.save_for_backward(*fa, *fb)
         ctx.rep, ctx.dims = rep, (Cs, Ps, L, N)
@@ -549,9 +549,9 @@ class _CosDistMulti(Function):
         fa, fb = ctx.saved_tensors[:L], ctx.saved_tensors[L:]
         g = _lib.f32(g)
         gb = [torch.empty_like(f) for f in fb]
-        pa = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fa])
-        pb = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fb])
-        pg = (ctypes.c_void_p * L)(*[f.data_ptr() for f in gb])
+        pa = _lib.pointers(fa)
+        pb = _lib.pointers(fb)
+        pg = _lib.pointers(gb)
         _lib.call('lasr_cosdist_multi_backward', pa, pb, Cs, Ps, L, g, pg, N, ctx.rep, on=fb[0])
         return (None,) + (None,) * L + tuple(gb)
 
@@ -687,7 +687,7 @@ class _WeightedMeans(Function):
         n = len(xs)
         ctx.numels = (ctypes.c_int * n)(*[x.numel() for x in xs])
         ctx.weights = (ctypes.c_float * n)(*[float(w) for w in weights])
-        ptrs = (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
+        ptrs = _lib.pointers(xs)
         grp = (ctypes.c_int * n)(*[int(g) for g in groups])
         out = torch.empty(n_groups + 1, dtype=torch.float32, device=xs[0].device)
         _lib.call('lasr_weighted_means_forward', ptrs, ctx.numels, ctx.weights, grp, n, n_groups, out, on=xs[0])

@@ -16,8 +16,22 @@ the call differs between two fills.  `run_case` runs a case plain, under 0xFF (f
   c. the run was not vacuous: a guarded allocation was made, the natives reached are exactly the declared ones, and some
      returned tensor holds more than one distinct value.
 
+Inputs come from the case, not from a wrapper: ordinary caching-allocator blocks, rounded up, with the same stale slack in all
+three runs.  `guarded(fill, relocate=True)` therefore also moves every tensor ARGUMENT of a native that is not one of the
+Guard's own allocations, at the call boundary: the bytes the argument can address (its span: data_ptr() and
+(1 + sum (size_i - 1) * stride_i) * itemsize, from its own shape and strides, so a view is tight) are copied into
+
+    | BAND bytes of `fill` (+ the address's residue) | span | BAND bytes of `fill` |
+
+whose first byte keeps the original address modulo 256 (the kernels that choose a 16-byte or a scalar form from the pointer take
+the path they took in the plain run), the native gets a tensor of the same dtype, shape and strides over the copy, and the bytes
+that changed are copied back afterwards (in/out buffers).  Arguments of one call whose spans overlap or touch in one storage move
+as one block; the same span gets the same block again for the whole `guarded` block, refreshed before each call.  `run_relocated`
+is run_case with relocate=True and the bands of the inputs among those of rule a.
+
 torch itself is never patched; the modules' globals are put back on exit, also after an exception."""
 import contextlib
+import ctypes
 import sys
 import types
 
@@ -41,12 +55,41 @@ def _size_of(args):
     return tuple(int(a) for a in args)
 
 
-class Guard:
-    """State of one `guarded` block: the allocations made, the natives reached."""
+class Block:
+    """One relocated span: backing[lead:lead + nbytes] holds a copy of the bytes start .. start + nbytes of the original."""
+    __slots__ = ('backing', 'lead', 'start', 'nbytes', 'native', 'arg')
 
-    def __init__(self, fill, guard_cpu=False):
-        self.fill, self.guard_cpu = int(fill), bool(guard_cpu)
+    def __init__(self, backing, lead, start, nbytes, native, arg):
+        self.backing, self.lead, self.start, self.nbytes, self.native, self.arg = backing, lead, start, nbytes, native, arg
+
+    def span(self):
+        return self.backing[self.lead:self.lead + self.nbytes]
+
+
+class RelocationError(AssertionError):
+    """An argument that cannot follow its tensor to the relocated copy (a pointer computed by hand)."""
+
+
+def span_bytes(t):
+    """Bytes a tensor can address from its data_ptr(): (1 + sum (size_i - 1) * stride_i) * itemsize."""
+    return (1 + sum((n - 1) * st for n, st in zip(t.shape, t.stride()))) * t.element_size()
+
+
+def _alias(storage, device, offset, nbytes):
+    """A fresh uint8 tensor over bytes offset .. offset + nbytes of an untyped storage: writing through it bumps no version counter
+    of the tensors that share the storage (save_for_backward holds some of them)."""
+    return _torch.empty(0, dtype=_torch.uint8, device=device).set_(storage, offset, (nbytes,), (1,))
+
+
+class Guard:
+    """State of one `guarded` block: the allocations made, the natives reached, the inputs relocated."""
+
+    def __init__(self, fill, guard_cpu=False, relocate=False):
+        self.fill, self.guard_cpu, self.relocate = int(fill), bool(guard_cpu), bool(relocate)
         self.allocations, self.natives = [], []
+        self.blocks = {}                                     # (device, start, nbytes) of the original span -> Block
+        self.relocated = {}                                  # native -> {'args': tensor arguments moved, 'bytes': bytes copied in}
+        self._own = set()                                    # addresses of the storages behind self.allocations
 
     # -- allocation -----------------------------------------------------------------------------------------------------------
     def _wants(self, device, kw):
@@ -64,6 +107,7 @@ class Guard:
         nbytes = numel * _torch.empty((), dtype=dtype).element_size()
         backing = _torch.full((BAND + nbytes + BAND,), self.fill, dtype=_torch.uint8, device=device)
         self.allocations.append(Allocation(backing, nbytes, tuple(shape), dtype, len(self.allocations)))
+        self._own.add(backing.untyped_storage().data_ptr())
         return backing[BAND:BAND + nbytes].view(dtype).view(shape)
 
     def empty(self, *size, **kw):
@@ -77,10 +121,107 @@ class Guard:
             return _torch.empty_like(t, **kw)
         return self.allocate(tuple(t.shape), kw.get('dtype', t.dtype), device)      # (contiguous, whatever t's strides are)
 
+    # -- relocation of the tensor arguments of one native ------------------------------------------------------------------------
+    def _is_input(self, t):
+        if t.numel() == 0 or (t.device.type != 'cuda' and not self.guard_cpu):
+            return False
+        return t.untyped_storage().data_ptr() not in self._own
+
+    def _block(self, device, start, nbytes, native, arg):
+        key = (device, start, nbytes)
+        b = self.blocks.get(key)
+        if b is None:
+            align = 256 if device.type == 'cuda' else 64
+            lead = BAND + start % align                      # the span's first byte keeps the original address modulo `align`
+            backing = _torch.full((lead + nbytes + BAND,), self.fill, dtype=_torch.uint8, device=device)
+            assert backing.data_ptr() % align == 0 and backing.storage_offset() == 0, \
+                'a backing buffer of %s at 0x%x is not %d-byte aligned' % (device, backing.data_ptr(), align)
+            assert (backing.data_ptr() + lead - start) % align == 0
+            b = self.blocks[key] = Block(backing, lead, start, nbytes, native, arg)
+        return b
+
+    def _refuse_pointers(self, name, pos, values):
+        for v in values:
+            if v is None or v < 2 ** 32:
+                continue
+            for b in self.blocks.values():
+                if b.start <= v < b.start + b.nbytes:
+                    raise RelocationError('%s: argument %d holds the integer 0x%x, an address inside a tensor that was relocated '
+                                          '(argument %d of %s): a pointer computed by hand does not follow the copy'
+                                          % (name, pos, v, b.arg, b.native))
+            for a in self.allocations:
+                if a.backing.data_ptr() <= v < a.backing.data_ptr() + a.backing.numel():
+                    raise RelocationError('%s: argument %d holds the integer 0x%x, an address inside guarded allocation %d: pass '
+                                          'the tensor, not a pointer computed by hand' % (name, pos, v, a.ordinal))
+
+    def call(self, real_call, name, args, kw):
+        """real_call(name, *args, **kw) with every input tensor among args (and among the `.tensors` of a ctypes pointer array,
+        lasr_amd._lib.pointers) replaced by a view of a relocated copy; the changed bytes go back afterwards."""
+        found = []                                           # (position, index in .tensors or None, tensor)
+        for pos, a in enumerate(args):
+            if isinstance(a, _torch.Tensor):
+                found.append((pos, None, a))
+            elif isinstance(a, ctypes.Array) and hasattr(a, 'tensors'):
+                found += [(pos, j, t) for j, t in enumerate(a.tensors)]
+        moved = [(pos, j, t, t.data_ptr(), t.data_ptr() + span_bytes(t)) for pos, j, t in found if self._is_input(t)]
+        # groups: spans of one storage that overlap or touch
+        groups = []
+        for item in sorted(moved, key=lambda m: (str(m[2].device), m[2].untyped_storage().data_ptr(), m[3])):
+            t, start, end = item[2], item[3], item[4]
+            last = groups[-1] if groups else None
+            if (last is not None and last['device'] == t.device and last['base'] == t.untyped_storage().data_ptr()
+                    and start <= last['end']):
+                last['end'] = max(last['end'], end)
+                last['items'].append(item)
+            else:
+                groups.append({'device': t.device, 'base': t.untyped_storage().data_ptr(), 'storage': t.untyped_storage(),
+                               'start': start, 'end': end, 'items': [item]})
+        new, work, nbytes = {}, [], 0
+        for grp in groups:
+            n = grp['end'] - grp['start']
+            first = grp['items'][0]
+            b = self._block(grp['device'], grp['start'], n, name, first[0])
+            original = _alias(grp['storage'], grp['device'], grp['start'] - grp['base'], n)
+            b.span().copy_(original)                         # (on the current stream, like the launch that follows)
+            work.append((b, original, original.clone()))
+            nbytes += n
+            for pos, j, t, start, _ in grp['items']:
+                at = b.lead + start - grp['start']
+                assert at % t.element_size() == 0, '%s: argument %d is not aligned to its element size' % (name, pos)
+                new[(pos, j)] = _torch.empty(0, dtype=t.dtype, device=t.device).set_(
+                    b.backing.untyped_storage(), at // t.element_size(), t.shape, t.stride())
+        out = []
+        for pos, a in enumerate(args):
+            if isinstance(a, _torch.Tensor):
+                a = new.get((pos, None), a)
+            elif isinstance(a, ctypes.Array) and hasattr(a, 'tensors'):
+                ts = tuple(new.get((pos, j), t) for j, t in enumerate(a.tensors))
+                a = type(a)(*[t.data_ptr() for t in ts])
+                a.tensors = ts
+            elif isinstance(a, ctypes.Array) and getattr(a, '_type_', None) is ctypes.c_void_p:
+                self._refuse_pointers(name, pos, list(a))
+            elif isinstance(a, int):
+                self._refuse_pointers(name, pos, [a])
+            out.append(a)
+        rec = self.relocated.setdefault(name, {'args': 0, 'bytes': 0})
+        rec['args'] += len(moved)
+        rec['bytes'] += nbytes
+        result = real_call(name, *out, **kw)
+        for b, original, before in work:                     # only the bytes the native changed: the original may have been
+            now = b.span()                                   # written meanwhile through an address a device table holds
+            original.copy_(_torch.where(now != before, now, original))
+        return result
+
     # -- checks ---------------------------------------------------------------------------------------------------------------
     def violations(self):
-        """[{ordinal, shape, dtype, side}] for every band that holds a byte other than the fill (synchronises the device)."""
+        """[{ordinal, shape, dtype, side}] for every band that holds a byte other than the fill, and [{input, arg, side}] (the
+        native and the position of the argument the block was made for) for the bands of the relocated inputs (synchronises the
+        device)."""
         bad = []
+        for b in self.blocks.values():
+            for side, band in (('before', b.backing[:b.lead]), ('after', b.backing[b.lead + b.nbytes:])):
+                if bool((band != self.fill).any()):
+                    bad.append({'input': b.native, 'arg': b.arg, 'side': side})
         for a in self.allocations:
             for side, band in (('before', a.backing[:BAND]), ('after', a.backing[BAND + a.nbytes:])):
                 if bool((band != self.fill).any()):
@@ -100,19 +241,21 @@ def _product_modules():
 
 
 @contextlib.contextmanager
-def guarded(fill, modules=None, lib=None, guard_cpu=False):
+def guarded(fill, modules=None, lib=None, guard_cpu=False, relocate=False):
     """Context manager: see the module docstring.  modules: the modules to patch (default: every loaded lasr_amd.* module);
     lib: the object whose `call(name, ...)` launches natives (default: lasr_amd._lib); guard_cpu: guard CPU tensors too (the
-    harness's own CPU test).  Yields the Guard."""
+    harness's own CPU test); relocate: move the natives' input tensors into tight, poisoned copies.  Yields the Guard."""
     if lib is None:
         from lasr_amd import _lib as lib
-    g = Guard(fill, guard_cpu)
+    g = Guard(fill, guard_cpu, relocate)
     proxy = _TorchProxy('torch')
     proxy.empty, proxy.empty_like = g.empty, g.empty_like
     real_call = lib.call
 
     def call(name, *args, **kw):
         g.natives.append(name)
+        if g.relocate:
+            return g.call(real_call, name, args, kw)
         return real_call(name, *args, **kw)
 
     undo = []
@@ -210,3 +353,33 @@ def run_case(case, device, modules=None, lib=None, guard_cpu=False):
     _same(case, runs[0], runs[1], 'fill 0xFF against fill 0x7F')
     _same(case, plain, runs[0], 'plain against fill 0xFF')
     _same(case, plain, runs[1], 'plain against fill 0x7F')
+
+
+def run_relocated(case, device, modules=None, lib=None, guard_cpu=False, not_relocated=()):
+    """run_case with the inputs relocated (relocate=True): the case plain, under 0xFF and under 0x7F; assert that no band was
+    touched, around outputs, scratch or inputs (a), the same bits in all three runs, by the case's own rule (b), and that the run
+    was not vacuous (c): the natives reached are the declared ones, each of them outside `not_relocated` had a tensor argument
+    relocated, with more than zero bytes, and some returned tensor holds more than one distinct value.  Returns the
+    Guard.relocated record of the last run."""
+    plain = _flat(case.fn(device))
+    runs = []
+    for fill in FILLS:
+        with guarded(fill, modules=modules, lib=lib, guard_cpu=guard_cpu, relocate=True) as g:
+            out = _flat(case.fn(device))
+            bad = g.violations()
+        # c. not vacuous
+        assert frozenset(g.natives) == case.natives, '%s: natives reached %s, declared %s' % (
+            case.name, sorted(set(g.natives)), sorted(case.natives))
+        idle = sorted(n for n in case.natives if n not in not_relocated
+                      and not (g.relocated.get(n, {}).get('args', 0) > 0 and g.relocated[n]['bytes'] > 0))
+        assert not idle, '%s: fill 0x%02X: no tensor argument was relocated for %s' % (case.name, fill, idle)
+        # a. bands intact
+        assert not bad, '%s: fill 0x%02X: guard band touched: %s' % (case.name, fill, bad)
+        runs.append(out)
+    assert any(t.numel() > 1 and bool((t.reshape(-1) != t.reshape(-1)[0]).any()) for t in plain), \
+        '%s: every returned tensor is constant' % case.name
+    # b. same bits
+    _same(case, runs[0], runs[1], 'fill 0xFF against fill 0x7F')
+    _same(case, plain, runs[0], 'plain against fill 0xFF')
+    _same(case, plain, runs[1], 'plain against fill 0x7F')
+    return g.relocated

@@ -207,6 +207,12 @@ def test_the_three_natives_with_guard_bands_and_poison(cuda):
     guarded.run_case(robustflow_guarded.CASE, cuda, modules=[rf] + guarded._product_modules())
 
 
+def test_the_three_natives_with_relocated_inputs(cuda):
+    rf = _rf()
+    record = guarded.run_relocated(robustflow_guarded.CASE, cuda, modules=[rf] + guarded._product_modules())
+    assert sorted(record) == sorted(robustflow_guarded.NATIVES)
+
+
 def test_propagate_mask_on_a_relit_sequence(cuda, tmp_path):
     sys.path.insert(0, os.path.join(ROOT, 'preprocess'))
     import auto_gen
