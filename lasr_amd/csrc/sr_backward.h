@@ -20,28 +20,6 @@ namespace lasr {
 // compaction they would idle through the heavy code.  The heavy code uses v_rcp/v_exp based math
 // (FM = true): the reference backward is itself only defined up to float-atomic ordering.
 constexpr bool BWD_FM = true;
-#ifndef LASR_BWD_LDSREC
-#define LASR_BWD_LDSREC 1      // LASR's modes: stage 2 reads the face's record and attributes from LDS (see the kernel)
-#endif
-#ifndef LASR_BWD_WPE8
-#define LASR_BWD_WPE8 0
-#endif
-#ifndef LASR_BWD_DIVREC
-#define LASR_BWD_DIVREC 1
-#endif
-#ifndef LASR_BWD_ONE
-#define LASR_BWD_ONE 1      // one edge projection per pixel for well-conditioned faces (sr_device.h: euclid_one)
-#endif
-// Per-face constants the wave no longer derives (measurement builds switch a part back to its earlier form: make variant DEFS=-D..=0)
-#ifndef LASR_FC_TIE
-#define LASR_FC_TIE 1       // the near-tie margin from the record (word R_TIE, written by set-up) instead of an IEEE division per wave
-#endif
-#ifndef LASR_FC_TBL
-#define LASR_FC_TBL 1       // the LDS extension's source words from k_bwd_ext_tbl instead of per-lane index arithmetic
-#endif
-#ifndef LASR_FC_DIV
-#define LASR_FC_DIV 1       // gw / F by the host's magic multiplier (sr_common.h: face_div) instead of the integer-division expansion
-#endif
 constexpr int QCAP = 128;   // ring entries per wave (power of two, >= 2 * 64)
 constexpr int BWD_THREADS = 64;   // one wave per workgroup (see backward_impl)
 
@@ -53,21 +31,16 @@ constexpr int BWD_THREADS = 64;   // one wave per workgroup (see backward_impl)
 // with both loops in one kernel the six-channel instantiation needs 101 VGPRs instead of 91 -- a resident wave.
 template <bool LASR_FAST, int NCH, bool WIDE = false>
 __global__ __launch_bounds__(BWD_THREADS)
-#if LASR_BWD_WPE8
-__attribute__((amdgpu_waves_per_eu(LASR_FAST && NCH == 3 ? 8 : 1, LASR_FAST && NCH == 3 ? 8 : 8)))      // measurement build
-#else
 // Three channels: seven waves per SIMD and no more.  Without its per-lane plane addresses the kernel fits 64 VGPRs, and a schedule
 // made for eight waves issues stage 2's plane loads one or two at a time, each followed by its wait (measured at 256 frames:
 // 1.108 ms against 1.008 ms); aimed at seven it issues the eight loads of the gradient block back to back as before (71 VGPRs).
 __attribute__((amdgpu_waves_per_eu(LASR_FAST && NCH == 3 && !WIDE ? 6 : 1, LASR_FAST && NCH == 3 && !WIDE ? 7 : 8)))
-#endif
 void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
                                                           const float* __restrict__ aggrs,
                                                           const float* __restrict__ gcolors,
                                                           float* __restrict__ gfaces, float* __restrict__ gtex)
 {
     __shared__ unsigned int s_ring[BWD_THREADS / 64][QCAP];
-#if LASR_BWD_LDSREC
     // LASR's modes: stage 2 reads the face's record and vertex attributes from LDS -- broadcast ds_reads whose results are VGPR
     // operands -- instead of scalar registers: a VALU instruction with an SGPR operand issues in ~4 cycles, with VGPR operands in
     // ~2.5 (profiles/r02_valu_issue.txt), and stage 2 has ~130 record operands per batch.  (Holding the record in VGPRs for the
@@ -77,7 +50,6 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
     // Behind the record the slot holds BX floats prepared once per face for the distance code (sr_device.h: euclid_one_ext): the three
     // edge blocks one projection reads at a run-time offset, the t[] permutation's 0 / 1 factors and the obtuse corner's operands.
     __shared__ __attribute__((aligned(16))) float s_rec[BWD_THREADS / 64][REC + (LASR_FAST ? BX : 0)];
-#endif
     constexpr bool FM = BWD_FM;
     const Modes m = LASR_FAST ? Modes{2, 1, 2, 1, 1} : A.m;
     if (A.near_far_dev) { A.near = A.near_far_dev[0]; A.far = A.near_far_dev[1]; }
@@ -89,54 +61,27 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
     // same box, first-to-last -> last-to-first: backward 1.292 -> 1.262 ms at 256 frames, 0.318 -> 0.310 at 64, 0.099 -> 0.092
     // at 16, 0.998 -> 0.961 at 64 frames of 512x512; profiles/r04_tile_order_ab.txt).  A face's gradients are written by its
     // own wave: the walk order does not enter the result.
-#if defined(LASR_BWD_ORDER) && LASR_BWD_ORDER == 1      // measurement build: the XCD's images interleaved face by face
-    int blk = xcd_remap(blockIdx.x, gridDim.x);
-    {
-        const int total = gridDim.x, per = total >> 3;
-        if ((total & 7) == 0 && per % A.F == 0) {
-            const int m = per / A.F, i = blockIdx.x >> 3, rank = i / m;
-            blk = ((blockIdx.x & 7) * m + (i - rank * m)) * A.F + rank;
-        }
-    }
-#elif defined(LASR_BWD_ORDER) && LASR_BWD_ORDER == 3    // measurement build: first to last (rounds 2-4 until this change)
-    const int blk = xcd_remap(blockIdx.x, gridDim.x);
-#else
     int blk;
     {
         const int total = gridDim.x, per = total >> 3;
         blk = (total & 7) == 0 ? (blockIdx.x & 7) * per + (per - 1 - (blockIdx.x >> 3)) : total - 1 - blockIdx.x;
     }
-#endif
-#if LASR_FC_TBL
     const int ext_src = LASR_FAST ? (int)k_bwd_ext_tbl[lane] : 0;       // (one coalesced load, in flight while the record's flags arrive)
-#endif
     const int gw = __builtin_amdgcn_readfirstlane((int)((blk * blockDim.x + threadIdx.x) >> 6));
     if (gw >= A.N * A.F) return;
-#if LASR_FC_DIV
-    const int bn = face_div(gw, A.fdiv_m, A.fdiv_s), fn = gw - bn * A.F;
-#else
-    const int bn = gw / A.F, fn = gw - bn * A.F;
-#endif
+    const int bn = face_div(gw, A.fdiv_m, A.fdiv_s), fn = gw - bn * A.F;       // gw / F by the host's magic multiplier (sr_common.h)
     const int IS = A.IS, P = IS * IS;
     const cptr_t rec = as_const(A.recs + (size_t)gw * REC);
     const cptr_t tex = as_const(A.textures + (size_t)gw * A.T * NCH);
     const int flags = __float_as_int(rec[R_FLAGS]);
-#if LASR_BWD_LDSREC
     typedef const float __attribute__((address_space(3)))* lptr_t;
     if (LASR_FAST && (flags & 16)) {
         float* dst = s_rec[threadIdx.x >> 6];
         if (lane < REC) dst[lane] = A.recs[(size_t)gw * REC + lane];
-#if LASR_BWD_ONE && (LASR_BWD_TBL || LASR_BWD_ONEPROJ)
-#if LASR_FC_TBL
         dst[REC + lane] = bwd_ext_word_tbl(A.recs + (size_t)gw * REC, flags, lane, ext_src);
-#else
-        dst[REC + lane] = bwd_ext_word(A.recs + (size_t)gw * REC, flags, lane);
-#endif
-#endif
         __builtin_amdgcn_wave_barrier();
     }
     const lptr_t lrec = (lptr_t)s_rec[threadIdx.x >> 6];
-#endif
 
     // exact pixel rectangle of the bbox test (columns x0..x1, rows r0..r1 from the top); empty when x0 > x1.  Read from the
     // record's first cache line (the flags sit there too) rather than from the separate rect array the forward's binning scans
@@ -157,7 +102,6 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
     const int lim = (A.N * A.F - gw) * A.T;      // texels from this face to the end of the tensor
     // cheap reject only for the soft distance modes and well-conditioned faces; 2 % slack on thr
     const bool use_far = (m.dist == 2) && (flags & 16);
-    const float thr_pad = A.thr * 1.05f;
     const float inv_is = A.inv_is;               // 1.f / (float)IS, from the host (sr_common.h)
     const bool pow2 = (IS & (IS - 1)) == 0;      // then n * (1/IS) == n / IS exactly: skip the division per pixel
     // pixel centres as ONE fma of the converted index: (2 i + 1 - IS) / IS = i * (2 / IS) + (1 - IS) / IS (K.cu:343-346; rows count
@@ -165,14 +109,15 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
     // the division in stage 2 (the distance code is ill-conditioned in the pixel position on edge-on faces, and the surface
     // texel choice must see the forward's barycentrics) and use the fma -- within an ulp -- for stage 1's conservative reject only
     const float cx_a = A.cx_a, cx_b = A.cx_b, cy_b = A.cy_b;      // 2 / IS, (1 - IS) / IS, (IS - 1) / IS
-    auto centre_x = [&](int xi) { return OPT_BWD_S1 && pow2 ? __builtin_fmaf((float)xi, cx_a, cx_b) : pix_center_p2(xi, IS, inv_is, pow2); };
-    auto centre_y = [&](int row) { return OPT_BWD_S1 && pow2 ? __builtin_fmaf((float)row, -cx_a, cy_b) : pix_center_p2(IS - 1 - row, IS, inv_is, pow2); };
+    auto centre_x = [&](int xi) { return pow2 ? __builtin_fmaf((float)xi, cx_a, cx_b) : pix_center_p2(xi, IS, inv_is, pow2); };
+    auto centre_y = [&](int row) { return pow2 ? __builtin_fmaf((float)row, -cx_a, cy_b) : pix_center_p2(IS - 1 - row, IS, inv_is, pow2); };
     // stage 1's reject as signed line distances: d_k = w_k * h_k (h_k = height of vertex k over its opposite edge) is linear in
     // the pixel, so the coefficients are scaled once per face and a pixel costs six fmas, one v_min3 and one compare:
-    // "some d_k < -sqrt(thr_pad)" == certainly_far (conservative either way: 5 % slack on thr, fused vs unfused ~1e-7)
+    // "some d_k < -sqrt(thr_pad)", thr_pad = 1.05 thr: the pixel is certainly farther than sqrt(thr) from the face, so the reference's
+    // `dis >= threshold` test would skip it as well (conservative either way: 5 % slack on thr, fused vs unfused ~1e-7)
     float ld[9];
     const float far_t = A.far_t;                 // -sqrtf(thr_pad)
-    if (OPT_BWD_S1 && use_far) {
+    if (use_far) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             // (v_sqrt_f32, 1 ulp, instead of the 14-instruction IEEE expansion per height: the reject carries 5 % slack on thr,
@@ -181,16 +126,12 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
             ld[3 * k] = rec[R_INV + 3 * k] * h; ld[3 * k + 1] = rec[R_INV + 3 * k + 1] * h; ld[3 * k + 2] = rec[R_INV + 3 * k + 2] * h;
         }
     }
-#if LASR_FC_TIE
     const float tie_scale = rec[R_TIE];          // near_tie_scale(hk2), 0 unless flags bit 4: derived once per face by set-up (sr_device.h)
-#else
-    const float tie_scale = (flags & 16) ? near_tie_scale(rec[R_HK2], rec[R_HK2 + 1], rec[R_HK2 + 2]) : 0.f;     // (sr_device.h: near_tie)
-#endif
     // K.cu:599: a fragment the forward pass depth-culled gets no gradient.  A well-conditioned face whose vertex depths lie
     // strictly inside (near, far) cannot be culled anywhere (its clipped barycentrics are >= 0 and sum to 1 within 1e-4, so the
     // interpolated depth stays within the vertex range up to rounding): one test per face instead of one per fragment
     bool depth_safe = false;
-    if (OPT_BWD_MATH && (flags & 16)) {
+    if (flags & 16) {
         const float z0 = rec[R_FACE + 2], z1 = rec[R_FACE + 5], z2 = rec[R_FACE + 8];
         const float zlo = fminf(fminf(z0, z1), z2), zhi = fmaxf(fmaxf(z0, z1), z2);
         depth_safe = zlo > 0.f && zlo * (1.f - 1e-4f) > A.near && zhi * (1.f + 1e-4f) < A.far;
@@ -208,15 +149,10 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
 
     // lane -> (row, col) inside the bbox, advanced incrementally (one division per face)
     int r = 0, c = 0;
-#if LASR_BWD_DIVREC
     // (the setup kernel left the divisions in the record: rec[15] = m | dr << 17 with lane / bw == (lane * m) >> 16, sr_device.h)
     const int walk = __float_as_int(rec[15]);
     const int dr = empty ? 0 : walk >> 17, dc = empty ? 0 : 64 - dr * bw;
     if (!empty) { r = (lane * (walk & 0x1ffff)) >> 16; c = lane - r * bw; }
-#else
-    const int dr = empty ? 0 : 64 / bw, dc = empty ? 0 : 64 - dr * bw;
-    if (!empty) { r = lane / bw; c = lane - r * bw; }
-#endif
 
     int head = 0, tail = 0, base = 0;            // wave-uniform ring state
     gplane_t pb[3];
@@ -242,18 +178,12 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
             if (c >= bw) { c -= bw; r += 1; }
             base += 64;
             bool keep = in_range;                              // every pixel of the rect passes the bbox test
-            if (OPT_BWD_S1) {
-                if (use_far) {
-                    const float xp = __builtin_fmaf((float)xi, cx_a, cx_b), yp = __builtin_fmaf((float)row, -cx_a, cy_b);
-                    const float d0 = __builtin_fmaf(ld[0], xp, __builtin_fmaf(ld[1], yp, ld[2]));
-                    const float d1 = __builtin_fmaf(ld[3], xp, __builtin_fmaf(ld[4], yp, ld[5]));
-                    const float d2 = __builtin_fmaf(ld[6], xp, __builtin_fmaf(ld[7], yp, ld[8]));
-                    keep = in_range && !(fminf(fminf(d0, d1), d2) < far_t);
-                }
-            } else if (in_range && use_far) {
-                float w0, w1, w2;
-                barycentric(rec, pix_center_p2(xi, IS, inv_is, pow2), pix_center_p2(IS - 1 - row, IS, inv_is, pow2), w0, w1, w2);
-                keep = !certainly_far(rec, w0, w1, w2, thr_pad);
+            if (use_far) {
+                const float xp = __builtin_fmaf((float)xi, cx_a, cx_b), yp = __builtin_fmaf((float)row, -cx_a, cy_b);
+                const float d0 = __builtin_fmaf(ld[0], xp, __builtin_fmaf(ld[1], yp, ld[2]));
+                const float d1 = __builtin_fmaf(ld[3], xp, __builtin_fmaf(ld[4], yp, ld[5]));
+                const float d2 = __builtin_fmaf(ld[6], xp, __builtin_fmaf(ld[7], yp, ld[8]));
+                keep = in_range && !(fminf(fminf(d0, d1), d2) < far_t);
             }
             const unsigned long long mask = wave_mask(keep);
             if (keep) ring[(tail + bits_below_lane(mask)) & (QCAP - 1)] = (unsigned)xi | ((unsigned)row << 16);
@@ -281,21 +211,11 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
 
         float w0, w1, w2;
         Frag fr;
-#if LASR_BWD_ONE
-        // (wave-uniform choice: the face's flags)
+        // (wave-uniform choice: the face's flags) one edge projection per pixel for well-conditioned faces (sr_device.h: euclid_one_ext)
         if (LASR_FAST && (flags & 16)) {
-#if LASR_BWD_LDSREC
-#if LASR_BWD_TBL || LASR_BWD_ONEPROJ
             if (!fragment_one_ext(lrec, lrec + REC, flags, A.thr, A.sigma, xp, yp, w0, w1, w2, fr, tie_scale)) continue;
-#else
-            if (!fragment_one(lrec, A.thr, A.sigma, xp, yp, w0, w1, w2, fr, tie_scale)) continue;
-#endif
-#else
-            if (!fragment_one(rec, A.thr, A.sigma, xp, yp, w0, w1, w2, fr, tie_scale)) continue;
-#endif
         } else
-#endif
-        if (!fragment<FM, cptr_t, (OPT_BWD_MATH && LASR_FAST)>(rec, m.dist, A.thr, A.sigma, xp, yp, w0, w1, w2, fr)) continue;
+        if (!fragment<FM, cptr_t, LASR_FAST>(rec, m.dist, A.thr, A.sigma, xp, yp, w0, w1, w2, fr)) continue;
         const float D = fr.D;
 #if defined(LASR_BWD_ABL) && LASR_BWD_ABL == 2       // measurement build: + the distance code, nothing after it (no plane loads)
         gv[0] += D + fr.dx + fr.dy + fr.t0 + fr.t1 + fr.t2 + fr.sign;
@@ -313,11 +233,11 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
 
         const float u0 = w0, u1 = w1, u2 = w2;       // unclipped barycentrics (w0 of K.cu:596)
         // surface sampling picks a texel from (int)(w * res): keep the exact division there
-        if (vertex_tex) clip_normalise<FM, (OPT_BWD_MATH && LASR_FAST)>(w0, w1, w2); else clip_normalise<false>(w0, w1, w2);
+        if (vertex_tex) clip_normalise<FM, LASR_FAST>(w0, w1, w2); else clip_normalise<false>(w0, w1, w2);
         // (the record holds the correctly rounded 1 / z_k: no v_rcp per fragment)
         const float iz0r = rec[R_IZ + 0], iz1r = rec[R_IZ + 1], iz2r = rec[R_IZ + 2];
         const float q0 = w0 * iz0r, q1 = w1 * iz1r, q2 = w2 * iz2r;
-        const float zp = OPT_BWD_MATH && LASR_FAST ? __builtin_amdgcn_rcpf(q0 + q1 + q2) : depth_at<FM>(rec, w0, w1, w2);
+        const float zp = LASR_FAST ? __builtin_amdgcn_rcpf(q0 + q1 + q2) : depth_at<FM>(rec, w0, w1, w2);
         if (!depth_safe) {
             // K.cu:599: no gradient at all for a fragment the forward pass depth-culled.  The fast-math depth decides unless it
             // lies within 1e-4 relative of a plane; then the forward's own arithmetic is re-run so both passes agree.
@@ -379,7 +299,7 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
             Crgb *= sm;
             C += div_<FM>(Crgb, D);
             const float Cz = div_<FM>(div_<FM>(Crgb, A.gamma), A.near - A.far) * zp * zp;
-            if (OPT_BWD_MATH && LASR_FAST) {
+            if (LASR_FAST) {
                 gz0 = Cz * q0 * iz0r; gz1 = Cz * q1 * iz1r; gz2 = Cz * q2 * iz2r;       // q_k = w_k / z_k
             } else {
                 const float iz0 = __builtin_amdgcn_rcpf(rec[R_FACE + 2]), iz1 = __builtin_amdgcn_rcpf(rec[R_FACE + 5]), iz2 = __builtin_amdgcn_rcpf(rec[R_FACE + 8]);

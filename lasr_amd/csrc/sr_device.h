@@ -43,21 +43,6 @@ namespace lasr {
 //         [44..47] padding
 constexpr int REC = 48;
 
-// Round-4 instruction-mix options (profiles/r04_opt_ab.txt has the A/B of each bit; every one leaves the forward's output
-// bit-identical -- the kernel-choice, reference-vector and oracle suites run with all of them on).  Measurement builds switch
-// bits off: make variant NAME=x DEFS=-DLASR_OPT=<mask>.
-#ifndef LASR_OPT
-#define LASR_OPT 0xffff
-#endif
-constexpr bool OPT_PKRECT = (LASR_OPT & 1) != 0;      // rect test as one packed u16 compare
-constexpr bool OPT_MED3 = (LASR_OPT & 2) != 0;        // clamps / inside test as v_med3 / v_min3 / v_max3 on tame records
-constexpr bool OPT_NOSCALE = (LASR_OPT & 4) != 0;     // 1/x and the f64 sigmoid division without v_div_scale / v_div_fixup
-constexpr bool OPT_SIGNFOLD = (LASR_OPT & 8) != 0;    // threshold cut inside the outside branch, no float sign
-constexpr bool OPT_SOFTMAX = (LASR_OPT & 16) != 0;    // depth-softmax update with -|zn - smax| and v_max
-// (bit 32, the backward's pixel planes through buffer descriptors, was measured slower and removed)
-constexpr bool OPT_BWD_S1 = (LASR_OPT & 64) != 0;     // backward stage 1: branch-free conservative reject, fused centres
-constexpr bool OPT_BWD_MATH = (LASR_OPT & 128) != 0;
-constexpr bool OPT_EDGESEL = (LASR_OPT & 256) != 0;   // which edge an outside pixel projects to: lane-mask algebra, not a nested if chain  // backward stage 2: record reciprocals, med3, per-face depth-range test
 constexpr int R_BB = 0, R_FLAGS = 2, R_INV = 3, R_HK2 = 12, R_FACE = 16, R_DEN = 25, R_IDEN = 28, R_TIE = 31, R_E = 32, R_IZ = 41;
 
 // Read-only buffers written by an EARLIER kernel are viewed through the constant address
@@ -151,13 +136,9 @@ __device__ __forceinline__ float max_finite(float a, float b)
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ bool rect_has(int lo, int ext, int pxy)
 {
-    if (OPT_PKRECT) {
-        const u16x2_t d = __builtin_bit_cast(u16x2_t, pxy) - __builtin_bit_cast(u16x2_t, lo);
-        const u16x2_t m = __builtin_elementwise_min(d, __builtin_bit_cast(u16x2_t, ext));
-        return __builtin_bit_cast(int, m) == __builtin_bit_cast(int, d);
-    }
-    const int px = pxy & 0xffff, py = (unsigned)pxy >> 16, x0 = lo & 0xffff, r0 = (unsigned)lo >> 16;
-    return px >= x0 && px <= x0 + (ext & 0xffff) && py >= r0 && py <= r0 + (int)((unsigned)ext >> 16);
+    const u16x2_t d = __builtin_bit_cast(u16x2_t, pxy) - __builtin_bit_cast(u16x2_t, lo);
+    const u16x2_t m = __builtin_elementwise_min(d, __builtin_bit_cast(u16x2_t, ext));
+    return __builtin_bit_cast(int, m) == __builtin_bit_cast(int, d);
 }
 
 // Pixel-index bounds equivalent to the float test `lo <= pix_center(i) <= hi` (pix_center is monotone in i):
@@ -372,16 +353,6 @@ template <bool FM, bool NOSCALE = false> __device__ __forceinline__ float sigmoi
     return (float)(1. / (1. + (double)exp_1ulp(neg_arg)));   // K.cu:397,403 promote this to double
 }
 
-// Conservative reject for the compaction stages: true only if the pixel is certainly farther than
-// sqrt(thr) from the face (so the reference's `dis >= threshold` test would skip it as well).
-template <typename RP>
-__device__ __forceinline__ bool certainly_far(RP rec, float w0, float w1, float w2, float thr_pad)
-{
-    return (w0 < 0.f && w0 * w0 * rec[R_HK2 + 0] > thr_pad) ||
-           (w1 < 0.f && w1 * w1 * rec[R_HK2 + 1] > thr_pad) ||
-           (w2 < 0.f && w2 * w2 * rec[R_HK2 + 2] > thr_pad);
-}
-
 // One edge projection with compile-time edge K (a=K, b=K+1, c=K+2 mod 3): K.cu:85-95 / 136-148.
 // Returns u (already minus w) in (u0,u1,u2).  CLAMP selects the outside-branch variant.
 template <int K, bool CLAMP, bool FM = false, bool MK = false, typename RP = cptr_t, bool IDEN = false>
@@ -449,43 +420,23 @@ __device__ __forceinline__ bool euclid(RP rec, float xp, float yp,
     } else {
         const int flags = __float_as_int(rec[R_FLAGS]);
         float u0, u1, u2;
-        if (OPT_EDGESEL) {
-            // K.cu:113-125 as lane-mask algebra instead of a nested if chain (which the compiler turns into a dozen exec-mask
-            // regions per entry): which edge a pixel outside the face projects to follows from the sign pattern of its
-            // barycentrics, with the obtuse-corner override; every lane takes exactly one of the three projections
-            const bool n0 = w0 <= 0, n1 = w1 <= 0, n2 = w2 <= 0;
-            bool o0 = false, o1 = false, o2 = false;                 // at most one corner of a face is obtuse (wave-uniform flags)
-            if (flags & 7) {
-                if (flags & 1) o0 = (xp - x0) * (x2 - x0) + (yp - y0) * (y2 - y0) > 0;
-                if (flags & 2) o1 = (xp - x1) * (x0 - x1) + (yp - y1) * (y0 - y1) > 0;
-                if (flags & 4) o2 = (xp - x2) * (x1 - x2) + (yp - y2) * (y1 - y2) > 0;
-            }
-            const bool c12 = n1 & n2, c20 = n2 & n0 & !n1, c01 = n0 & n1 & !n2;        // two (or three) non-positive: a corner region
-            const bool e1 = (c20 & !o1) | (c01 & o2) | (n0 & !n1 & !n2);
-            const bool e2 = (c01 & !o2) | (c12 & o0) | (n1 & !n0 & !n2);
-            const bool e0 = !(e1 | e2);             // incl. "none <= 0" (the reference indexes [-1] there: UB; pinned to edge 0 like the oracle)
-            if (e0) edge_project<0, true, FM, MK, RP, IDEN>(rec, w0, w1, w2, u0, u1, u2);
-            if (e1) edge_project<1, true, FM, MK, RP, IDEN>(rec, w0, w1, w2, u0, u1, u2);
-            if (e2) edge_project<2, true, FM, MK, RP, IDEN>(rec, w0, w1, w2, u0, u1, u2);
-        } else {
-        int a = -1;
-        if (w1 <= 0 && w2 <= 0) {
-            a = 0;
-            if ((flags & 1) && (xp - x0) * (x2 - x0) + (yp - y0) * (y2 - y0) > 0) a = 2;
-        } else if (w2 <= 0 && w0 <= 0) {
-            a = 1;
-            if ((flags & 2) && (xp - x1) * (x0 - x1) + (yp - y1) * (y0 - y1) > 0) a = 0;
-        } else if (w0 <= 0 && w1 <= 0) {
-            a = 2;
-            if ((flags & 4) && (xp - x2) * (x1 - x2) + (yp - y2) * (y1 - y2) > 0) a = 1;
-        } else if (w0 <= 0) a = 1;
-        else if (w1 <= 0) a = 2;
-        else if (w2 <= 0) a = 0;
-        if (a < 0) a = 0;   // reference indexes [-1] here (UB); pinned to edge 0 like the oracle
-        if (a == 0) edge_project<0, true, FM, MK, RP, IDEN>(rec, w0, w1, w2, u0, u1, u2);
-        else if (a == 1) edge_project<1, true, FM, MK, RP, IDEN>(rec, w0, w1, w2, u0, u1, u2);
-        else edge_project<2, true, FM, MK, RP, IDEN>(rec, w0, w1, w2, u0, u1, u2);
+        // K.cu:113-125 as lane-mask algebra instead of a nested if chain (which the compiler turns into a dozen exec-mask
+        // regions per entry): which edge a pixel outside the face projects to follows from the sign pattern of its
+        // barycentrics, with the obtuse-corner override; every lane takes exactly one of the three projections
+        const bool n0 = w0 <= 0, n1 = w1 <= 0, n2 = w2 <= 0;
+        bool o0 = false, o1 = false, o2 = false;                 // at most one corner of a face is obtuse (wave-uniform flags)
+        if (flags & 7) {
+            if (flags & 1) o0 = (xp - x0) * (x2 - x0) + (yp - y0) * (y2 - y0) > 0;
+            if (flags & 2) o1 = (xp - x1) * (x0 - x1) + (yp - y1) * (y0 - y1) > 0;
+            if (flags & 4) o2 = (xp - x2) * (x1 - x2) + (yp - y2) * (y1 - y2) > 0;
         }
+        const bool c12 = n1 & n2, c20 = n2 & n0 & !n1, c01 = n0 & n1 & !n2;        // two (or three) non-positive: a corner region
+        const bool e1 = (c20 & !o1) | (c01 & o2) | (n0 & !n1 & !n2);
+        const bool e2 = (c01 & !o2) | (c12 & o0) | (n1 & !n0 & !n2);
+        const bool e0 = !(e1 | e2);             // incl. "none <= 0" (the reference indexes [-1] there: UB; pinned to edge 0 like the oracle)
+        if (e0) edge_project<0, true, FM, MK, RP, IDEN>(rec, w0, w1, w2, u0, u1, u2);
+        if (e1) edge_project<1, true, FM, MK, RP, IDEN>(rec, w0, w1, w2, u0, u1, u2);
+        if (e2) edge_project<2, true, FM, MK, RP, IDEN>(rec, w0, w1, w2, u0, u1, u2);
         fr.dx = u0 * x0 + u1 * x1 + u2 * x2;
         fr.dy = u0 * y0 + u1 * y1 + u2 * y2;
         if (FWD) { fr.narg = fr.dx * fr.dx + fr.dy * fr.dy; return !(fr.narg >= thr); }
@@ -496,7 +447,7 @@ __device__ __forceinline__ bool euclid(RP rec, float xp, float yp,
 
 // K.cu:113-125 as a table: the edge (0..2) an outside pixel projects to, for the sign pattern idx = n0 + 2 n1 + 4 n2 of its
 // barycentrics (n_k = "w_k <= 0") and `over` = "beyond the face's obtuse corner" (only ever true for the face's one obtuse
-// corner, flags bit0..2).  Same truth table as euclid<>'s and euclid_one's lane-mask algebra; idx 0 ("none <= 0", which the
+// corner, flags bit0..2).  Same truth table as euclid<>'s lane-mask algebra; idx 0 ("none <= 0", which the
 // reference leaves undefined) is pinned to edge 0 like there.  Two bits per case, `over` cases in the high half.
 __host__ __device__ constexpr unsigned edge_table(int obtuse_bits)
 {
@@ -514,7 +465,7 @@ __host__ __device__ constexpr unsigned edge_table(int obtuse_bits)
 }
 
 // the table against the two other statements of the same choice, for all 8 sign patterns x {over, not over} x {no obtuse corner, corner
-// 0, 1, 2}: euclid_one's lane-mask algebra (e0 / e1 / e2, exactly one of them set) and the reference's nested if chain (K.cu:113-125)
+// 0, 1, 2}: euclid<>'s lane-mask algebra (e0 / e1 / e2, exactly one of them set) and the reference's nested if chain (K.cu:113-125)
 __host__ __device__ constexpr bool edge_table_matches()
 {
     for (int v = 0; v < 4; v++) {
@@ -525,7 +476,7 @@ __host__ __device__ constexpr bool edge_table_matches()
                 const int k = (int)((tbl >> (2 * idx + 16 * over)) & 3u);
                 const bool n0 = idx & 1, n1 = idx & 2, n2 = idx & 4;
                 const bool o0 = over && (ob & 1), o1 = over && (ob & 2), o2 = over && (ob & 4);
-                // euclid_one
+                // euclid<>
                 const bool c12 = n1 & n2, c20 = n2 & n0 & !n1, c01 = n0 & n1 & !n2;
                 const bool e1 = (c20 & !o1) | (c01 & o2) | (n0 & !n1 & !n2);
                 const bool e2 = (c01 & !o2) | (c12 & o0) | (n1 & !n0 & !n2);
@@ -547,7 +498,7 @@ __host__ __device__ constexpr bool edge_table_matches()
     }
     return true;
 }
-static_assert(edge_table_matches(), "edge_table disagrees with euclid_one's edge choice");
+static_assert(edge_table_matches(), "edge_table disagrees with euclid<>'s edge choice");
 
 // Well-conditioned faces (flags bit 4), euclidean distance: ONE edge projection per pixel, inside or outside, wherever the choice of
 // the edge is clear.  K.cu:61-110 projects an inside pixel on all three edge LINES (no clamp) and keeps the nearest: that is the
@@ -558,7 +509,7 @@ static_assert(edge_table_matches(), "edge_table disagrees with euclid_one's edge
 // is evaluated -- by the same instructions on the
 // same barycentrics as edge_project<k>, hence with the bits the three-projection form gives for that edge.  The clamp of the
 // outside branch is a no-op for an inside pixel (the foot of the perpendicular on the nearest line lies on the triangle's
-// boundary), so both kinds of pixel share the three exec-masked projections.  Inside pixels near a bisector take the reference's
+// boundary), so both kinds of pixel share the one projection (euclid_one_ext below).  Inside pixels near a bisector take the reference's
 // three projections (a region most batches skip).  Why: in the bench launch 15 % of the surviving pixels of a face are inside and
 // nearly every batch holds some -- the three-projection branch ran for every batch at ~10 live lanes.
 constexpr float NEAR_TIE = 0.985f;
@@ -579,81 +530,10 @@ __device__ __forceinline__ bool near_tie(float qlo, float qmid, float scale)
     const float gap = qmid - qlo;
     return (bool)((int)!(qlo < NEAR_TIE * qmid) | (int)!(gap * gap > scale * qmid));
 }
-#ifndef LASR_BWD_FMA
-#define LASR_BWD_FMA 0
-#endif
-// edge_project<K, CLAMP = true, FM = true, IDEN = true> for the backward's single projection; with LASR_BWD_FMA its multiply-add
-// pairs may fuse (the translation unit's -ffp-contract=fast): a well-conditioned face's distance moves by ~1e-6 relative
-template <int K, typename RP>
-__device__ __forceinline__ void edge_project_one(RP rec, float w0, float w1, float w2, float& u0, float& u1, float& u2)
-{
-#if !LASR_BWD_FMA
-#pragma clang fp contract(off)
-#endif
-    constexpr int B = (K + 1) % 3;
-    const float num = w0 * rec[R_E + 3 * K + 0] + w1 * rec[R_E + 3 * K + 1] + w2 * rec[R_E + 3 * K + 2] - rec[R_E + 3 * K + B];
-    float ta = num * rec[R_IDEN + K];
-    float tb = 1 - ta;
-    ta = fminf(fmaxf(ta, 0.f), 1.f);
-    tb = fminf(fmaxf(tb, 0.f), 1.f);
-    float t[3];
-    t[K] = ta; t[B] = tb; t[(K + 2) % 3] = 0;
-    u0 = t[0] - w0; u1 = t[1] - w1; u2 = t[2] - w2;
-}
-template <typename RP>
-__device__ __forceinline__ void euclid_one(RP rec, float xp, float yp, float w0, float w1, float w2, Frag& fr, float tie_scale)
-{
-#if !LASR_BWD_FMA
-#pragma clang fp contract(off)   // see edge_project
-#endif
-    const float x0 = rec[R_FACE + 0], y0 = rec[R_FACE + 1], x1 = rec[R_FACE + 3], y1 = rec[R_FACE + 4], x2 = rec[R_FACE + 6], y2 = rec[R_FACE + 7];
-    const bool inside = (bool)((int)(fminf(fminf(w0, w1), w2) > 0) & (int)(fmaxf(fmaxf(w0, w1), w2) < 1));
-    const int flags = __float_as_int(rec[R_FLAGS]);
-    const bool n0 = w0 <= 0, n1 = w1 <= 0, n2 = w2 <= 0;
-    bool o0 = false, o1 = false, o2 = false;
-    if (flags & 7) {
-        if (flags & 1) o0 = (xp - x0) * (x2 - x0) + (yp - y0) * (y2 - y0) > 0;
-        if (flags & 2) o1 = (xp - x1) * (x0 - x1) + (yp - y1) * (y0 - y1) > 0;
-        if (flags & 4) o2 = (xp - x2) * (x1 - x2) + (yp - y2) * (y1 - y2) > 0;
-    }
-    const bool c12 = n1 & n2, c20 = n2 & n0 & !n1, c01 = n0 & n1 & !n2;
-    bool e1 = (c20 & !o1) | (c01 & o2) | (n0 & !n1 & !n2);
-    bool e2 = (c01 & !o2) | (c12 & o0) | (n1 & !n0 & !n2);
-    // inside: edge k (from vertex k to k + 1, edge_project<k>) is the one opposite vertex (k + 2) % 3, at distance w_{k+2} h_{k+2}
-    const float q0 = w2 * w2 * rec[R_HK2 + 2], q1 = w0 * w0 * rec[R_HK2 + 0], q2 = w1 * w1 * rec[R_HK2 + 1];   // edge 0, 1, 2
-    const float qlo = fminf(fminf(q0, q1), q2), qmid = __builtin_amdgcn_fmed3f(q0, q1, q2);
-    const bool tie = (bool)((int)inside & (int)near_tie(qlo, qmid, tie_scale));
-    float u0, u1, u2;
-    if (tie) {
-        float best = 100000000.f, bx = 0, by = 0, b0 = 0, b1 = 0, b2 = 0;
-#define LASR_TRY_EDGE(K)                                                          \
-        edge_project<K, false, true, false, RP, true>(rec, w0, w1, w2, u0, u1, u2);   \
-        {                                                                         \
-            const float px = u0 * x0 + u1 * x1 + u2 * x2;                         \
-            const float py = u0 * y0 + u1 * y1 + u2 * y2;                         \
-            const float d2 = px * px + py * py;                                   \
-            if (d2 < best) { best = d2; bx = px; by = py; b0 = u0; b1 = u1; b2 = u2; } \
-        }
-        LASR_TRY_EDGE(0) LASR_TRY_EDGE(1) LASR_TRY_EDGE(2)
-#undef LASR_TRY_EDGE
-        fr.dx = bx; fr.dy = by; u0 = b0; u1 = b1; u2 = b2;
-    } else {
-        const bool i1 = q1 == qlo, i2 = q2 == qlo;      // (clear of a tie: exactly one)
-        e1 = inside ? i1 : e1;
-        e2 = inside ? i2 : e2;
-        const bool e0 = !(e1 | e2);
-        if (e0) edge_project_one<0>(rec, w0, w1, w2, u0, u1, u2);
-        if (e1) edge_project_one<1>(rec, w0, w1, w2, u0, u1, u2);
-        if (e2) edge_project_one<2>(rec, w0, w1, w2, u0, u1, u2);
-        fr.dx = u0 * x0 + u1 * x1 + u2 * x2;
-        fr.dy = u0 * y0 + u1 * y1 + u2 * y2;
-    }
-    fr.t0 = u0; fr.t1 = u1; fr.t2 = u2; fr.sign = inside ? 1.f : -1.f;
-}
 
-// ---- euclid_one on the backward's extended LDS record (sr_backward.h: the wave's slot holds the record and, behind it, BX floats
-// written once per face).  Same operations on the same operands in the same order per pixel as euclid_one; what changes is how
-// the wave gets there:
+// ---- the one-projection distance on the backward's extended LDS record (sr_backward.h: the wave's slot holds the record and, behind
+// it, BX floats written once per face).  Per pixel the same operations on the same operands in the same order as euclid<>'s clamped
+// projection of the chosen edge; how the wave gets there (profiles/r08_backward_edge_ab.txt):
 //   * which edge an outside pixel projects to comes from edge_table (the word is chosen per face on the scalar side);
 //   * the obtuse-corner test runs once, on operands prepared per face (x_c, y_c, x_o - x_c, y_o - y_c: the difference is the one
 //     fp32 subtraction of the inline form), and only when the face's SCALAR flags name an obtuse corner;
@@ -661,38 +541,14 @@ __device__ __forceinline__ void euclid_one(RP rec, float xp, float yp, float w0,
 // Layout of the extension, floats, block k = 0..2 at 16 k:
 //   [0..3] e[k][0..2], e[k][(k+1)%3]   [4] 1 / den[k]   [5..7] (k == 0, k == 1, k == 2)   [8..10] ((k+1)%3 == 0, == 1, == 2) as 0 / 1
 //   [12..15] of block 0: the obtuse corner's operands
-#ifndef LASR_BWD_TBL
-#define LASR_BWD_TBL 1          // edge choice from edge_table, obtuse test on prepared operands
-#endif
-#ifndef LASR_BWD_ONEPROJ
-#define LASR_BWD_ONEPROJ 1      // one projection at a run-time offset
-#endif
-#ifndef LASR_BWD_TSEL
-#define LASR_BWD_TSEL 0         // the t[] permutation: 0 = exact 0 / 1 factors from the block, 1 = selects
-#endif
 constexpr int BX = 64, BX_STRIDE = 16, BX_OBT = 12;
 typedef float f4_t __attribute__((ext_vector_type(4)));
 typedef const float __attribute__((address_space(3)))* lds_cptr_t;
 typedef const f4_t __attribute__((address_space(3)))* lds_c4ptr_t;
-// the value lane L (0..63) of the wave stores at word L of the extension: two loads from the face's record `f` (global) per lane
-__device__ __forceinline__ float bwd_ext_word(const float* __restrict__ f, int flags, int L)
-{
-    const int k = L >> 4, i = L & 15;
-    const int c = (flags & 1) ? 0 : (flags & 2) ? 1 : 2, o = c == 0 ? 2 : c - 1;       // scalar: the obtuse corner and its far neighbour
-    const bool obt = L >= BX_OBT && L < BX_OBT + 4;
-    int ia = i < 3 ? R_E + 3 * k + i : i == 3 ? (k == 2 ? R_E + 6 : R_E + 4 * k + 1) : R_IDEN + k;
-    ia = obt ? R_FACE + 3 * ((L & 2) ? o : c) + (L & 1) : ia;
-    const int ib = R_FACE + 3 * c + (L & 1);
-    const float a = f[ia], b = f[ib];
-    float v = (obt && (L & 2)) ? a - b : a;
-    const int kb = k == 2 ? 0 : k + 1;
-    if (i >= 5 && i < 8) v = (i - 5 == k) ? 1.f : 0.f;
-    if (i >= 8 && i < 11) v = (i - 8 == kb) ? 1.f : 0.f;
-    return v;
-}
-// The same word by a TABLE: where lane L's value comes from does not depend on the face, except for the obtuse corner's operands
-// in lanes 12..15, so the index arithmetic above (~40 half-rate integer / compare / select instructions in every wave) becomes one
-// 2-byte load per lane that does not wait for the record.  Entry: bits 0..5 a record word; BXT_ONE / BXT_ZERO: the value is the
+// The value lane L (0..63) of the wave stores at word L of the extension, by a TABLE: where it comes from does not depend on the face,
+// except for the obtuse corner's operands in lanes 12..15, so per-lane index arithmetic (~40 half-rate integer / compare / select
+// instructions in every wave; profiles/r09_face_constants_ab.txt) becomes one 2-byte load per lane that does not wait for the record.
+// Entry: bits 0..5 a record word; BXT_ONE / BXT_ZERO: the value is the
 // constant 1 / 0 (the word is not used); BXT_C: add the obtuse corner's base R_FACE + 3 c; BXT_O: add its far neighbour's base
 // R_FACE + 3 o, and the value is that word MINUS the corner's (word R_FACE + 3 c + (L & 1)): the one fp32 subtraction x_o - x_c.
 constexpr int BXT_ONE = 0x40, BXT_ZERO = 0x80, BXT_C = 0x100, BXT_O = 0x200;
@@ -702,7 +558,8 @@ static __constant__ constexpr unsigned short k_bwd_ext_tbl[BX] = {
     0x026, 0x027, 0x028, 0x026, 0x01e, 0x09e, 0x09e, 0x05e, 0x05e, 0x09e, 0x09e, 0x01e, 0x01e, 0x01e, 0x01e, 0x01e,
     0x029, 0x02a, 0x02b, 0x02d, 0x01f, 0x09f, 0x09f, 0x09f, 0x09f, 0x09f, 0x09f, 0x01f, 0x01f, 0x01f, 0x01f, 0x01f
 };
-// bwd_ext_word's index arithmetic, restated: (record word, subtract the corner's word, constant: -1 none / 0 / 1) packed in an int
+// What defines k_bwd_ext_tbl: the layout above as index arithmetic (bwd_ext_formula) and the table's decoding (bwd_ext_decode), each as
+// (record word, subtract the corner's word, constant: -1 none / 0 / 1) packed in an int
 __host__ __device__ constexpr int bwd_ext_formula(int L, int c)
 {
     const int k = L >> 4, i = L & 15, o = c == 0 ? 2 : c - 1, kb = k == 2 ? 0 : k + 1;
@@ -729,7 +586,7 @@ __host__ __device__ constexpr bool bwd_ext_tbl_matches()
         }
     return true;
 }
-static_assert(bwd_ext_tbl_matches(), "k_bwd_ext_tbl disagrees with bwd_ext_word's index arithmetic");
+static_assert(bwd_ext_tbl_matches(), "k_bwd_ext_tbl disagrees with the extension's layout (bwd_ext_formula)");
 // t: the lane's table entry (k_bwd_ext_tbl[L], loaded by the caller before the record's flags arrive)
 __device__ __forceinline__ float bwd_ext_word_tbl(const float* __restrict__ f, int flags, int L, int t)
 {
@@ -749,9 +606,7 @@ __host__ __device__ constexpr unsigned edge_table_of_flags(int flags)
 __device__ __forceinline__ void euclid_one_ext(lds_cptr_t rec, lds_cptr_t ext, int flags, float xp, float yp, float w0, float w1, float w2,
                                                Frag& fr, float tie_scale)
 {
-#if !LASR_BWD_FMA
 #pragma clang fp contract(off)   // see edge_project
-#endif
     const float x0 = rec[R_FACE + 0], y0 = rec[R_FACE + 1], x1 = rec[R_FACE + 3], y1 = rec[R_FACE + 4], x2 = rec[R_FACE + 6], y2 = rec[R_FACE + 7];
     const bool inside = (bool)((int)(fminf(fminf(w0, w1), w2) > 0) & (int)(fmaxf(fmaxf(w0, w1), w2) < 1));
     // inside: edge k (from vertex k to k + 1) is the one opposite vertex (k + 2) % 3, at distance w_{k+2} h_{k+2}
@@ -773,7 +628,6 @@ __device__ __forceinline__ void euclid_one_ext(lds_cptr_t rec, lds_cptr_t ext, i
 #undef LASR_TRY_EDGE
         fr.dx = bx; fr.dy = by; u0 = b0; u1 = b1; u2 = b2;
     } else {
-#if LASR_BWD_TBL
         // an inside pixel (clear of a tie: exactly one of q0, q1, q2 is the smallest) has no barycentric <= 0, which the table pins to
         // edge 0 whatever `over` says: its own edge is OR-ed in, no select between the two kinds of pixel
         const bool i1 = (bool)((int)inside & (int)(q1 == qlo)), i2 = (bool)((int)inside & (int)(q2 == qlo));
@@ -784,24 +638,7 @@ __device__ __forceinline__ void euclid_one_ext(lds_cptr_t rec, lds_cptr_t ext, i
         }
         const int sh = (w0 <= 0 ? 2 : 0) | (w1 <= 0 ? 4 : 0) | (w2 <= 0 ? 8 : 0) | (over ? 16 : 0);
         const int k = (int)__builtin_amdgcn_ubfe(edge_table_of_flags(flags), (unsigned)sh, 2u) | (i1 ? 1 : 0) | (i2 ? 2 : 0);
-#else
-        const bool i1 = q1 == qlo, i2 = q2 == qlo;      // (clear of a tie: exactly one of q0, q1, q2)
-        const bool n0 = w0 <= 0, n1 = w1 <= 0, n2 = w2 <= 0;
-        bool o0 = false, o1 = false, o2 = false;
-        if (flags & 7) {
-            if (flags & 1) o0 = (xp - x0) * (x2 - x0) + (yp - y0) * (y2 - y0) > 0;
-            if (flags & 2) o1 = (xp - x1) * (x0 - x1) + (yp - y1) * (y0 - y1) > 0;
-            if (flags & 4) o2 = (xp - x2) * (x1 - x2) + (yp - y2) * (y1 - y2) > 0;
-        }
-        const bool c12 = n1 & n2, c20 = n2 & n0 & !n1, c01 = n0 & n1 & !n2;
-        bool e1 = (c20 & !o1) | (c01 & o2) | (n0 & !n1 & !n2);
-        bool e2 = (c01 & !o2) | (c12 & o0) | (n1 & !n0 & !n2);
-        e1 = inside ? i1 : e1;
-        e2 = inside ? i2 : e2;
-        const int k = e2 ? 2 : e1 ? 1 : 0;
-#endif
-#if LASR_BWD_ONEPROJ
-        // edge_project_one's body on the lane's own block
+        // the clamped projection of edge k (edge_project<k, CLAMP = true, FM = true, IDEN = true>) on the lane's own block
         const lds_cptr_t E = ext + BX_STRIDE * k;
         const f4_t ea = *(lds_c4ptr_t)E;
         const float num = w0 * ea.x + w1 * ea.y + w2 * ea.z - ea.w;
@@ -809,19 +646,10 @@ __device__ __forceinline__ void euclid_one_ext(lds_cptr_t rec, lds_cptr_t ext, i
         float tb = 1 - ta;
         ta = fminf(fmaxf(ta, 0.f), 1.f);
         tb = fminf(fmaxf(tb, 0.f), 1.f);
-#if LASR_BWD_TSEL
-        const float t0 = k == 0 ? ta : k == 2 ? tb : 0.f, t1 = k == 1 ? ta : k == 0 ? tb : 0.f, t2 = k == 2 ? ta : k == 1 ? tb : 0.f;
-#else
         // t[k] = ta, t[(k + 1) % 3] = tb, the third 0, by exact 0 / 1 factors (ta, tb lie in [0, 1]: every product and sum is exact)
         const f4_t fa = *(lds_c4ptr_t)(E + 4), fb = *(lds_c4ptr_t)(E + 8);
         const float t0 = __builtin_fmaf(tb, fb.x, ta * fa.y), t1 = __builtin_fmaf(tb, fb.y, ta * fa.z), t2 = __builtin_fmaf(tb, fb.z, ta * fa.w);
-#endif
         u0 = t0 - w0; u1 = t1 - w1; u2 = t2 - w2;
-#else
-        if (k == 0) edge_project_one<0>(rec, w0, w1, w2, u0, u1, u2);
-        if (k == 1) edge_project_one<1>(rec, w0, w1, w2, u0, u1, u2);
-        if (k == 2) edge_project_one<2>(rec, w0, w1, w2, u0, u1, u2);
-#endif
         fr.dx = u0 * x0 + u1 * x1 + u2 * x2;
         fr.dy = u0 * y0 + u1 * y1 + u2 * y2;
     }
@@ -867,50 +695,24 @@ __device__ __forceinline__ bool fragment_w(RP rec, int dist, float thr, float si
         fr.dis = d; fr.t0 = w0; fr.t1 = w1; fr.t2 = w2;
         if (-d >= thr) return false;
         fr.D = sigmoid_neg_<FM>(MK ? div_by_recip(-d, sigma, inv_sigma) : div_<FM>(-d, sigma));
-    } else if (!FM && MK && OPT_SIGNFOLD) {
-        if (!euclid<FM, MK, RP, true, OPT_MED3>(rec, xp, yp, w0, w1, w2, fr, thr)) return false;
-        fr.D = sigmoid_neg_<FM, OPT_NOSCALE>(div_by_recip(fr.narg, sigma, inv_sigma));
+    } else if (!FM && MK) {
+        if (!euclid<FM, MK, RP, true, true>(rec, xp, yp, w0, w1, w2, fr, thr)) return false;
+        fr.D = sigmoid_neg_<FM, true>(div_by_recip(fr.narg, sigma, inv_sigma));
     } else {
-        euclid<FM, MK, RP, false, (!FM && MK && OPT_MED3) || BT, BT>(rec, xp, yp, w0, w1, w2, fr);
+        euclid<FM, MK, RP, false, (!FM && MK) || BT, BT>(rec, xp, yp, w0, w1, w2, fr);
         fr.dis = fr.dx * fr.dx + fr.dy * fr.dy;
         if (fr.sign < 0 && fr.dis >= thr) return false;
-        fr.D = sigmoid_neg_<FM, (!FM && MK && OPT_NOSCALE)>(MK ? div_by_recip(-fr.sign * fr.dis, sigma, inv_sigma) : div_<FM>(-fr.sign * fr.dis, sigma));
+        fr.D = sigmoid_neg_<FM, (!FM && MK)>(MK ? div_by_recip(-fr.sign * fr.dis, sigma, inv_sigma) : div_<FM>(-fr.sign * fr.dis, sigma));
     }
     return true;
 }
 
-// fragment<FM = true, .., BT = true> for a well-conditioned face in the euclidean mode, on euclid_one
-template <typename RP>
-__device__ __forceinline__ bool fragment_one(RP rec, float thr, float sigma, float xp, float yp, float& w0, float& w1, float& w2, Frag& fr,
-                                             float tie_scale)
-{
-#if LASR_BWD_FMA
-    w0 = rec[R_INV + 0] * xp + rec[R_INV + 1] * yp + rec[R_INV + 2];   // K.cu:24-29, contractable
-    w1 = rec[R_INV + 3] * xp + rec[R_INV + 4] * yp + rec[R_INV + 5];
-    w2 = rec[R_INV + 6] * xp + rec[R_INV + 7] * yp + rec[R_INV + 8];
-#else
-#pragma clang fp contract(off)   // see edge_project
-    barycentric(rec, xp, yp, w0, w1, w2);
-#endif
-    euclid_one(rec, xp, yp, w0, w1, w2, fr, tie_scale);
-    fr.dis = fr.dx * fr.dx + fr.dy * fr.dy;
-    if (fr.sign < 0 && fr.dis >= thr) return false;
-    fr.D = sigmoid_neg_<true>(div_<true>(-fr.sign * fr.dis, sigma));
-    return true;
-}
-
-// fragment_one on the backward's extended LDS record (euclid_one_ext)
+// fragment<FM = true, .., BT = true> for a well-conditioned face in the euclidean mode, on the backward's extended LDS record (euclid_one_ext)
 __device__ __forceinline__ bool fragment_one_ext(lds_cptr_t rec, lds_cptr_t ext, int flags, float thr, float sigma, float xp, float yp,
                                                  float& w0, float& w1, float& w2, Frag& fr, float tie_scale)
 {
-#if LASR_BWD_FMA
-    w0 = rec[R_INV + 0] * xp + rec[R_INV + 1] * yp + rec[R_INV + 2];   // K.cu:24-29, contractable
-    w1 = rec[R_INV + 3] * xp + rec[R_INV + 4] * yp + rec[R_INV + 5];
-    w2 = rec[R_INV + 6] * xp + rec[R_INV + 7] * yp + rec[R_INV + 8];
-#else
 #pragma clang fp contract(off)   // see edge_project
     barycentric(rec, xp, yp, w0, w1, w2);
-#endif
     euclid_one_ext(rec, ext, flags, xp, yp, w0, w1, w2, fr, tie_scale);
     fr.dis = fr.dx * fr.dx + fr.dy * fr.dy;
     if (fr.sign < 0 && fr.dis >= thr) return false;
@@ -927,7 +729,7 @@ __device__ __forceinline__ float depth_at(RP rec, float c0, float c1, float c2)
         // tame record: 0 <= c_k <= 1 with sum >= 1e-5-ish and 1e-6 <= z_k <= 1e6, so the sum lies in [1e-11, 3e6]: no scaling
         const float s = div_by_recip(c0, rec[R_FACE + 2], rec[R_IZ + 0]) + div_by_recip(c1, rec[R_FACE + 5], rec[R_IZ + 1]) +
                         div_by_recip(c2, rec[R_FACE + 8], rec[R_IZ + 2]);
-        return OPT_NOSCALE ? recip_noscale(s) : 1.f / s;
+        return recip_noscale(s);
     }
     return div_<FM>(1.f, div_<FM>(c0, rec[R_FACE + 2]) + div_<FM>(c1, rec[R_FACE + 5]) + div_<FM>(c2, rec[R_FACE + 8]));
 }

@@ -142,7 +142,7 @@ __device__ __forceinline__ void coop_tile_body(RasterArgs A, float* __restrict__
         const int fn = __builtin_amdgcn_readfirstlane(base + (int)s_list[e]);
         const cptr_t rec = as_const(recs + (size_t)fn * REC);
         const cptr_t tex = as_const(texs + (size_t)fn * texstride);
-#if LASR_PREFETCH       // the entry's other two record lines and its attribute line in the same round trip as the rect (sr_raster.hip)
+        // the entry's other two record lines and its attribute line in the same round trip as the rect (sr_raster.hip)
         int pf1, pf2, pf3;
         {
             const float* rn = recs + (size_t)fn * REC;
@@ -150,11 +150,8 @@ __device__ __forceinline__ void coop_tile_body(RasterArgs A, float* __restrict__
             asm volatile("s_load_dword %0, %3, 0x40\n\ts_load_dword %1, %3, 0x80\n\ts_load_dword %2, %4, 0x0"
                          : "=&s"(pf1), "=&s"(pf2), "=&s"(pf3) : "s"(rn), "s"(tn) : "memory");
         }
-#endif
         const bool cand = rect_has(__float_as_int(rec[R_BB + 0]), __float_as_int(rec[R_BB + 1]), pxy);
-#if LASR_PREFETCH
         asm volatile("s_waitcnt lgkmcnt(0)" : : "s"(pf1), "s"(pf2), "s"(pf3));
-#endif
         float w0, w1, w2;
         barycentric(rec, xp, yp, w0, w1, w2);
         const bool mk = (__float_as_int(rec[R_FLAGS]) & ok_bit) != 0;     // wave-uniform; ok_bit = U.ok ? 32 : 0 (no branch on U.ok per entry)
@@ -168,10 +165,10 @@ __device__ __forceinline__ void coop_tile_body(RasterArgs A, float* __restrict__
                 s_buf[b][slot][1][lane] = fr.D;
                 float c0 = w0, c1 = w1, c2 = w2;
                 float zp;
-                if (mk) { clip_normalise<false, OPT_MED3>(c0, c1, c2); zp = depth_at<false, true>(rec, c0, c1, c2); }
+                if (mk) { clip_normalise<false, true>(c0, c1, c2); zp = depth_at<false, true>(rec, c0, c1, c2); }
                 else { clip_normalise<false>(c0, c1, c2); zp = depth_at<false, false>(rec, c0, c1, c2); }
                 // (a tame record's NaN depth stands for the reference's 1 / 0 = inf: cut, see forward_face)
-                if (mk && OPT_NOSCALE ? (zp >= A.near && zp <= A.far) : !(zp < A.near || zp > A.far)) {
+                if (mk ? (zp >= A.near && zp <= A.far) : !(zp < A.near || zp > A.far)) {
                     fl |= 2;
                     s_buf[b][slot][2][lane] = mk ? div_by_recip(A.far - zp, fmn, U.inv_fmn) : (A.far - zp) / fmn;
 #pragma unroll
@@ -192,10 +189,10 @@ __device__ __forceinline__ void coop_tile_body(RasterArgs A, float* __restrict__
             if (fl & 2) {
                 const float zn = s_buf[b][slot][2][lane];
                 const bool up = zn > s.smax;
-                const float d = OPT_SOFTMAX ? -fabsf(zn - s.smax) : (up ? s.smax - zn : zn - s.smax);      // see forward_face
+                const float d = -fabsf(zn - s.smax);      // see forward_face
                 const float E = exp_1ulp((fl & 4) ? div_by_recip(d, A.gamma, U.inv_gamma) : d / A.gamma);
                 const float hist = up ? E : 1.f, wgt = up ? D : E * D;
-                s.smax = OPT_SOFTMAX && (fl & 4) ? max_finite(zn, s.smax) : (up ? zn : s.smax);
+                s.smax = (fl & 4) ? max_finite(zn, s.smax) : (up ? zn : s.smax);
                 s.ssum = hist * s.ssum + wgt;
 #pragma unroll
                 for (int k = 0; k < NCH; k++) s.c[k] = hist * s.c[k] + wgt * s_buf[b][slot][3 + k][lane];

@@ -16,7 +16,7 @@
 //            mask -- the entries whose exact integer pixel rect holds its pixel -- and each lane pops its own candidates: record
 //            gathered from LDS, barycentrics, then one bit per (pixel, entry) in one of three per-lane 64-bit masks: INSIDE the
 //            face, OUTSIDE but not certainly beyond the distance threshold (the backward's conservative line-distance reject,
-//            sr_device.h: certainly_far), or SLOW (a record that is not tame: never popped, handled by the generic arithmetic,
+//            sr_backward.h: stage 1), or SLOW (a record that is not tame: never popped, handled by the generic arithmetic,
 //            wave-uniform, at the end of the chunk).  The loop runs as long as its fullest lane, so the candidates are evened
 //            out first: lanes ranked by candidate count (six ballots), rank r partnered with rank 63 - r, the lighter partner
 //            classifies the upper half of the difference at the heavier one's pixel centre and hands the result masks back
@@ -25,7 +25,7 @@
 //            half of the difference from the heavier one's outside mask and folds it into a private partial state;
 //   walk     every lane pops its own masks, inside pairs first, gathers the entry's record from LDS with 16-byte reads and applies
 //            the pair with the arithmetic of forward_face.  Inside and outside pixels share ONE clamped edge projection: an inside
-//            pixel's nearest edge line follows from the three products w_k^2 hk2_k (sr_device.h: euclid_one); only where two
+//            pixel's nearest edge line follows from the three products w_k^2 hk2_k (sr_device.h: euclid_one_ext); only where two
 //            lines are equidistant within 1.5 % or within the face's rounding scale (sr_device.h: near_tie) -- the reference's own
 //            choice is then decided by its rounding -- the reference's
 //            three projections run (a region most iterations skip).  Before: in 43 % of the walk's iterations some lane was
@@ -55,10 +55,7 @@ typedef unsigned long long u64_t;
 // tile: a few lanes hold most of the chunk's pairs and both per-lane loops run as long as their fullest lane.  Dealt, every chunk
 // is a sample of the whole list and its pairs spread over the tile (tools/pair_stats.py: walk iterations -8.9 %, classification
 // -5.7 % on the bench frames).  Bit e of every mask is still lane e's entry, and a chunk's entries are still in ascending face order.
-// LASR_PW_DEAL=0 (a measurement build, make variant) keeps 64 consecutive entries per chunk.
-#ifndef LASR_PW_DEAL
-#define LASR_PW_DEAL 1
-#endif
+// (A/B against 64 consecutive entries per chunk: profiles/r12_chunk_deal_ab.txt.)
 __host__ __device__ constexpr int chunk_count(int count) { return (count + PW_CAP - 1) / PW_CAP; }
 __host__ __device__ constexpr int chunk_size(int count, int nch, int c) { return c < nch ? count / nch + (c < count % nch ? 1 : 0) : 0; }
 __host__ __device__ constexpr int chunk_pos(int nch, int c, int l) { return c + l * nch; }
@@ -115,15 +112,6 @@ struct PairLds {
 };
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *(const float4*)p; }
-// "these values are needed HERE": keeps the compiler from sinking an LDS read to its first use, where the wave would sit out the
-// whole round trip alone -- reads requested together come back together (nothing is emitted)
-#ifndef LASR_PW_FENCE
-#define LASR_PW_FENCE 0
-#endif
-#ifndef LASR_PW_WAVES
-#define LASR_PW_WAVES 0      // no occupancy request: the compiler's own budget (see the kernel below)
-#endif
-#define PW_LANDED(q) asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w))
 
 // the conservative corner cull of the tile kernels on a block of pixels [xlo, xhi] x [ylo, yhi]: false when all four corners lie
 // beyond one edge's line by more than sqrt(thr_cull)
@@ -232,15 +220,12 @@ __device__ __forceinline__ void pair_apply(const RasterArgs& A, const UniRecip& 
 #pragma clang fp contract(off)
     float4 q0 = ld4(R), q1 = ld4(R + 4), q2 = ld4(R + 8);
     float4 q4 = ld4(R + PR_XY), q5 = ld4(R + PR_XY + 4), ob = ld4(R + PR_OBT);      // one LDS round trip for the six quads
-#if LASR_PW_FENCE & 1
-    PW_LANDED(q0); PW_LANDED(q1); PW_LANDED(q2); PW_LANDED(q4); PW_LANDED(q5); PW_LANDED(ob);
-#endif
     const float w0 = q0.x * xp + q0.y * yp + q0.z;                    // K.cu:24-29 (barycentric())
     const float w1 = q0.w * xp + q1.x * yp + q1.y;
     const float w2 = q1.z * xp + q1.w * yp + q2.x;
     const float x0 = q4.x, y0 = q4.y, x1 = q4.z, y1 = q4.w, x2 = q5.x, y2 = q5.y, z0 = q5.z, z1 = q5.w;
     float narg;
-    // which edge: an inside pixel's nearest edge LINE from the three products w^2 hk2 (sr_device.h: euclid_one), an outside pixel's
+    // which edge: an inside pixel's nearest edge LINE from the three products w^2 hk2 (sr_device.h: euclid_one_ext), an outside pixel's
     // from the sign pattern of its barycentrics (K.cu:113-125); inside pixels near an angle bisector -- or of a face that is not
     // well conditioned (hq = 0) -- take the reference's three projections
     bool tie = false;
@@ -305,11 +290,6 @@ __device__ __forceinline__ void pair_apply(const RasterArgs& A, const UniRecip& 
     // K.cu:409-417, (float)((double)a * (1. - (double)D)): a - a D in ONE rounding is that product rounded once -- the same float
     // except where the double rounding of the reference's form shows (about one product in 2^29)
     s.a = __builtin_fmaf(-s.a, D, s.a);
-#if LASR_PW_FENCE & 2
-    PW_LANDED(q6);
-#pragma unroll
-    for (int q = 0; q < (3 * NCH + 3) / 4; q++) PW_LANDED(tq[q]);
-#endif
     // clip / normalise (K.cu:53-58) and depth (K.cu:423) with single-correction quotients (div_by_recip1)
     float c0 = clamp01(w0), c1 = clamp01(w1), c2 = clamp01(w2);
     {
@@ -451,17 +431,9 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
     if (A.near_far_dev) { A.near = A.near_far_dev[0]; A.far = A.near_far_dev[1]; }
     const int tid = threadIdx.x, wave_all = tid >> 6, lane = tid & 63;
     const int team = SPLIT > 1 ? wave_all >> 2 : 0, wave = wave_all & 3;        // wave: within its team (the pixel rows it owns)
-#ifndef LASR_PW_ROWS
-#define LASR_PW_ROWS 1
-#endif
-#if LASR_PW_ROWS
     // wave w takes the rows w, w + 4, w + 8, w + 12 of the tile (16 pixels = 64 bytes each): the four waves of a tile see the same
     // load (they meet at two barriers per chunk), and a store instruction covers whole 64-byte segments
     const int px = tx * PW_TILE + (lane & 15), py = ty * PW_TILE + wave + 4 * (lane >> 4);
-#else
-    const int qx0 = tx * PW_TILE + (wave & 1) * 8, qy0 = ty * PW_TILE + (wave >> 1) * 8;       // this wave's 8x8 quadrant
-    const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
-#endif
     const bool valid = px < IS && py < IS;
     const int pn = py * IS + px;
 
@@ -514,15 +486,10 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
     const UniRecip U = uni_recip(A);
     const int ok_bit = U.ok ? 32 : 0;
     const float thr_cull = A.thr * 1.10f, thr_far = A.thr * 1.05f;
-    // corners of the tile (list building) and of this wave's quadrant (which entries of a chunk the wave looks at); wave-uniform
-    // values the VALU computed (divisions) go back to scalar registers
+    // corners of the tile (list building); wave-uniform values the VALU computed (divisions) go back to scalar registers
     auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
     const float t_xlo = uni(pix_center(tX0, IS)), t_xhi = uni(pix_center(min(tX1, IS - 1), IS));
     const float t_yhi = uni(pix_center(IS - 1 - tY0, IS)), t_ylo = uni(pix_center(IS - 1 - min(tY1, IS - 1), IS));
-#if !LASR_PW_ROWS
-    const float q_xlo = uni(pix_center(qx0, IS)), q_xhi = uni(pix_center(min(qx0 + 7, IS - 1), IS));
-    const float q_yhi = uni(pix_center(IS - 1 - qy0, IS)), q_ylo = uni(pix_center(IS - 1 - min(qy0 + 7, IS - 1), IS));
-#endif
     int g_next = 64, g_mask0 = 0;
     bool more = true;
     while (more) {                                    // one round unless the tile meets more than PW_LIST - 256 faces
@@ -584,18 +551,11 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
         // the round's chunks (chunk_count / chunk_size / chunk_pos above); quotient and remainder once per round, in scalar registers
         const int cnt = __builtin_amdgcn_readfirstlane(count);
         const int nch = chunk_count(cnt);
-#if LASR_PW_DEAL
         const int n_lo = nch ? cnt / nch : 0, n_rem = nch ? cnt % nch : 0;
-#endif
         for (int cb = 0; cb < nch; cb += SPLIT) {       // team t takes the chunks t, t + SPLIT, ...: same trip count, same barriers
             const int c = cb + team;                    // (a trip past the last chunk runs with n = 0)
-#if LASR_PW_DEAL
             const int n = c < nch ? n_lo + (c < n_rem ? 1 : 0) : 0;            // chunk_size(cnt, nch, c)
             const int lpos = c + lane * nch;                                   // chunk_pos(nch, c, lane)
-#else
-            const int n = max(0, min(PW_CAP, cnt - c * PW_CAP));
-            const int lpos = c * PW_CAP + lane;
-#endif
             // ---- stage: lane = entry, every wave a quarter of the record's source quads (all loads of a chunk in flight at once)
             int cm = 0, rm = 0;                       // the entry's rect as a 16-bit column mask and row mask of the tile
             if (lane < n) {
@@ -865,9 +825,6 @@ __global__ __launch_bounds__(256) void sr_forward_pairs_kernel(RasterArgs A, flo
 }
 // three channels: no occupancy request (87 VGPRs = 5 waves per SIMD; six / seven forced were slower, profiles/experiments/README.md)
 __global__ __launch_bounds__(256)
-#if LASR_PW_WAVES
-__attribute__((amdgpu_waves_per_eu(LASR_PW_WAVES, LASR_PW_WAVES)))
-#endif
 void sr_forward_pairs3_kernel(RasterArgs A, float* __restrict__ aggrs, float* __restrict__ colors)
 {
     __shared__ __attribute__((aligned(16))) PairLds<3, 1> L;

@@ -33,13 +33,7 @@
 namespace lasr {
 
 constexpr int TILE = 16;        // pixels per tile side (4 waves of 8x8)
-#ifndef LASR_PREFETCH
-#define LASR_PREFETCH 1         // scalar-cache prefetch of the next list entry in the forward walk (A/B: profiles/r05_prefetch_ab.txt)
-#endif
-#ifndef LASR_LIST_CAP
-#define LASR_LIST_CAP 2048
-#endif
-constexpr int LIST_CAP = LASR_LIST_CAP;  // capacity of each LDS face list (u16 ids relative to the round's first face; 5 lists = 20 KB)
+constexpr int LIST_CAP = 2048;  // capacity of each LDS face list (u16 ids relative to the round's first face; 5 lists = 20 KB)
 
 // ---------------------------------------------------------------------------
 // One thread builds one face's record -- into LDS; the block then writes its 256 records (48 KB, contiguous in the
@@ -289,11 +283,11 @@ __device__ __forceinline__ void forward_face(const RasterArgs& A, const Modes m,
     else s.a = (float)((double)s.a * (1. - (double)D));
 
     float c0 = w0, c1 = w1, c2 = w2;
-    clip_normalise<RX, (MK && OPT_MED3)>(c0, c1, c2);
+    clip_normalise<RX, MK>(c0, c1, c2);
     const float zp = RX ? __builtin_amdgcn_rcpf(c0 * rec[R_IZ + 0] + c1 * rec[R_IZ + 1] + c2 * rec[R_IZ + 2])
                         : depth_at<false, MK>(rec, c0, c1, c2);
     // tame records: the only NaN depth is recip_noscale(0) where the reference has 1 / 0 = inf, beyond any far plane
-    if (MK && OPT_NOSCALE ? !(zp >= A.near && zp <= A.far) : (zp < A.near || zp > A.far)) return;
+    if (MK ? !(zp >= A.near && zp <= A.far) : (zp < A.near || zp > A.far)) return;
 
     const bool front = (__float_as_int(rec[R_FLAGS]) & 8) != 0;
     if (m.rgb == 0) {
@@ -313,11 +307,11 @@ __device__ __forceinline__ void forward_face(const RasterArgs& A, const Modes m,
             // identical bits (exp_1ulp(0) == 1, x * 1 == x).
             const bool up = zn > s.smax;
             // -|zn - smax| is (up ? smax - zn : zn - smax) bit for bit (a - b == -(b - a)); the new maximum is a v_max
-            const float d = OPT_SOFTMAX ? -fabsf(zn - s.smax) : (up ? s.smax - zn : zn - s.smax);
+            const float d = -fabsf(zn - s.smax);
             const float E = RX ? __expf(d * U.inv_gamma)
                                : exp_1ulp(MK ? div_by_recip(d, A.gamma, U.inv_gamma) : d / A.gamma);
             const float hist = up ? E : 1.f, wgt = up ? D : E * D;     // (rescale, ez * D) of the reference, branch-free
-            s.smax = OPT_SOFTMAX && MK ? max_finite(zn, s.smax) : (up ? zn : s.smax);
+            s.smax = MK ? max_finite(zn, s.smax) : (up ? zn : s.smax);
             s.ssum = hist * s.ssum + wgt;
 #pragma unroll
             for (int k = 0; k < NCH; k++)
@@ -348,23 +342,19 @@ __device__ __forceinline__ void tile_of_block(int b, int total, int tiles_x, int
     }
     const int tiles = tiles_x * tiles_x;
     const int per = total >> 3;
-#ifndef LASR_ORDER
-#define LASR_ORDER 1
-#endif
-    if ((tiles_x & 1) == 0 && LASR_ORDER != 0) {
+    if ((tiles_x & 1) == 0) {
         int rank;
         if ((total & 7) == 0 && per % tiles == 0) {
             const int m = per / tiles;              // images per XCD
             const int i = b >> 3;                   // position in this XCD's issue order
-#ifndef LASR_ILV
-#define LASR_ILV 4      // images interleaved at a time: the records of 4 images (1.9 MB at 2420 faces) stay in the XCD's 4 MB L2.
-#endif                  // All 32 of the XCD: forward 2.16 ms but 700 MB fetched per 256 frames; 4: 2.18 ms, 170 MB (profiles/r03_tile_order_ab.txt)
-            const int g = m < LASR_ILV ? m : LASR_ILV;
+            // images interleaved at a time: the records of 4 images (1.9 MB at 2420 faces) stay in the XCD's 4 MB L2.
+            // All 32 of the XCD: forward 2.16 ms but 700 MB fetched per 256 frames; 4: 2.18 ms, 170 MB (profiles/r03_tile_order_ab.txt)
+            constexpr int ILV = 4;
+            const int g = m < ILV ? m : ILV;
             const int grp = i / (tiles * g), j = i - grp * tiles * g;
             rank = j / g;
             bn = (b & 7) * m + grp * g + (j - rank * g);
             if (m % g) { rank = i / m; bn = (b & 7) * m + (i - rank * m); }
-            if (LASR_ORDER == 3) { bn = (b & 7) * m + i / tiles; rank = i % tiles; }      // measurement: spiral, image-major
         } else {                                    // fewer images than XCDs (or a ragged count): rank-major over all images
             const int n_img = total / tiles;
             rank = b / n_img;
@@ -372,10 +362,6 @@ __device__ __forceinline__ void tile_of_block(int b, int total, int tiles_x, int
         }
         // rank -> cell of the square spiral around the grid's centre: ring r holds the 8r + 4 cells at Chebyshev distance
         // r + 1/2 from the centre, 4 r^2 cells lie inside it
-        if (LASR_ORDER == 2) { ty = rank / tiles_x; tx = rank - ty * tiles_x; return; }    // measurement: row-major, interleaved
-        if (LASR_ORDER == 4) rank = tiles - 1 - rank;                                      // measurement: outside-in
-        if (LASR_ORDER == 5) rank = (int)(((long long)rank * 167) % tiles);                // measurement: scattered (tiles = 2^k)
-        if (LASR_ORDER == 6) { rank = (rank & 1) ? tiles - 1 - (rank >> 1) : (rank >> 1); }   // measurement: centre and border alternate
         int r = (int)(sqrtf((float)rank) * 0.5f);
         while (4 * r * r > rank) r--;
         while (4 * (r + 1) * (r + 1) <= rank) r++;
@@ -580,12 +566,12 @@ __device__ __forceinline__ void forward_tile_body(RasterArgs A, float* __restric
             for (int j = 0; j < n; j++) {
                 const int fn = base + __builtin_amdgcn_readlane(chunk, j);     // wave-uniform -> scalar loads
                 const cptr_t rec = as_const(recs + (size_t)fn * REC);
-#if LASR_PREFETCH
                 // The walk is a chain of dependent scalar loads per entry: rect, wait, test; first record line, wait; the other two
                 // lines and the attributes on demand, wait again -- three round trips to L2 one after the other, and the occupancy
                 // sweep (profiles/r05_occupancy_sweep.txt) puts a third of the launch in exposed latency even at eight waves per
                 // SIMD.  Touch the entry's other two record lines and its attribute line together with the rect load: one
-                // round trip, the later loads hit the scalar cache.  The touched words are never used (no arithmetic changes).
+                // round trip, the later loads hit the scalar cache.  The touched words are never used (no arithmetic changes;
+                // A/B: profiles/r05_prefetch_ab.txt).
                 int pf1, pf2, pf3;
                 {
                     const float* rn = recs + (size_t)fn * REC;
@@ -593,12 +579,9 @@ __device__ __forceinline__ void forward_tile_body(RasterArgs A, float* __restric
                     asm volatile("s_load_dword %0, %3, 0x40\n\ts_load_dword %1, %3, 0x80\n\ts_load_dword %2, %4, 0x0"
                                  : "=&s"(pf1), "=&s"(pf2), "=&s"(pf3) : "s"(rn), "s"(tn) : "memory");
                 }
-#endif
                 // exact integer form of the bbox test K.cu:375 (see first_pixel_ge / last_pixel_le)
                 const bool cand = rect_has(__float_as_int(rec[R_BB + 0]), __float_as_int(rec[R_BB + 1]), pxy);
-#if LASR_PREFETCH
                 asm volatile("s_waitcnt lgkmcnt(0)" : : "s"(pf1), "s"(pf2), "s"(pf3));      // (the rect test has waited already)
-#endif
                 float w0, w1, w2;
                 barycentric(rec, xp, yp, w0, w1, w2);
                 const int lim = (A.N * A.F - (bn * A.F + fn)) * A.T;   // texels to the end of the tensor

@@ -7,7 +7,7 @@ entry points accept, (2^31 - 1) / 64 (check_common), for each F below.  For F = 
 
 The LDS extension of the distance code (sr_device.h: euclid_one_ext): which record word lane L copies comes from the static table
 k_bwd_ext_tbl instead of per-lane index arithmetic.  The table is read out of the header, decoded as bwd_ext_word_tbl decodes it, and
-held against the arithmetic of bwd_ext_word restated below, for all 64 lanes and the three obtuse corners.
+held against the layout restated below, for all 64 lanes and the three obtuse corners.
 """
 import ctypes
 import os
@@ -79,7 +79,7 @@ def table():
 
 
 def formula(L, c):
-    """bwd_ext_word (sr_device.h) for lane L of a face whose obtuse corner is c: (record word a, record word b or None when the value
+    """The extension's layout (sr_device.h: euclid_one_ext, bwd_ext_formula) for lane L of a face whose obtuse corner is c: (record word a, record word b or None when the value
     is a alone and a - b otherwise, constant or None)."""
     R_E, R_IDEN, R_FACE, BX_OBT = constant('R_E'), constant('R_IDEN'), constant('R_FACE'), constant('BX_OBT')
     k, i = L >> 4, L & 15

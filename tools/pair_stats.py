@@ -85,7 +85,7 @@ for fr in frames:
                 ent.append(k)
             if ent: DEAL['tiles']+=1; DEAL['entries']+=len(ent); DEAL['chunks']+=-(-len(ent)//64)
             # the same list DEALT round-robin over its chunks (the kernel: chunk c of nch holds positions c, c + nch, ...) against 64
-            # consecutive entries per chunk (LASR_PW_DEAL=0): iterations of the two per-lane loops, rank-paired as the kernel pairs them
+            # consecutive entries per chunk (the composition before the deal): iterations of the two per-lane loops, rank-paired as the kernel pairs them
             # (the walk moves outside pairs only), with no balance, and dense (pairs / 64)
             nch=-(-len(ent)//64)
             for mode,chunks in (('consecutive',[ent[c0:c0+64] for c0 in range(0,len(ent),64)]),('dealt',[ent[c::nch] for c in range(nch)])):

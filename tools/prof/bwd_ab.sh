@@ -1,7 +1,7 @@
 # A/B of the round-5 backward changes on one box:  bash tools/prof/bwd_ab.sh > gpurun_out/r05_backward_ab.txt
 #   old   = the library before them (commit f5b26ba's sources)
 #   nowpe = launch constants from the host + v_sqrt for the per-face heights (prologue 185 -> 99 VALU instructions, 68 -> 64 VGPRs
-#           = 7 -> 8 waves per SIMD), without the occupancy request for the six / nine-channel instantiations (-DLASR_BWD_WPE=0)
+#           = 7 -> 8 waves per SIMD), without the occupancy request for the six / nine-channel instantiations (a build of that round; the request is not in the tree)
 #   base  = shipped: + amdgpu_waves_per_eu(6 / 5) for six / nine channels (90 / 106 -> 78 / 88 VGPRs)
 R=$GRAFT_REPO_ROOT; cd $R
 echo "# three channels (bench.py --full step; kernel ms from library HIP events)"
