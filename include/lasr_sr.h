@@ -343,6 +343,9 @@ int lasr_selftest_div3(const float* a, const float* b, int* mismatches, int n, v
  * gw[i] / F, by the multiplication and shift the kernel uses instead of an integer division.  0 <= gw[i] <= (2^31 - 1) / 64 (the
  * largest N x F the entry points accept), F >= 1; LASR_E_BADARG otherwise. */
 int lasr_selftest_face_div(int F, const int* gw, int n, int* out);
+/* Test hook for the forward pair walk's 64 x 64 bit transpose across one wave: in and out are 64 64-bit words each on the device;
+ * bit e of out[p] = bit p of in[e]. */
+int lasr_selftest_transpose64(const unsigned long long* in, unsigned long long* out, void* hip_stream);
 
 #ifdef __cplusplus
 }

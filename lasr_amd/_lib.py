@@ -207,6 +207,7 @@ SIGNATURES = {
     'lasr_selftest_div': (_i, [_p, _p, _p, _i, _p]),
     'lasr_selftest_div3': (_i, [_p, _p, _p, _i, _p]),
     'lasr_selftest_face_div': (_i, [_i, _p, _i, _p]),
+    'lasr_selftest_transpose64': (_i, [_p, _p, _p]),
     'lasr_prof_enable': (_i, [_p, _i]),
     'lasr_prof_kernel_count': (_i, []),
     'lasr_prof_kernel_name': (ctypes.c_char_p, [_i]),

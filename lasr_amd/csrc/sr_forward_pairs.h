@@ -12,30 +12,33 @@
 //            projects to is ONE run-time offset, not three exec-masked code variants), the obtuse-corner test's operands
 //            precomputed -- at an odd quad stride, so that 16 lanes reading the same quad of 16 different entries hit 16
 //            different bank groups;
-//   classify (lanes = four rows of the tile, 16 pixels each; entry PER LANE) the chunk's rect ballots give every lane its candidate
-//            mask -- the entries whose exact integer pixel rect holds its pixel -- and each lane pops its own candidates: record
-//            gathered from LDS, barycentrics, then one bit per (pixel, entry) in one of three per-lane 64-bit masks: INSIDE the
-//            face, OUTSIDE but not certainly beyond the distance threshold (the backward's conservative line-distance reject,
-//            sr_backward.h: stage 1), or SLOW (a record that is not tame: never popped, handled by the generic arithmetic,
-//            wave-uniform, at the end of the chunk).  The loop runs as long as its fullest lane, so the candidates are evened
-//            out first: lanes ranked by candidate count (six ballots), rank r partnered with rank 63 - r, the lighter partner
-//            classifies the upper half of the difference at the heavier one's pixel centre and hands the result masks back
-//            (the same instructions on the same operands: no mask bit changes);
-//   balance  the lanes are ranked again, by their pair count, and partnered the same way: the lighter partner takes the upper
-//            half of the difference from the heavier one's outside mask and folds it into a private partial state;
-//   walk     every lane pops its own masks, inside pairs first, gathers the entry's record from LDS with 16-byte reads and applies
-//            the pair with the arithmetic of forward_face.  Inside and outside pixels share ONE clamped edge projection: an inside
-//            pixel's nearest edge line follows from the three products w_k^2 hk2_k (sr_device.h: euclid_one_ext); only where two
-//            lines are equidistant within 1.5 % or within the face's rounding scale (sr_device.h: near_tie) -- the reference's own
-//            choice is then decided by its rounding -- the reference's
-//            three projections run (a region most iterations skip).  Before: in 43 % of the walk's iterations some lane was
-//            inside and the 90-instruction three-projection branch ran at 27 % live lanes (tools/pair_stats.py);
+//   spans    (lane = ENTRY) every lane turns its own staged entry into the columns of the wave's four tile rows that the entry does
+//            not certainly miss: the not-far region of a well-conditioned face is the intersection of the three half-planes
+//            w_k >= far[k] (the backward's conservative line-distance reject, sr_backward.h: stage 1), its cut with a pixel row is ONE
+//            run of columns -- one fma per edge and row, rounded outward, cut with the entry's exact pixel rect (span_edge / span_row
+//            below).  An entry the reject does not apply to keeps its whole rect.  Four 16-bit runs make the lane's 64-bit word;
+//   transpose the 64 x 64 bit matrix (entry x pixel of the wave) is transposed across the wave in six block-swap stages
+//            (wave_transpose64 below: v_permlane32_swap, v_permlane16_swap, DPP, ds_swizzle): pixel lane p = 16 j + c now holds
+//            the mask of the entries whose span covers its pixel.  (Before: every lane popped the rect candidates of its pixel one per
+//            iteration -- 49 VALU each, 835 k candidates per bench frame, a fifth of the kernel's vector instructions -- after
+//            ranking, partnering and handing masks back and forth to even the loop out; profiles/r16_row_spans_ab.txt.)
+//            Records that are not tame get no bit: they are SLOW entries, handled wave-uniform by the generic arithmetic at the end
+//            of the chunk for the pixels of their rect;
+//   balance  the lanes are ranked by their pair count (six ballots), rank r partnered with rank 63 - r: the lighter partner takes
+//            the upper half of the difference from the heavier one's mask and folds it into a private partial state, at the
+//            heavier lane's pixel centre;
+//   walk     every lane pops its own mask, gathers the entry's record from LDS with 16-byte reads and applies the pair with the
+//            arithmetic of forward_face; whether the pixel lies inside the face follows from the pair's own barycentrics.  Inside and
+//            outside pixels share ONE clamped edge projection: an inside pixel's nearest edge line follows from the three products
+//            w_k^2 hk2_k (sr_device.h: euclid_one_ext); only where two lines are equidistant within 1.5 % or within the face's
+//            rounding scale (sr_device.h: near_tie) -- the reference's own choice is then decided by its rounding -- the
+//            reference's three projections run (a region most iterations skip);
 //   merge    partial states (alpha product, running maximum, rescaled sums) are folded into their pixel's state.
 //
 // What changes against the one-wave kernel is the ORDER in which a pixel's fragments meet its state: chunk by chunk, and a round's
 // list is DEALT over its chunks (chunk c of nch holds the list positions c, c + nch, ...: see chunk_pos below), so a pixel meets
-// the faces of residue 0 first, then those of residue 1, ...; within a chunk inside fragments first, then outside fragments in
-// index order, a stolen run merged at the end of the chunk; with two teams, the odd chunks' state merged at the very end.  Alpha
+// the faces of residue 0 first, then those of residue 1, ...; within a chunk in index order (inside and outside fragments alike),
+// a stolen run merged at the end of the chunk; with two teams, the odd chunks' state merged at the very end.  Alpha
 // product and depth softmax are symmetric in the fragments, only the rounding sequence moves (image within ~1e-6 of the
 // reference-order kernels; the running maximum is exact).  Every (pixel, face) pair itself goes through the same instruction
 // sequence as in forward_face (K.cu:370-453).
@@ -107,7 +110,6 @@ struct PairLds {
     int wcnt[2][4 * SPLIT];
     float sel[32];                    // edge k: (k == 0, k == 1, k == 2 | k + 1 == 0, k + 1 == 1, k + 1 == 2 mod 3) as 0 / 1, 8 floats apart;
                                       // [24..31]: zeros, the block a 2-bit edge index of 3 would name (see pairs_tile_body)
-    unsigned long long ball[SPLIT][2][16];   // the chunk's rect ballots: [0][x] entries whose rect holds column x, [1][y] row y (of the tile)
     float merge[SPLIT > 1 ? (SPLIT - 1) * 256 * (3 + NCH) : 1];       // partial states of the teams >= 1, [team - 1][field][pixel lane]
 };
 
@@ -210,12 +212,12 @@ __device__ __forceinline__ void merge_partial(PixState<NCH>& S, float pa, float 
 }
 
 // One (pixel, face) pair of a TAME record against the pixel state: forward_face<LASR, MK = true> (sr_raster.hip) with the record
-// gathered per lane from its staged slot R.  is_in: the classification's inside test (the same predicate on the same
-// barycentrics as euclid<.., TAME>).  Same operations in the same order per pair: the fragment's D, depth and weights are the
-// bits the one-wave kernel computes.
+// gathered per lane from its staged slot R.  Whether the pixel lies inside the face follows from the pair's own barycentrics (the
+// same predicate on the same operands as euclid<.., TAME>).  Same operations in the same order per pair: the fragment's D, depth
+// and weights are the bits the one-wave kernel computes.
 template <int NCH>
 __device__ __forceinline__ void pair_apply(const RasterArgs& A, const UniRecip& U, const float* __restrict__ R, const float* __restrict__ SEL,
-                                           bool is_in, bool has, float xp, float yp, PixState<NCH>& s)
+                                           bool has, float xp, float yp, PixState<NCH>& s)
 {
 #pragma clang fp contract(off)
     float4 q0 = ld4(R), q1 = ld4(R + 4), q2 = ld4(R + 8);
@@ -223,14 +225,16 @@ __device__ __forceinline__ void pair_apply(const RasterArgs& A, const UniRecip& 
     const float w0 = q0.x * xp + q0.y * yp + q0.z;                    // K.cu:24-29 (barycentric())
     const float w1 = q0.w * xp + q1.x * yp + q1.y;
     const float w2 = q1.z * xp + q1.w * yp + q2.x;
+    const bool is_in = (bool)((int)has & (int)(fminf(fminf(w0, w1), w2) > 0) & (int)(fmaxf(fmaxf(w0, w1), w2) < 1));
     const float x0 = q4.x, y0 = q4.y, x1 = q4.z, y1 = q4.w, x2 = q5.x, y2 = q5.y, z0 = q5.z, z1 = q5.w;
     float narg;
     // which edge: an inside pixel's nearest edge LINE from the three products w^2 hk2 (sr_device.h: euclid_one_ext), an outside pixel's
     // from the sign pattern of its barycentrics (K.cu:113-125); inside pixels near an angle bisector -- or of a face that is not
-    // well conditioned (hq = 0) -- take the reference's three projections
+    // well conditioned (hq = 0) -- take the reference's three projections.  (Not behind a "some lane is inside" branch: inside pairs
+    // are no longer walked first, some lane holds one in nearly every iteration.)
     bool tie = false;
     int k_in = 0;
-    if (wave_mask(is_in) != 0) {
+    {
         const float4 hq = ld4(R + PR_HQ);
         const float g0 = w2 * w2 * hq.x, g1 = w0 * w0 * hq.y, g2 = w1 * w1 * hq.z;
         const float glo = fminf(fminf(g0, g1), g2), gmid = __builtin_amdgcn_fmed3f(g0, g1, g2);
@@ -359,6 +363,93 @@ __device__ __forceinline__ u64_t upper_bits(u64_t hm, int moved)
     return p >= 63 ? 0ull : (hm >> (p + 1)) << (p + 1);
 }
 
+// ---- spans: which pixels of a tile row entry e does not certainly miss, as ONE run of columns (lane = entry).
+// The not-far region of a well-conditioned face is the intersection of the three half-planes w_k >= far[k]; with w_k = A x + B y + C
+// its cut with the pixel row y is the x interval  A x >= far[k] - (B y + C)  over the three edges: a lower bound where A > 0, an upper
+// bound where A < 0.  In tile columns (pixel centre x_c = (2 c + 1 - IS) / IS, so c = (x IS + IS - 1) / 2) the bound of edge k is
+//     c_k(y) = g (far[k] - C - B y) + off = y p + q,    g = (IS / 2) / A,  off = (IS - 1) / 2 - tile's first column,
+// one fma per edge and row with p = -B g and q = (far[k] - C) g + off prepared once per edge and entry (one v_rcp_f32 per edge).
+// A == 0 needs no case of its own: g is clamped to +-2^40, the bound becomes +-2^40 t and the whole row passes or fails by the sign
+// of t = far[k] - (B y + C).  The bounds are rounded OUTWARD, ceil(lo - slack) .. floor(hi + slack), and cut with the entry's pixel
+// rect and the tile.
+// The slack.  A pixel that matters (d^2 < thr, or inside the face) has w_k - far[k] >= 0.024 |far[k]| on every edge: far[k] carries
+// the 1.05 pad on thr, sqrt(1.05) = 1.0247.  The rounding of y p + q is that of t scaled by g -- a few ulp of |B y| + |C| + |far[k]|,
+// below 1e-6 / h for a face inside a few image widths (|grad w_k| = 1 / h, h the height over edge k), against the pad's
+// 0.024 sqrt(thr) / h: the pad absorbs it whatever g is, for every reach above 1e-4 of the image.  What the pad does not see is the
+// rounding in COLUMN units that does not scale with t: v_rcp_f32 (1 ulp), the products forming p and q and the final fma, relative
+// to the column coordinate itself, (3 + 1) ulp of at most IS columns = IS 2.4e-7 columns.  PW_SPAN_SLACK = 1/128 of a pixel covers
+// that for every image side up to 32768 and costs one extra pixel at an interval end in 1/128 of the cases (tools/pair_stats.py
+// counts them).  A pair the spans keep beyond the per-pixel test w_k < far[k] lies beyond the threshold and leaves at the walk's
+// exact cut d^2 >= thr.
+// Entries the conservative reject does not apply to (not well conditioned: far[k] = -inf) or that are not tame keep their whole pixel
+// rect: span = false.
+constexpr float PW_SPAN_SLACK = 1.f / 128.f;
+struct SpanEdge { float pl, ql, pu, qu; };            // the edge as a lower bound y pl + ql and as an upper bound y pu + qu of the column
+__device__ __forceinline__ SpanEdge span_edge(float a, float b, float c, float far, float half_is, float off, bool span)
+{
+    const float big = 1e9f, gmax = 1099511627776.f;           // 2^40
+    const float g = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(a) * half_is, -gmax, gmax);
+    const float p = -b * g, q = __builtin_fmaf(far - c, g, off);
+    const bool lower = (bool)((int)span & (int)(g > 0)), upper = (bool)((int)span & (int)(g < 0));
+    SpanEdge e;
+    e.pl = lower ? p : 0.f; e.ql = lower ? q - PW_SPAN_SLACK : -big;
+    e.pu = upper ? p : 0.f; e.qu = upper ? q + PW_SPAN_SLACK : big;
+    return e;
+}
+// the 16-bit column mask of one row: [a0, a1] the entry's rect columns within the tile (as floats), y the row's pixel centre
+__device__ __forceinline__ unsigned span_row(const SpanEdge (&E)[3], float y, float a0, float a1, bool row_in)
+{
+    const float lo = fmaxf(fmaxf(__builtin_fmaf(y, E[0].pl, E[0].ql), __builtin_fmaf(y, E[1].pl, E[1].ql)), __builtin_fmaf(y, E[2].pl, E[2].ql));
+    const float hi = fminf(fminf(__builtin_fmaf(y, E[0].pu, E[0].qu), __builtin_fmaf(y, E[1].pu, E[1].qu)), __builtin_fmaf(y, E[2].pu, E[2].qu));
+    // 0 <= a0 <= 16 and -1 <= a1 <= 15: l in [a0, 16], h in [-1, a1], both within [0, 15] when l <= h
+    const int l = (int)__builtin_amdgcn_fmed3f(__builtin_ceilf(lo), a0, 16.f), h = (int)__builtin_amdgcn_fmed3f(__builtin_floorf(hi), -1.f, a1);
+    return (bool)((int)row_in & (int)(l <= h)) ? (2u << (h & 15)) - (1u << (l & 15)) : 0u;
+}
+
+// ---- the 64 x 64 bit transpose across the wave: lane e comes in with the word S_e, lane p leaves with the word whose bit e is
+// bit p of S_e.  Six block-swap stages: at stage s lane L and lane L ^ 2^s trade the off-diagonal blocks of their 2 x 2 block
+// matrix -- the lane with bit s clear gives its bits at positions with bit s set and takes the partner's bits at positions with bit
+// s clear, moved up by 2^s.  Stage 5 is one v_permlane32_swap of the two halves; stage 4 one v_permlane16_swap per half of the
+// word and its rotation by 16 (after it BOTH rows of a pair hold "mine" in the low and "the partner's" in the high 16 bits of the
+// wanted result, so one merge serves them); stages 3, 1, 0 fetch the partner's word by DPP (row_ror:8, quad_perm), stage 2 by
+// ds_swizzle.  No ballot, no v_writelane.
+template <int J>
+__device__ __forceinline__ unsigned lane_xor_get(unsigned v)
+{
+    static_assert(J == 1 || J == 2 || J == 4 || J == 8, "");
+    if (J == 1) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);       // quad_perm:[1,0,3,2]
+    if (J == 2) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);       // quad_perm:[2,3,0,1]
+    if (J == 8) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false);      // row_ror:8
+    return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);                                        // swizzle: and 0x1f, or 0, xor 4
+}
+template <int J>
+__device__ __forceinline__ unsigned transpose_stage(unsigned own, bool up)
+{
+    constexpr unsigned M = J == 1 ? 0x55555555u : J == 2 ? 0x33333333u : J == 4 ? 0x0F0F0F0Fu : 0x00FF00FFu;    // positions with bit s clear
+    const unsigned t = lane_xor_get<J>(own);
+    const unsigned keep = up ? ~M : M;                  // up: this lane's index has bit s set
+    return (own & keep) | ((up ? t >> J : t << J) & ~keep);
+}
+__device__ __forceinline__ u64_t wave_transpose64(u64_t S, int lane)
+{
+    unsigned lo = (unsigned)S, hi = (unsigned)(S >> 32);
+    {
+        const auto r = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);     // lo of the lanes 32.. <-> hi of the lanes ..31
+        lo = r[0]; hi = r[1];
+    }
+    {
+        const auto a = __builtin_amdgcn_permlane16_swap(lo, __builtin_amdgcn_alignbit(lo, lo, 16), false, false);
+        const auto b = __builtin_amdgcn_permlane16_swap(hi, __builtin_amdgcn_alignbit(hi, hi, 16), false, false);
+        lo = (a[0] & 0xFFFFu) | (a[1] << 16);
+        hi = (b[0] & 0xFFFFu) | (b[1] << 16);
+    }
+    lo = transpose_stage<8>(lo, (lane & 8) != 0); hi = transpose_stage<8>(hi, (lane & 8) != 0);
+    lo = transpose_stage<4>(lo, (lane & 4) != 0); hi = transpose_stage<4>(hi, (lane & 4) != 0);
+    lo = transpose_stage<2>(lo, (lane & 2) != 0); hi = transpose_stage<2>(hi, (lane & 2) != 0);
+    lo = transpose_stage<1>(lo, (lane & 1) != 0); hi = transpose_stage<1>(hi, (lane & 1) != 0);
+    return (u64_t)hi << 32 | lo;
+}
+
 // A tile that no face's pixel rect overlaps (ORDER_EMPTY in the launch's order table, sr_raster.hip: sr_order_kernel): its list
 // would be empty, so every pixel ends as it starts and every output bit is a function of the launch's scalars.  ONE wave writes the
 // whole 16x16 tile; the values are formed with the expressions of pairs_tile_body's set-up and finalise (same operations on the
@@ -436,6 +527,7 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
     const int px = tx * PW_TILE + (lane & 15), py = ty * PW_TILE + wave + 4 * (lane >> 4);
     const bool valid = px < IS && py < IS;
     const int pn = py * IS + px;
+    const int pxy = valid ? (px | (py << 16)) : (int)0xfffefffe;                // for rect_has (sr_device.h): no rect holds a lane outside the image
 
     PixState<NCH> s;
     s.a = 1.f;
@@ -477,8 +569,11 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
         gmask = wave_mask(t);
     }
     if (gmask != 0 || G > 64) {
-    const float xp = pix_center(px, IS);
-    const float yp = pix_center(IS - 1 - py, IS);
+    float xp = pix_center(px, IS);                      // (not const: a lane that walks its partner's share holds the partner's centre here meanwhile)
+    float yp = pix_center(IS - 1 - py, IS);
+    float yrow[4];                                      // the centres of this wave's four rows (lane 16 j owns row j): wave-uniform
+#pragma unroll
+    for (int j = 0; j < 4; j++) yrow[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(yp), 16 * j));
     const short4* __restrict__ rects = A.rects + (size_t)bn * A.F;
     const float* __restrict__ recs = A.recs + (size_t)bn * A.F * REC;
     const int texstride = A.T * NCH;
@@ -557,14 +652,13 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
             const int n = c < nch ? n_lo + (c < n_rem ? 1 : 0) : 0;            // chunk_size(cnt, nch, c)
             const int lpos = c + lane * nch;                                   // chunk_pos(nch, c, lane)
             // ---- stage: lane = entry, every wave a quarter of the record's source quads (all loads of a chunk in flight at once)
-            int cm = 0, rm = 0;                       // the entry's rect as a 16-bit column mask and row mask of the tile
+            int ca0 = PW_TILE, ca1 = -1, rm = 0;      // the entry's rect: its columns [ca0, ca1] within the tile, its rows as a 16-bit mask
             if (lane < n) {
                 const int fn = base + (int)L.list[lpos];
                 {
                     const short4 q = rects[fn];       // x0, x1, row0, row1 (empty: 32767, -1, 32767, -1)
-                    const int a0 = max((int)q.x - tX0, 0), a1 = min((int)q.y - tX0, PW_TILE - 1);
+                    ca0 = min(max((int)q.x - tX0, 0), PW_TILE); ca1 = max(min((int)q.y - tX0, PW_TILE - 1), -1);
                     const int b0 = max((int)q.z - tY0, 0), b1 = min((int)q.w - tY0, PW_TILE - 1);
-                    if (a0 <= a1) cm = (2 << a1) - (1 << a0);
                     if (b0 <= b1) rm = (2 << b1) - (1 << b0);
                 }
                 const float4* __restrict__ src = (const float4*)(recs + (size_t)fn * REC);
@@ -592,109 +686,42 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
                 for (int i = 0; i < (3 * NCH + 3) / 4; i++)
                     if (wave + 4 * i < 3 * NCH) dst[PR_TEX + wave + 4 * i] = tv[i];
             }
-            // the rect ballots of the chunk (the exact bbox test, K.cu:375): wave w forms those of columns 4w .. 4w + 3 and of rows
-            // 4w .. 4w + 3 -- lanes = entries -- and leaves them in LDS for the four waves' pixel lanes
-            {
-                u64_t mine = 0;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const u64_t Bc = wave_mask((cm >> (4 * wave + j)) & 1), Br = wave_mask((rm >> (4 * wave + j)) & 1);
-                    if (lane == j) mine = Bc;
-                    if (lane == 4 + j) mine = Br;
-                }
-                if (lane < 8) L.ball[team][lane >> 2][4 * wave + (lane & 3)] = mine;
-            }
-            __syncthreads();
+            __syncthreads();                            // the staged records, before anybody reads a slot another wave wrote
 
-            // ---- candidates: bit e of a lane's mask = "entry e's pixel rect holds my pixel": the ballots of its column and of its row
-            u64_t cand, tame_mask;
+            // ---- spans: lane = entry.  The columns of this wave's four rows that the entry does not certainly miss (span_edge /
+            // span_row above) as the word S: bit 16 j + c = row wave + 4 j, column c of the tile.  Entries that are not tame (or every
+            // entry of a launch whose uniforms are not safe for the reciprocal arithmetic) get no bit: they are the slow entries below.
+            u64_t mn = 0;                               // per pixel lane: the near pairs of the chunk's tame entries
+            u64_t slow_mask = 0;                        // wave-uniform: the chunk's entries that are not tame
+#if !(defined(LASR_PW_ABL) && LASR_PW_ABL == 2)     // (2: measurement build, list + stage only)
             {
+                u64_t S = 0;
                 bool tame_e = false;
                 if (lane < n) tame_e = (__float_as_int(Lrec[lane * RS + PR_FLAGS]) & ok_bit) != 0;
-                const u64_t cxv = L.ball[team][0][px - tX0], ryv = L.ball[team][1][py - tY0];
-                cand = valid ? cxv & ryv : 0ull;
-                tame_mask = wave_mask(tame_e);
-            }
-#if defined(LASR_PW_ABL) && LASR_PW_ABL == 2        // measurement build: list + stage only
-            s.a += (float)__popcll(cand); cand = 0;
-#endif
-            // ---- classify: every lane pops its own candidates of TAME records (the others -- or every record of a launch whose
-            // uniforms are not safe for the reciprocal arithmetic -- go to the slow mask as they are): inside the face, or outside
-            // and not certainly beyond the threshold (the staged far[k]: w_k < far[k] puts the pixel farther than sqrt(1.05 thr)
-            // beyond edge k's line; -inf for faces the conservative reject does not apply to)
-            u64_t ms = cand & ~tame_mask, mi = 0, mo = 0;
-            cand &= tame_mask;
-            if (wave_mask(cand != 0) != 0) {
-                // the loop below runs as long as the fullest lane, so the candidates are evened out first, like the walk's pairs:
-                // rank the lanes by their candidate count, partner rank r with rank 63 - r; the lighter partner takes the upper
-                // half of the difference out of the heavier one's mask, classifies those bits at the HEAVIER lane's pixel centre
-                // (same instructions on the same operands: every mask bit is what its own lane would have computed) and hands
-                // the two result masks back.  Lanes outside a ragged image have no candidates: they are light partners.
-                const int kmine = min((int)__popcll(cand), 63);
-                const int rank = rank_of(kmine);
-                const int id_at_rank = __builtin_amdgcn_ds_permute(rank << 2, lane);             // lane r: the lane of rank r
-                const int partner = __builtin_amdgcn_ds_bpermute((63 - rank) << 2, id_at_rank);
-                const int kpart = __builtin_amdgcn_ds_bpermute(partner << 2, kmine);
-                const unsigned pc_lo = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)cand);
-                const unsigned pc_hi = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)(cand >> 32));
-                const float xq = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(xp)));
-                const float yq = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(yp)));
-                const bool heavy = rank < 32;
-                const u64_t hm = heavy ? cand : ((u64_t)pc_hi << 32 | pc_lo);
-                const u64_t top = upper_bits(hm, (heavy ? kmine - kpart : kpart - kmine) >> 1);
-                u64_t st = 0;                           // light lane: the partner's candidates it classifies
-                if (heavy) cand ^= top;
-                else st = top;
-                const bool gave = (bool)((int)heavy & (int)(top != 0));
-                // ONE loop over a lane's own run and then the partner's share (a second loop would cost max(own) + max(stolen)
-                // iterations); results collect in ri / ro and are set aside where a lane changes over -- an own bit and a stolen
-                // bit may name the same entry.  No divergent region but the change-over: a lane without work rides along on
-                // slot 63 with an empty bit.
-                float cx = xp, cy = yp;
-                u64_t ri = 0, ro = 0, more_m = ~0ull;
-                bool in_stolen = false;
-                auto advance = [&]() {
-                    if ((wave_mask(cand == 0) & more_m) != 0) {
-                        if ((bool)((int)(cand == 0) & (int)(st != 0))) {
-                            mi = ri; mo = ro; ri = 0; ro = 0;
-                            cx = xq; cy = yq; cand = st; st = 0; in_stolen = true;
-                        }
-                        more_m = wave_mask(st != 0);
-                    }
-                };
-                advance();
-                do {
-                    const int e = __builtin_ctzll(cand | (1ull << 63));
-                    const u64_t rest = cand & (cand - 1), bit = cand ^ rest;
-                    cand = rest;
-                    const float* R = Lrec + e * RS;
-                    const float4 q0 = ld4(R), q1 = ld4(R + 4);
-                    const float inv8 = R[8];
-                    const float4 q3 = ld4(R + PR_HK2);
-                    // (unfused like the walk's: on an edge-on face the fused form moves the barycentrics by whole pixels, and which
-                    // distance formula a pixel gets must be the reference's choice)
-                    const float w0 = q0.x * cx + q0.y * cy + q0.z;                  // barycentric()
-                    const float w1 = q0.w * cx + q1.x * cy + q1.y;
-                    const float w2 = q1.z * cx + q1.w * cy + inv8;
-                    const bool inside = (bool)((int)(fminf(fminf(w0, w1), w2) > 0) & (int)(fmaxf(fmaxf(w0, w1), w2) < 1));
-                    const bool far = (bool)((int)(w0 < q3.x) | (int)(w1 < q3.y) | (int)(w2 < q3.z));
-                    ri |= inside ? bit : 0ull;
-                    ro |= (bool)((int)!inside & (int)!far) ? bit : 0ull;
-                    advance();
-                } while (wave_mask(cand != 0) != 0);
-                if (!in_stolen) { mi = ri; mo = ro; ri = 0; ro = 0; }
-                // the hand-back: the light lane's results for the taken subset go into the heavy lane's masks
-                if (wave_mask(gave) != 0) {
-                    const unsigned gi_lo = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)ri);
-                    const unsigned gi_hi = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)(ri >> 32));
-                    const unsigned go_lo = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)ro);
-                    const unsigned go_hi = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)(ro >> 32));
-                    if (gave) { mi |= (u64_t)gi_hi << 32 | gi_lo; mo |= (u64_t)go_hi << 32 | go_lo; }
+                if (tame_e) {
+                    const float* R = Lrec + lane * RS;
+                    const float4 q0 = ld4(R), q1 = ld4(R + 4), q2 = ld4(R + 8), q3 = ld4(R + PR_HK2);
+                    const int fl = __float_as_int(q2.y);
+                    const bool span = (fl & 16) != 0;                         // else: the conservative reject does not apply, the rect as it is
+                    const float half_is = 0.5f * (float)IS, off = 0.5f * (float)(IS - 1) - (float)tX0;
+                    const SpanEdge E[3] = {span_edge(q0.x, q0.y, q0.z, q3.x, half_is, off, span),
+                                           span_edge(q0.w, q1.x, q1.y, q3.y, half_is, off, span),
+                                           span_edge(q1.z, q1.w, q2.x, q3.z, half_is, off, span)};
+                    const float a0 = (float)ca0, a1 = (float)ca1;
+                    unsigned m[4];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) m[j] = span_row(E, yrow[j], a0, a1, ((rm >> (wave + 4 * j)) & 1) != 0);
+                    S = (u64_t)(m[2] | m[3] << 16) << 32 | (m[0] | m[1] << 16);
                 }
+                // ---- transpose: pixel lane p = 16 j + c gets the word whose bit e is entry e's bit for that pixel
+                slow_mask = wave_mask((bool)((int)(lane < n) & (int)!tame_e));
+                const u64_t T = wave_transpose64(S, lane);
+                mn = valid ? T : 0ull;
             }
+#endif
 
 #if defined(LASR_PW_ABL) && LASR_PW_ABL == 1        // measurement build: no walk
-            s.a += (float)(__popcll(mi) + 2 * __popcll(mo)); mi = mo = 0;
+            s.a += (float)__popcll(mn); mn = 0;
 #endif
 #if defined(LASR_PW_ABL) && LASR_PW_ABL == 3        // measurement build: no balance (every lane its own pairs)
             const bool no_steal = true;
@@ -702,50 +729,45 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
             const bool no_steal = false;
 #endif
             // ---- balance: rank the lanes by their pair count (heaviest first), partner rank r with rank 63 - r
-            const int kmine = min((int)__popcll(mi) + (int)__popcll(mo), 63);
+            const int kmine = min((int)__popcll(mn), 63);
             const int rank = rank_of(kmine);
             const int id_at_rank = __builtin_amdgcn_ds_permute(rank << 2, lane);                 // lane r: the lane of rank r
             const int partner = __builtin_amdgcn_ds_bpermute((63 - rank) << 2, id_at_rank);
             const int kpart = __builtin_amdgcn_ds_bpermute(partner << 2, kmine);
-            const unsigned pmo_lo = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)mo);
-            const unsigned pmo_hi = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)(mo >> 32));
-            const float xq = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(xp)));
-            const float yq = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(yp)));
+            const unsigned pmn_lo = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)mn);
+            const unsigned pmn_hi = (unsigned)__builtin_amdgcn_ds_bpermute(partner << 2, (int)(unsigned)(mn >> 32));
+            float xq = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(xp)));
+            float yq = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(yp)));
             const bool heavy = rank < 32;
-            // the heavier partner's outside mask and the number of its pairs that change hands (both partners compute the same)
-            const u64_t hm = heavy ? mo : ((u64_t)pmo_hi << 32 | pmo_lo);
-            const int moved = min((heavy ? kmine - kpart : kpart - kmine) >> 1, (int)__popcll(hm));
+            // the heavier partner's mask and the number of its pairs that change hands (both partners compute the same); any pair may
+            // move: whether it is an inside pair shows in its own barycentrics, at the heavier lane's pixel centre
+            const u64_t hm = heavy ? mn : ((u64_t)pmn_hi << 32 | pmn_lo);
+            const int moved = (heavy ? kmine - kpart : kpart - kmine) >> 1;
             u64_t st = 0;                                                       // light lane: the pairs it takes over
             bool gave = false;
             if (moved > 0 && !no_steal) {
                 const u64_t top = upper_bits(hm, moved);
-                if (heavy) { mo ^= top; gave = top != 0; }
+                if (heavy) { mn ^= top; gave = top != 0; }
                 else st = top;
             }
 
-            // ---- walk: every lane pops its runs of pairs -- its inside pairs, its outside pairs, the partner's share -- one pair per
-            // iteration; a lane moves on to its next run inside the (rarely entered) region below
-            float cx = xp, cy = yp;
+            // ---- walk: every lane pops its run of pairs, then the partner's share, one pair per iteration; a lane moves on to the
+            // stolen run inside the (rarely entered) region below
             bool in_stolen = false;
             PixState<NCH> saved = s;
-            u64_t cur = mi, nxt = mo;
-            bool is_in = mi != 0;
+            u64_t cur = mn;
             u64_t more_m = ~0ull;
-            // a lane whose current run is used up moves on to its next one (entered when some lane has to)
             auto advance = [&]() {
                 if ((wave_mask(cur == 0) & more_m) != 0) {
-                    if (cur == 0) {
-                        if (nxt != 0) { cur = nxt; nxt = 0; }
-                        else if (st != 0) {                                         // the partner's share, into a fresh partial state
-                            saved = s;
-                            s.a = 1.f; s.ssum = 0.f; s.smax = A.eps;
+                    if ((bool)((int)(cur == 0) & (int)(st != 0))) {                 // the partner's share, into a fresh partial state
+                        saved = s;
+                        s.a = 1.f; s.ssum = 0.f; s.smax = A.eps;
 #pragma unroll
-                            for (int k = 0; k < NCH; k++) s.c[k] = 0.f;
-                            cx = xq; cy = yq; cur = st; st = 0; in_stolen = true;
-                        }
-                        is_in = false;
+                        for (int k = 0; k < NCH; k++) s.c[k] = 0.f;
+                        { const float ox = xp, oy = yp; xp = xq; yp = yq; xq = ox; yq = oy; }     // the two centres trade places (and back after the walk)
+                        cur = st; st = 0; in_stolen = true;
                     }
-                    more_m = wave_mask((nxt | st) != 0);
+                    more_m = wave_mask(st != 0);
                 }
             };
             advance();
@@ -755,14 +777,14 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
                 const bool has = cur != 0;
                 const int e = __builtin_ctzll(cur | (1ull << 63));
                 cur &= cur - 1;
-                pair_apply<NCH>(A, U, Lrec + e * RS, L.sel, (bool)((int)is_in & (int)has), has, cx, cy, s);
+                pair_apply<NCH>(A, U, Lrec + e * RS, L.sel, has, xp, yp, s);
                 advance();
             } while (wave_mask(cur != 0) != 0);
             // ---- merge the partial states into their pixels
             float pa = s.a, pm = s.smax, ps = s.ssum, pc[NCH];
 #pragma unroll
             for (int k = 0; k < NCH; k++) pc[k] = s.c[k];
-            if (in_stolen) s = saved;
+            if (in_stolen) { s = saved; xp = xq; yp = yq; }
             if (wave_mask(gave) != 0) {
                 pa = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(pa)));
                 pm = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(pm)));
@@ -771,11 +793,12 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
                 for (int k = 0; k < NCH; k++) pc[k] = __int_as_float(__builtin_amdgcn_ds_bpermute(partner << 2, __float_as_int(pc[k])));
                 if (gave) merge_partial<NCH>(s, pa, pm, ps, pc, A.gamma, U.inv_gamma);
             }
-            // ---- the chunk's slow pairs (records that are not tame): wave-uniform entry, generic arithmetic
-            for (int e = 0; wave_mask(ms != 0) != 0 && e < n; e++) {
-                if (wave_mask((ms >> e) & 1) == 0) continue;
+            // ---- the chunk's slow pairs (records that are not tame): wave-uniform entry, generic arithmetic, for the pixels of the entry's
+            // exact rect (the staged rect words: no mask is carried across the walk for them)
+            for (u64_t sm = slow_mask; sm != 0; sm &= sm - 1) {
+                const int e = __builtin_ctzll(sm);
                 const PairRecView R{Lrec + e * RS};
-                if ((ms >> e) & 1) {
+                if (rect_has(__float_as_int(Lrec[e * RS + PR_BB]), __float_as_int(Lrec[e * RS + PR_BBE]), pxy)) {
                     float w0, w1, w2;
                     barycentric(R, xp, yp, w0, w1, w2);
                     forward_face<true, false, NCH>(A, m, R, Lrec + e * RS + PR_TEX, 0, 0, xp, yp, w0, w1, w2, s, U);
@@ -808,12 +831,13 @@ __device__ __forceinline__ void pairs_tile_body(RasterArgs A, float* __restrict_
         }
     }
     if (!valid) return;
-    // ---- finalise (K.cu:458-482)
-    colors[((size_t)bn * (NCH + 1) + NCH) * P + pn] = (float)(1. - (double)s.a);
+    // ---- finalise (K.cu:458-482); the pixel's index once more from the packed coordinates (one register across the walk, not two)
+    const int pe = (int)((unsigned)pxy >> 16) * IS + (pxy & 0xffff);
+    colors[((size_t)bn * (NCH + 1) + NCH) * P + pe] = (float)(1. - (double)s.a);
 #pragma unroll
-    for (int k = 0; k < NCH; k++) colors[((size_t)bn * (NCH + 1) + k) * P + pn] = s.c[k] / s.ssum;
-    aggrs[((size_t)bn * 2 + 0) * P + pn] = s.ssum;
-    aggrs[((size_t)bn * 2 + 1) * P + pn] = s.smax;
+    for (int k = 0; k < NCH; k++) colors[((size_t)bn * (NCH + 1) + k) * P + pe] = s.c[k] / s.ssum;
+    aggrs[((size_t)bn * 2 + 0) * P + pe] = s.ssum;
+    aggrs[((size_t)bn * 2 + 1) * P + pe] = s.smax;
 }
 
 // six / nine channels: the compiler's own register budget (95 / 112 VGPRs)

@@ -1197,6 +1197,13 @@ extern "C" int lasr_sr_plan_forward(int N, int F, int T, int channels, int IS, i
     return k_forward[out->form][channel_index(channels)].fn ? LASR_OK : LASR_E_BADMODE;
 }
 
+// Self-test of the pair walk's 64 x 64 bit transpose (sr_forward_pairs.h: wave_transpose64): one wave, lane e reads in[e], lane p writes out[p].
+__global__ __launch_bounds__(64) void selftest_transpose64_kernel(const unsigned long long* __restrict__ in, unsigned long long* __restrict__ out)
+{
+    const int lane = threadIdx.x;
+    out[lane] = wave_transpose64(in[lane], lane);
+}
+
 // Test hook: number of (a[i], b[i]) pairs for which div_by_recip(a, b, RN(1/b)) != a / b bitwise (added to *mismatches).
 extern "C" int lasr_selftest_div(const float* a, const float* b, int* mismatches, int n, void* hip_stream)
 {
@@ -1216,6 +1223,14 @@ extern "C" int lasr_selftest_face_div(int F, const int* gw, int n, int* out)
         out[i] = face_div(gw[i], d.m, d.s);
     }
     return LASR_OK;
+}
+
+// Test hook: out[p] bit e = in[e] bit p for 64 words on the device, by the forward pair walk's cross-lane transpose (one wave).
+extern "C" int lasr_selftest_transpose64(const unsigned long long* in, unsigned long long* out, void* hip_stream)
+{
+    if (!in || !out) return LASR_E_BADARG;
+    hipLaunchKernelGGL(selftest_transpose64_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, in, out);
+    return launch_ok();
 }
 
 extern "C" int lasr_selftest_div3(const float* a, const float* b, int* mismatches, int n, void* hip_stream)

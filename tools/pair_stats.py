@@ -3,6 +3,9 @@
 # (the kernel), in quads, synchronised over a tile, dense.
 #   python tools/pair_stats.py [frame ...]      (default: frames 0, 37, 101, 200 of the bench cycle)
 # The last block sets the kernel's chunks -- a tile's list DEALT round-robin over them -- beside 64 consecutive entries per chunk.
+# The kernel classifies by ROW SPANS (sr_forward_pairs.h: span_edge / span_row): per entry and pixel row the one run of columns inside
+# the three half-planes w_k >= far[k], rounded outward by SPAN_SLACK of a pixel.  `span` counts the pairs the spans keep per frame
+# beside the per-pixel line test's `inside` + `near`; `span_missing` must be 0: every `real` pair (inside, or d^2 < thr) is kept.
 import numpy as np, sys, math, collections
 import os; sys.path.insert(0,os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lasr_amd import synth
@@ -17,7 +20,8 @@ thr=math.log(1./m['dist_eps']-1.)*m['sigma_val']
 r=math.sqrt(thr)
 print('F',f.shape[0],'thr',thr,'r px',r*IS/2)
 xs=(2*np.arange(IS)+1-IS)/IS
-tot=dict(cand=0,inside=0,near=0,real=0)
+tot=dict(cand=0,inside=0,near=0,real=0,span=0,span_missing=0)
+SPAN_SLACK=1./128.
 stats=[]
 ALT=[]
 def tri_dist2(px,py,a,b,c):
@@ -68,6 +72,16 @@ for fr in frames:
         d2=tri_dist2(X,Y,a,b,c)
         real=inside|(d2<thr)
         near=(~inside)&(~far)
+        # the spans: w_k is affine in x along a row, so the columns with w_k >= far_k are a half-line; the run is their intersection
+        cols=ix[None,:].astype(float); lo=np.full((len(iy),1),-np.inf); hi=np.full((len(iy),1),np.inf)
+        for wk,hk,Ak in ((w0,h0,(b[1]-c[1])/det),(w1,h1,(c[1]-a[1])/det),(w2,h2,(a[1]-b[1])/det)):
+            t=-r*1.0247/hk-wk[:,:1]                     # far_k - w_k at the rect's first column
+            if Ak==0: lo=np.where(t>0,np.inf,lo); continue
+            bound=ix[0]+t/(Ak*2./IS)                    # a pixel step is 2 / IS in x
+            if Ak>0: lo=np.maximum(lo,np.ceil(bound-SPAN_SLACK))
+            else: hi=np.minimum(hi,np.floor(bound+SPAN_SLACK))
+        span=(cols>=lo)&(cols<=hi)
+        tot['span']+=span.sum(); tot['span_missing']+=(real&~span).sum()
         rows=IS-1-iy  # row from top
         per_face.append((ix,rows,inside,near))
         sl=np.ix_(rows,ix)
@@ -130,6 +144,8 @@ for fr in frames:
                     row.append((kk.sum(),kk.max(),bal,cand.max(),cand.sum(),ci[w::4].max(),ci[w::4].sum(),cbal,cquad))
                 stats.append((len(ch),row))
 print(tot)
+kept=tot['inside']+tot['near']
+print('row spans keep %d pairs per frame against %d of the per-pixel line test (%+.3f %%); real pairs missing from the spans: %d (must be 0)'%(tot['span']/len(frames),kept/len(frames),100.*(tot['span']-kept)/kept,tot['span_missing']))
 st=stats
 nchunks=len(st)
 pairs=sum(r[0] for _,rows in st for r in rows)

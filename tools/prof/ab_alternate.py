@@ -3,8 +3,8 @@
    python tools/prof/ab_alternate.py time <other.so> <alternations> [size ...]   rows as they come, then per size the means, the
                                                                                  same-library spreads and the project's rule
    python tools/prof/ab_alternate.py outputs <other.so>                           bench.py --dump-outputs of both at 256 and 16 frames, compared
-sizes: f256 (the headline), f16, f64_512, f8_teams (the two-team pair walk), nine16 (nine channels, 16 meshes of 1280 faces, forward
-only through the operator).  The process that alternates never opens the GPU; a child that fails or runs into its time limit ends the
+sizes: f256 (the headline), f16, f64_512, f8_teams (the two-team pair walk), six16 / nine16 (six / nine channels, 16 meshes of 1280
+faces, forward only through the operator).  The process that alternates never opens the GPU; a child that fails or runs into its time limit ends the
 session.  profiles/r12_chunk_deal_ab.txt was taken with it."""
 import collections
 import json
@@ -20,11 +20,12 @@ SIZES = {
     'f16': BENCH + ['--frames', '16', '--steps', '600', '--warmup', '20'],
     'f64_512': BENCH + ['--frames', '64', '--image-size', '512', '--steps', '40', '--warmup', '5'],
     'f8_teams': BENCH + ['--frames', '8', '--steps', '1000', '--warmup', '20'],
+    'six16': [sys.executable, os.path.abspath(__file__), 'nine', '300', '6'],
     'nine16': [sys.executable, os.path.abspath(__file__), 'nine', '300'],
 }
 
 
-def nine(reps):
+def nine(reps, C=9):
     import numpy as np
     import torch
     sys.path.insert(0, R)
@@ -34,8 +35,8 @@ def nine(reps):
     dev = torch.device('cuda:0')
     fv, ft, near, far = synth.raster_batch(8, 3, count=16)
     rng = np.random.default_rng(9)
-    tex = np.concatenate([ft] + [rng.uniform(-2, 2, ft.shape).astype(np.float32) for _ in range(2)], -1)
-    kw = dict(synth.LASR_MODES, near=near, far=far, background_color=[0.1 * k for k in range(9)])
+    tex = np.concatenate([ft] + [rng.uniform(-2, 2, ft.shape).astype(np.float32) for _ in range(C // 3 - 1)], -1)
+    kw = dict(synth.LASR_MODES, near=near, far=far, background_color=[0.1 * k for k in range(C)])
     tfv, tft = torch.from_numpy(fv).to(dev), torch.from_numpy(tex).to(dev)
     h = _lib.lib()
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -73,7 +74,7 @@ def time_(other, alts, sizes):
             for name, lib in (('parent', other), ('branch', None)):
                 out = child(SIZES[size], lib)
                 d = collections.OrderedDict()
-                if size == 'nine16':
+                if size in ('six16', 'nine16'):
                     k = json.loads([l for l in out.splitlines() if l.startswith('RESULT ')][0][7:])
                 else:
                     j = json.loads([l for l in out.splitlines() if l.startswith('{')][-1])
@@ -113,7 +114,7 @@ def outputs(other):
 
 if __name__ == '__main__':
     if sys.argv[1] == 'nine':
-        nine(int(sys.argv[2]))
+        nine(int(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 9)
     elif sys.argv[1] == 'outputs':
         outputs(sys.argv[2])
     else:
