@@ -1240,6 +1240,45 @@ int lasr_rflow_weights(const float* Jb, const float* Jg, const float* uv, const 
                        float beta, float gamma, void* hip_stream);
 
 /*
+ * ---- Large-displacement matching for the variational optical flow (--vf_match; lasr_amd/csrc/flowmatch.hip,
+ * preprocess/flow_match.py) -------------------------------------------------------------------------------
+ * This project's own addition, as the flow above: a factor-2 pyramid loses a structure smaller than its own motion.  At one pyramid
+ * level an integer block-matching stage (SAD over 8-bit pixels) finds a displacement per pixel, and the forward-backward-consistent
+ * matches that explain the images clearly better than the upsampled flow replace it there before the level's unchanged warps (the
+ * "extended coarse-to-fine" idea of Xu, Jia & Matsushita 2012, reduced to a greedy per-pixel choice).  The definition is
+ * tests/flowmatch_restated.py; all of it is integer arithmetic, so the kernels give its very numbers.
+ *
+ * A quantised frame q is [H,W] uint32, one word r | g << 8 | b << 16 per pixel.  A displacement field is [H,W,2] int32 = (dx, dy).
+ *   C(p, d) = sum over q in [-r, r]^2 and the three channels of |A(clamp(p + q)) - B(clamp(p + q + d))|, both taps clamped.
+ * lasr_flowmatch_quantise: exactly one of img (uint8 [H,W,3]: the bytes themselves) and level (fp32 [H,W,3]:
+ *   clip(rint(255 I), 0, 255), half to even) is non-NULL -> out.
+ * lasr_flowmatch_search: d(p) = the minimum of the key (C, dx^2 + dy^2, dy, dx) in lexicographic order over the d in [-R, R]^2 with
+ *   p + d in the frame (d = 0 always is), c1(p) = C(p, d(p)).  A workgroup owns 32 x 8 pixels and stages A's tile with a halo of r
+ *   and B's with a halo of r + R in LDS, 33952 bytes at R = 32, r = 3; one v_sad_u8 per pixel pair.
+ * lasr_flowmatch_select: uv [2,H,W] fp32, the flow handed to the level.  cu = clip(rint(uv), -R, R) (half to even);
+ *   ccur = C(p, cu), or (2r+1)^2 765 where p + cu leaves the frame; seeded(p) = 1 where |d_ab(p) + d_ba(p + d_ab(p))|_inf <= 1 and
+ *   256 c1 < K ccur and |d_ab(p) - cu|_inf > 1, else 0; cand = d_ab where seeded, cu elsewhere.  K = rint(256 kappa).
+ * lasr_flowmatch_propagate: one Jacobi iteration from (seeded_in, cand_in) to (seeded_out, cand_out).  A seeded pixel is copied.
+ *   Another one looks at its left, right, upper and lower neighbour, in that order, and from one that is inside the frame and
+ *   seeded in seeded_in takes d = cand_in(neighbour) where p + d is in the frame, 256 C(p, d) < K ccur and C(p, d) is strictly below
+ *   the best it holds so far (ccur to begin with); it is then seeded.  Otherwise it keeps cand_in(p) and stays unseeded.
+ * No entry point uses atomics: the same input gives the same bits on every run.  Every read is clamped in index space.
+ * Checked on the host before any launch (LASR_E_BADARG): LASR_VARFLOW_MIN_SIZE <= H, W <= LASR_VARFLOW_MAX_SIZE;
+ *   1 <= R <= LASR_FLOWMATCH_MAX_R; 1 <= r <= LASR_FLOWMATCH_MAX_PATCH; 1 <= K <= 256; every pointer non-NULL (quantise: exactly one
+ *   source); no output is an input or another output.  Device contents are not read on the host: displacements within [-R, R] are a
+ *   precondition of select and propagate.  These launches are not in the lasr_prof_* kernel table.
+ */
+#define LASR_FLOWMATCH_MAX_R 32
+#define LASR_FLOWMATCH_MAX_PATCH 3
+int lasr_flowmatch_quantise(const unsigned char* img, const float* level, unsigned int* out, int H, int W, void* hip_stream);
+int lasr_flowmatch_search(const unsigned int* qA, const unsigned int* qB, int* d, int* c1, int H, int W, int R, int r, void* hip_stream);
+int lasr_flowmatch_select(const unsigned int* qA, const unsigned int* qB, const int* d_ab, const int* c1, const int* d_ba,
+                          const float* uv, unsigned char* seeded, int* cand, int* ccur, int H, int W, int R, int r, int K,
+                          void* hip_stream);
+int lasr_flowmatch_propagate(const unsigned int* qA, const unsigned int* qB, const unsigned char* seeded_in, const int* cand_in, const int* ccur,
+                             unsigned char* seeded_out, int* cand_out, int H, int W, int r, int K, void* hip_stream);
+
+/*
  * ---- Motion segmentation of preprocess/auto_mask.py (lasr_amd/csrc/motionseg.hip, lasr_amd/nnutils/motionseg.py, DESIGN.md
  * section 4.17) -------------------------------------------------------------------------------------------------------------------
  * This project's own addition: the reference fills Annotations/ with a detector (preprocess/mask.py), which stays out of scope;

@@ -149,6 +149,11 @@ SIGNATURES = {
     'lasr_rflow_derivs': (_i, [_p] * 2 + [_i] * 2 + [_p]),
     'lasr_rflow_tensor': (_i, [_p] * 5 + [_i] * 2 + [_p]),
     'lasr_rflow_weights': (_i, [_p] * 6 + [_i] * 2 + [_f, _f, _f, _p]),
+    # lasr_amd/csrc/flowmatch.hip
+    'lasr_flowmatch_quantise': (_i, [_p] * 3 + [_i] * 2 + [_p]),
+    'lasr_flowmatch_search': (_i, [_p] * 4 + [_i] * 4 + [_p]),
+    'lasr_flowmatch_select': (_i, [_p] * 9 + [_i] * 5 + [_p]),
+    'lasr_flowmatch_propagate': (_i, [_p] * 7 + [_i] * 4 + [_p]),
     # lasr_amd/csrc/motionseg.hip
     'lasr_motionseg_conf': (_i, [_p] * 3 + [_i] * 2 + [_f, _p]),
     'lasr_motionseg_moments': (_i, [_p] * 5 + [_i] * 2 + [_p]),
@@ -228,6 +233,7 @@ TRACK_MAX_SNAP, TRACK_MAX_WINDOW, TRACK_MAX_RADIUS, TRACK_MAX_SIZE, TRACK_SPLAT_
 REPROJ_MAX_RADIUS = 96                              # LASR_REPROJ_MAX_RADIUS of include/lasr_ops.h
 VARFLOW_MIN_SIZE, VARFLOW_MAX_SIZE = 2, 16384       # LASR_VARFLOW_* of include/lasr_ops.h
 RFLOW_RECORD = 18                                   # LASR_RFLOW_RECORD of include/lasr_ops.h
+FLOWMATCH_MAX_R, FLOWMATCH_MAX_PATCH = 32, 3        # LASR_FLOWMATCH_* of include/lasr_ops.h
 MOTIONSEG_MAX_SIZE, MOTIONSEG_BLOCKS, MOTIONSEG_MOMENTS, MOTIONSEG_BINS, MOTIONSEG_STATE = 16384, 256, 28, 1024, 12   # LASR_MOTIONSEG_*
 MESHCHECK_TILE, MESHCHECK_MAX_FACES, MESHCHECK_MAX_FRAMES = 256, 1 << 20, 65535   # LASR_MESHCHECK_* of include/lasr_ops.h
 SSIM_MIN_SIZE, SSIM_MAX_SIZE, SSIM_TILE_W, SSIM_TILE_H = 11, 4096, 32, 16         # LASR_SSIM_* of include/lasr_ops.h

@@ -176,8 +176,9 @@ def occlusion(f_ab, f_ba, tau=OCC_TAU, s=OCC_S):
     return occ
 
 
-def flow_planar(imgA, imgB, **over):
-    """uint8 [H,W,3] x 2 -> uv [2,H,W]: the whole estimate A -> B.  Launches only: no host synchronisation."""
+def flow_planar(imgA, imgB, init=None, **over):
+    """uint8 [H,W,3] x 2 -> uv [2,H,W]: the whole estimate A -> B.  Launches only: no host synchronisation.  init(level, uv) -> uv,
+    when given, sees the flow a level starts from: after expand, and the zero field of the coarsest level (preprocess/flow_match.py)."""
     p = params(**over)
     if not (torch.is_tensor(imgA) and torch.is_tensor(imgB)):
         raise TypeError('varflow: imgA and imgB must be tensors')
@@ -190,6 +191,8 @@ def flow_planar(imgA, imgB, **over):
         I1, I2 = A[lev], B[lev]
         h, w = int(I1.shape[0]), int(I1.shape[1])
         uv = torch.zeros(2, h, w, dtype=torch.float32, device=I1.device) if uv is None else expand(uv, h, w)
+        if init is not None:
+            uv = init(lev, uv)
         d, scratch = torch.empty_like(uv), torch.empty_like(uv)
         for _ in range(int(p['NW'])):
             J = tensor(I1, I2, uv)
@@ -201,9 +204,9 @@ def flow_planar(imgA, imgB, **over):
     return uv
 
 
-def flow(imgA, imgB, **over):
+def flow(imgA, imgB, init=None, **over):
     """uint8 [H,W,3] x 2 on the device -> flow A -> B, fp32 [H,W,2] in pixels."""
-    return flow_planar(imgA, imgB, **over).permute(1, 2, 0).contiguous()
+    return flow_planar(imgA, imgB, init, **over).permute(1, 2, 0).contiguous()
 
 
 def flow_pair(imgA, imgB, **over):

@@ -95,6 +95,9 @@ CAVEATS = collections.OrderedDict([
                            'is derived on relit closed-form fixtures, not on footage, and quality on real footage is unverified.  '
                            'One flow takes 1.11 (640 x 800) to 1.13 (1080p) times as long with it as without, so the default '
                            'limits of the masks and flow steps, which carry a factor of 4, hold.'),
+    ('large_displacement', 'Large-displacement matching stage of the variational flow (-- --vf_match, preprocess/flow_match.py): '
+                           'its patch radius, acceptance ratio and propagation count are derived on closed-form fixtures, not on '
+                           'footage: unverified on real footage.  A thin limb is only partly recovered.'),
     ('vcn_dry', 'No VCN checkpoint was given and the network was chosen: its weights are random, the flows are a dry run.'),
     ('ssim', 'Texture term --ptex_method ssim (no AlexNet weights): its weight is derived, not measured, and quality on real '
              'footage is unverified.'),
@@ -396,12 +399,12 @@ def plan(args):
     return steps
 
 
-def passed_gamma(tokens):
-    """The value of the last --vf_gamma among a script's handed-through tokens (`--vf_gamma 5` or `--vf_gamma=5`); 0 without one or
-    with one the script itself will refuse."""
+def passed_gamma(tokens, flag='--vf_gamma'):
+    """The value of the last --vf_gamma (or `flag`) among a script's handed-through tokens (`--vf_gamma 5` or `--vf_gamma=5`); 0
+    without one or with one the script itself will refuse."""
     val = 0.
     for i, tok in enumerate(tokens):
-        if tok == '--vf_gamma' or tok.startswith('--vf_gamma='):
+        if tok == flag or tok.startswith(flag + '='):
             text = tok.partition('=')[2] if '=' in tok else (tokens[i + 1] if i + 1 < len(tokens) else '')
             try:
                 val = float(text)
@@ -418,6 +421,8 @@ def describe(args):
     used.append('variational' if args.flow_method == 'variational' else ('vcn_dry' if not args.loadmodel else None))
     if args.flow_method == 'variational' and passed_gamma(getattr(args, 'passthrough', {}).get('auto_gen', [])) > 0:
         used.append('gradient_constancy')
+    if args.flow_method == 'variational' and passed_gamma(getattr(args, 'passthrough', {}).get('auto_gen', []), '--vf_match') > 0:
+        used.append('large_displacement')
     used += ['ssim' if f.get('ptex_method', 'alexnet') == 'ssim' else ('alexnet_random' if not f.get('alexnet_weights') else None)
              for f in stages[:1]]
     used += [None if args.encoder_weights else 'encoder_random', 'one_gpu', 'eval_reproj', 'eval_shape',

@@ -12,7 +12,9 @@ and i moves to j; j always moves on.  Without --loadmodel the model keeps its (s
 --flow_method variational replaces the network by the classical variational flow of lasr_amd/nnutils/varflow.py (DESIGN.md section
 4.16), which needs no checkpoint: no model is built, --loadmodel is refused, and occ-*.pfm holds its forward-backward consistency map.
 With it, --vf_gamma 5 adds the gradient-constancy term of preprocess/robust_flow.py for footage whose lighting changes (default 0:
-brightness constancy alone, as before; the value is derived on relit fixtures, not on footage).
+brightness constancy alone, as before; the value is derived on relit fixtures, not on footage), and --vf_match 24 adds the
+large-displacement matching stage of preprocess/flow_match.py for small parts that move further than their own size (default 0: off,
+as before; the radius is in pixels of the pyramid level --vf_match_level, its tuning is derived on fixtures, not on footage).
 Images are read and written with PIL and resized with bilinear interpolation on pixel centres (cv2.INTER_LINEAR's convention;
 uint8 images are rounded back to uint8 as cv2 does).
 """
@@ -48,6 +50,14 @@ FLOW_TUNING = (('alpha', float, 0.03, 'weight of the smoothness term'),
 # lighting changes (5 is the value derived on relit closed-form fixtures, not on footage)
 FLOW_ROBUST = (('gamma', float, 0., 'weight of the gradient-constancy term; 0: brightness constancy alone, 5: the derived value'),
                ('beta', float, 1., 'weight of the brightness-constancy term once --vf_gamma > 0'))
+# the large-displacement matching stage of --flow_method variational: with --vf_match R > 0 the flow is preprocess/flow_match.py's,
+# for small parts that move further than their own size (the tuning is derived on closed-form fixtures, not on footage); the keyword
+# of flow_match.make_flow_fn, the flag's suffix, type, default, (lowest, highest) and help
+FLOW_MATCH = (('match', '', int, 0, (0, 32), 'search radius R of the block-matching stage in pixels of its level; 0: off, 24: the fixtures\' value'),
+              ('patch', '_patch', int, 2, (1, 3), 'patch radius r of the matching cost: (2r+1)^2 pixels'),
+              ('level', '_level', int, -1, (-1, 32), 'pyramid level of the stage; -1: the finest whose longer side is <= 512'),
+              ('kappa', '_kappa', float, 0.9, (0., 1.), 'a match replaces the flow where its cost is below kappa times the flow\'s, inside (0, 1]'),
+              ('prop', '_prop', int, 16, (0, 64), 'iterations that spread accepted matches to their neighbours'))
 
 
 def add_flow_arguments(p):
@@ -56,6 +66,8 @@ def add_flow_arguments(p):
                    help='vcn: the network (needs --loadmodel to be more than a dry run); variational: the classical flow, no checkpoint')
     for name, kind, default, text in FLOW_TUNING + FLOW_ROBUST:
         p.add_argument('--vf_' + name, type=kind, default=default, help='variational: %s (default %s)' % (text, default))
+    for _, suffix, kind, default, _, text in FLOW_MATCH:
+        p.add_argument('--vf_match' + suffix, type=kind, default=default, help='variational: %s (default %s)' % (text, default))
 
 
 def check_flow_arguments(p, args):
@@ -67,6 +79,10 @@ def check_flow_arguments(p, args):
             p.error('--vf_%s must be finite and not negative, got %s' % (name, v))
     if args.vf_gamma == 0 and args.vf_beta == 0:
         p.error('--vf_gamma and --vf_beta are both 0: the flow would have no data term')
+    for _, suffix, _, _, (lo, hi), _ in FLOW_MATCH:
+        v = getattr(args, 'vf_match' + suffix)
+        if not (math.isfinite(v) and lo <= v <= hi) or (suffix == '_kappa' and v == 0):
+            p.error('--vf_match%s must be %s%s..%s, got %s' % (suffix, 'above ' if suffix == '_kappa' else '', lo, hi, v))
 
 
 def parse_args(argv=None):
@@ -161,9 +177,19 @@ def variational_flow_fn(args, make=None):
     """flow_fn(imgL, imgR) of --flow_method variational: lasr_amd.nnutils.varflow.make_flow_fn with the vf_* flags.  --testres
     scales the frames before the flow, as it does for the network (without the padding to multiples of 64, which only the network
     needs); flow and occ come back at the frames' size, the flow in their pixels.  With --vf_gamma > 0 the flow is
-    preprocess/robust_flow.py's (brightness and gradient constancy), built with gamma= and beta= beside the same flags."""
+    preprocess/robust_flow.py's (brightness and gradient constancy), built with gamma= and beta= beside the same flags.  With
+    --vf_match > 0 it is preprocess/flow_match.py's, built with match=, patch=, level=, kappa=, prop=, gamma= and beta= beside them."""
     tuning = {name: getattr(args, 'vf_' + name) for name, _, _, _ in FLOW_TUNING}
-    if getattr(args, 'vf_gamma', 0.) > 0:
+    if getattr(args, 'vf_match', 0) > 0:
+        if make is None:
+            here = os.path.dirname(os.path.abspath(__file__))
+            if here not in sys.path:
+                sys.path.insert(0, here)
+            import flow_match                                                      # (beside this file)
+            make = flow_match.make_flow_fn
+        stage = {key: getattr(args, 'vf_match' + suffix) for key, suffix, _, _, _, _ in FLOW_MATCH}
+        inner = make(gamma=args.vf_gamma, beta=args.vf_beta, **stage, **tuning)
+    elif getattr(args, 'vf_gamma', 0.) > 0:
         if make is None:
             here = os.path.dirname(os.path.abspath(__file__))
             if here not in sys.path:

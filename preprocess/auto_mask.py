@@ -94,6 +94,9 @@ def propagate_argv(args, key_paths):
     for name, _, default, _ in auto_gen.FLOW_ROBUST:                               # (a default run prints the line it always printed)
         if getattr(args, 'vf_' + name) != default:
             argv += ['--vf_' + name, str(getattr(args, 'vf_' + name))]
+    for _, suffix, _, default, _, _ in auto_gen.FLOW_MATCH:
+        if getattr(args, 'vf_match' + suffix) != default:
+            argv += ['--vf_match' + suffix, str(getattr(args, 'vf_match' + suffix))]
     for flag in ('roundtrip', 'force'):
         if getattr(args, flag):
             argv.append('--' + flag)

@@ -75,8 +75,9 @@ def weights(Jb, Jg, uv, d, eps=1e-3, beta=BETA, gamma=GAMMA):
     return J, psi
 
 
-def flow_planar(imgA, imgB, gamma=GAMMA, beta=BETA, **over):
-    """uint8 [H,W,3] x 2 -> uv [2,H,W]: the whole estimate A -> B.  Launches only: no host synchronisation."""
+def flow_planar(imgA, imgB, gamma=GAMMA, beta=BETA, init=None, **over):
+    """uint8 [H,W,3] x 2 -> uv [2,H,W]: the whole estimate A -> B.  Launches only: no host synchronisation.  init(level, uv) -> uv
+    is varflow.flow_planar's."""
     p = varflow.params(**over)
     gamma, beta = check_terms(gamma, beta)
     if not (torch.is_tensor(imgA) and torch.is_tensor(imgB)):
@@ -90,6 +91,8 @@ def flow_planar(imgA, imgB, gamma=GAMMA, beta=BETA, **over):
         R1, R2 = derivs(A[lev]), derivs(B[lev])                           # once per level: the warps below share them
         h, w = int(R1.shape[0]), int(R1.shape[1])
         uv = torch.zeros(2, h, w, dtype=torch.float32, device=R1.device) if uv is None else varflow.expand(uv, h, w)
+        if init is not None:
+            uv = init(lev, uv)
         d, scratch = torch.empty_like(uv), torch.empty_like(uv)
         for _ in range(int(p['NW'])):
             Jb, Jg = tensor(R1, R2, uv)
@@ -101,9 +104,9 @@ def flow_planar(imgA, imgB, gamma=GAMMA, beta=BETA, **over):
     return uv
 
 
-def flow(imgA, imgB, gamma=GAMMA, beta=BETA, **over):
+def flow(imgA, imgB, gamma=GAMMA, beta=BETA, init=None, **over):
     """uint8 [H,W,3] x 2 on the device -> flow A -> B, fp32 [H,W,2] in pixels."""
-    return flow_planar(imgA, imgB, gamma, beta, **over).permute(1, 2, 0).contiguous()
+    return flow_planar(imgA, imgB, gamma, beta, init, **over).permute(1, 2, 0).contiguous()
 
 
 def flow_pair(imgA, imgB, gamma=GAMMA, beta=BETA, **over):

@@ -12,7 +12,8 @@ configs/r<seq>.config), stage-0 ... stage-N (optimize.py, one run per stage of t
 before), extract (extract.py --rig), scores-reproj and scores-shape (scripts/eval_reproj.py, scripts/eval_shape.py) and the exports
 asked for.  Without --loadmodel and --alexnet_weights nothing needs a download: the flow is --flow_method variational, the texture
 term --ptex_method ssim; for footage whose lighting changes, `-- --vf_gamma 5` hands the gradient-constancy term of that flow to
-the masks and both flow steps (the report names it among the unverified pieces).  The first step that fails or runs into its limit ends the run (exit status 2 or 3) and nothing is started
+the masks and both flow steps, and `-- --vf_match 24` its large-displacement matching stage, for small parts that move further than
+their own size (the report names either among the unverified pieces).  The first step that fails or runs into its limit ends the run (exit status 2 or 3) and nothing is started
 after it; the same command again resumes at the first step whose stamp under <workdir>/reconstruct/steps/ no longer matches.
 --dry_run prints the plan as shell lines and does nothing else.  The run ends in <workdir>/reconstruct/report.md and report.json.
 """
