@@ -1388,6 +1388,61 @@ int lasr_meshcheck_pairs(const void* workspace, size_t workspace_bytes, int* fac
                          int* pairs, int T, int F, int max_pairs, void* hip_stream);
 
 /*
+ * ---- Folds between neighbouring faces: scripts/eval_shape.py --neighbours (lasr_amd/csrc/meshnbr.hip, scripts/shape_neighbours.py,
+ *      DESIGN.md section 4.18) ----
+ * This project's own addition, as the block above, and its second pass: the pair pass never tests two faces that share a vertex,
+ * this pass tests exactly those.  Parity is to the restatement in tests/meshnbr_restated.py and to closed forms only.  orient and
+ * PIERCES are the ones above, strict and without contraction.
+ *
+ * Topology (faces only, once for all frames).  A face with a repeated index is DEGENERATE: counted, part of nothing.  For
+ *   non-degenerate faces i < j, s = the number of corners of i whose index is a corner of j.  s = 0: no neighbour.  s = 1: a VERTEX
+ *   pair, ca / cb = the position (0..2) of the shared corner in i / in j.  s = 2: an EDGE pair, ca / cb = the position of the corner
+ *   that is not shared (the apex) in i / in j, and `same` is set when the shared edge runs in the same direction in both cyclic orders
+ *   (an inconsistent orientation).  s = 3: a DUPLICATE, counted and never tested.  A list entry is the 64-bit key
+ *   i << 32 | j << 8 | ca | cb << 2 | edge << 4 | same << 5, so sorted keys are in lexicographic (i, j) order.
+ * Vertex pair, A = tri(i), B = tri(j) in stored corner order: PIERCED iff (A[(ca+1)%3], A[(ca+2)%3]) pierces B or
+ *   (B[(cb+1)%3], B[(cb+2)%3]) pierces A.  Only the edge opposite the shared corner is tested: the two planes meet in a line through
+ *   the shared vertex, and if the triangles overlap beyond it the overlap segment ends where the nearer opposite edge enters the other
+ *   triangle.  The edges through the shared vertex touch the other triangle in that vertex; their plane determinants are zero in exact
+ *   arithmetic and noise in fp32, so they are not tested.
+ * Edge pair: nA = (A1 - A0) x (A2 - A0), nB likewise (the component order of orient's cross product), d = (nAx nBx + nAy nBy) +
+ *   nAz nBz, negated when `same` is set, qa = (nAx^2 + nAy^2) + nAz^2, qb likewise, q = qa qb.  CREASED iff d < 0 and d d > k q,
+ *   strictly, where k = cos^2(fold_deg) is computed in double by the caller and rounded once to fp32: the interior dihedral angle is
+ *   then below fold_deg.  A pair with q = 0, or with q or d d not finite, is not creased.  Non-coplanar faces that share an edge cannot
+ *   intersect outside that edge: this is an angle criterion, not an intersection test.  Supported edge lengths: about 1e-4 to 1e4
+ *   (q is the eighth power of a length).  The callers' default fold_deg = 20 is derived from nothing measured on a real
+ *   reconstruction.
+ *   min_cos[t] = min(1, the minimum over the edge pairs with 0 < q < inf of d / sqrt(q), clamped to [-1, 1]); the division and the
+ *   root are not part of any equality.
+ *
+ * lasr_meshnbr_list: faces [F,3] int32 -> list, uint64 [capacity], in no defined order (the caller sorts it), and counters, uint64
+ *   [LASR_MESHNBR_COUNTERS]: n_list, n_duplicate, n_degenerate, n_same.  The grid is the pair pass's (tile I, tile J >= I) over the
+ *   index triples only; a thread keeps one face of tile I, tile J's indices are staged in LDS.  Survivors are compacted per wave and
+ *   written 64 at a time through one atomicAdd on n_list per wave and batch, while the slot is below capacity: the list is complete
+ *   iff n_list <= capacity, and the counters are exact either way (capacity = 0: list may be NULL, a counting pass).  Zeroes the
+ *   counters itself.  A closed manifold has about 6 F entries.
+ * lasr_meshnbr_test: reads the records lasr_meshcheck_faces left in the workspace, n_list keys and k.  The grid is (list blocks,
+ *   frames), one lane per (entry, frame).  Zeroes or initialises, then fills:
+ *     nbr_count [T,2,F] int32    per face, the neighbours it is pierced by (plane 0) and creased with (plane 1)
+ *     totals    [T,2]   uint64   n_pierced, n_creased
+ *     cursor    [T]     uint32   scratch: counts the hits again, modulo 2^32
+ *     hits      [T,max_pairs,3] int32   (i, j, kind: 0 pierced, 1 creased) in no defined order, filled while cursor < max_pairs:
+ *                                complete iff n_pierced + n_creased <= max_pairs; max_pairs = 0: may be NULL
+ *     min_cos   [T]     fp32     as above (an integer atomicMin on an order-preserving encoding, decoded by a second small launch)
+ *   Integer atomics only: two runs give the same bits, the hits once sorted.  A key that names a face outside [0, F) is skipped.
+ * Checked on the host before any launch (LASR_E_BADARG): 0 <= F <= LASR_MESHCHECK_MAX_FACES, capacity >= 0; T, F as
+ *   lasr_meshcheck_pairs, n_list >= 0, max_pairs >= 0, 3 T max_pairs <= INT_MAX, 0 <= k <= 1; then F == 0 (list), or T == 0, F == 0 or
+ *   n_list == 0 (test), is LASR_OK with nothing launched and nothing written; then every pointer non-NULL (list only when
+ *   capacity > 0, hits only when max_pairs > 0) and no two buffers the same; LASR_E_WORKSPACE when workspace_bytes <
+ *   lasr_meshcheck_workspace_bytes(T, F).  Device contents are not read on the host.  Neither kernel is in the lasr_prof_* table.
+ */
+#define LASR_MESHNBR_COUNTERS 4
+int lasr_meshnbr_list(const int* faces, unsigned long long* list, unsigned long long* counters, int F, int capacity, void* hip_stream);
+int lasr_meshnbr_test(const void* workspace, size_t workspace_bytes, const unsigned long long* list, int n_list, float k, int* nbr_count,
+                      unsigned long long* totals, unsigned* cursor, int* hits, float* min_cos, int T, int F, int max_pairs,
+                      void* hip_stream);
+
+/*
  * ---- Structural similarity as the texture term of optimize.py --ptex_method ssim (lasr_amd/csrc/ssim.hip,
  *      lasr_amd/nnutils/fused_ops.py: ssim_distance) ----
  * This project's own addition: the reference has no counterpart (its texture term is an AlexNet feature distance that needs

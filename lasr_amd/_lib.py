@@ -163,6 +163,9 @@ SIGNATURES = {
     'lasr_meshcheck_workspace_bytes': (_sz, [_i, _i]),
     'lasr_meshcheck_faces': (_i, [_p, _p, _p, _sz, _p, _p] + [_i] * 3 + [_p]),
     'lasr_meshcheck_pairs': (_i, [_p, _sz] + [_p] * 4 + [_i] * 3 + [_p]),
+    # lasr_amd/csrc/meshnbr.hip
+    'lasr_meshnbr_list': (_i, [_p] * 3 + [_i] * 2 + [_p]),
+    'lasr_meshnbr_test': (_i, [_p, _sz, _p, _i, _f] + [_p] * 5 + [_i] * 3 + [_p]),
     # lasr_amd/csrc/ssim.hip
     'lasr_ssim_scratch_floats': (_sz, [_i] * 4),
     'lasr_ssim_forward': (_i, [_p] * 5 + [_i] * 4 + [_f, _p]),
@@ -236,6 +239,7 @@ RFLOW_RECORD = 18                                   # LASR_RFLOW_RECORD of inclu
 FLOWMATCH_MAX_R, FLOWMATCH_MAX_PATCH = 32, 3        # LASR_FLOWMATCH_* of include/lasr_ops.h
 MOTIONSEG_MAX_SIZE, MOTIONSEG_BLOCKS, MOTIONSEG_MOMENTS, MOTIONSEG_BINS, MOTIONSEG_STATE = 16384, 256, 28, 1024, 12   # LASR_MOTIONSEG_*
 MESHCHECK_TILE, MESHCHECK_MAX_FACES, MESHCHECK_MAX_FRAMES = 256, 1 << 20, 65535   # LASR_MESHCHECK_* of include/lasr_ops.h
+MESHNBR_COUNTERS = 4                                # LASR_MESHNBR_COUNTERS of include/lasr_ops.h: n_list, n_duplicate, n_degenerate, n_same
 SSIM_MIN_SIZE, SSIM_MAX_SIZE, SSIM_TILE_W, SSIM_TILE_H = 11, 4096, 32, 16         # LASR_SSIM_* of include/lasr_ops.h
 
 

@@ -109,6 +109,10 @@ CAVEATS = collections.OrderedDict([
     ('eval_reproj', 'scripts/eval_reproj.py scores against the silhouettes and flows the reconstruction was fitted to: agreement, '
                     'not ground truth.'),
     ('eval_shape', 'scripts/eval_shape.py does not see folds between neighbouring faces.'),
+    ('eval_shape_neighbours', 'scripts/eval_shape.py --neighbours also tests faces that share a vertex or an edge.  Two faces that '
+                              'share an edge count as folded (n_creased) below an interior dihedral angle of 20 degrees: an angle '
+                              'criterion, not an intersection test, and the threshold is derived from nothing measured on a real '
+                              'reconstruction: unverified on real footage.  Judge by min_dihedral.'),
     ('bake_texture', 'The baked atlas (scripts/bake_texture.py) is only as good as the fitted cameras; unseen texels stay unfilled '
                      'without --fill.'),
     ('export_tracks', 'Point tracks (scripts/export_tracks.py) follow the fitted surface, not the image: unverified on real footage.'),
@@ -196,6 +200,8 @@ def build_parser():
     for name, text in (('gif', 'render_vis.py'), ('glb', 'scripts/export_gltf.py'), ('atlas', 'scripts/bake_texture.py'),
                        ('tracks', 'scripts/export_tracks.py')):
         p.add_argument('--' + name, action='store_true', help='also run ' + text)
+    p.add_argument('--neighbours', action='store_true',
+                   help='scripts/eval_shape.py --neighbours: also score folds between neighbouring faces (n_pierced, n_creased, min_dihedral)')
     p.add_argument('--worst', type=int, default=5, help='frames listed as worst by each score (default 5)')
     p.add_argument('--dry_run', action='store_true', help='print the plan as shell lines; run nothing, write nothing')
     p.add_argument('--from', dest='start', default=None, metavar='STEP', help='first step to run')
@@ -382,7 +388,8 @@ def plan(args):
     add('scores-reproj', 'eval_reproj', [py, script('scripts', 'eval_reproj.py')] + common +
         ['--outpath', OUT + '/reproj.json', '--worst', str(args.worst)], inputs=meshes, outputs=[OUT + '/reproj.json'], work=T)
     add('scores-shape', 'eval_shape', [py, script('scripts', 'eval_shape.py')] + common +
-        ['--outpath', OUT + '/shape.json', '--worst', str(args.worst)], inputs=meshes, outputs=[OUT + '/shape.json'], work=T)
+        ['--outpath', OUT + '/shape.json', '--worst', str(args.worst)] + (['--neighbours'] if getattr(args, 'neighbours', False) else []),
+        inputs=meshes, outputs=[OUT + '/shape.json'], work=T)
     if args.gif:
         add('gif', 'render_vis', [py, script('render_vis.py')] + common + ['--outpath', '%s/%s.gif' % (OUT, seq)], inputs=meshes,
             outputs=['%s/%s.gif' % (OUT, seq)], work=T)
@@ -425,7 +432,8 @@ def describe(args):
         used.append('large_displacement')
     used += ['ssim' if f.get('ptex_method', 'alexnet') == 'ssim' else ('alexnet_random' if not f.get('alexnet_weights') else None)
              for f in stages[:1]]
-    used += [None if args.encoder_weights else 'encoder_random', 'one_gpu', 'eval_reproj', 'eval_shape',
+    used += [None if args.encoder_weights else 'encoder_random', 'one_gpu', 'eval_reproj',
+             'eval_shape_neighbours' if getattr(args, 'neighbours', False) else 'eval_shape',
              'bake_texture' if args.atlas else None, 'export_tracks' if args.tracks else None]
     return dict(seqname=args.seqname, frames=args.n_frames, size=[args.width, args.height], mask_route=route,
                 flow_method=args.flow_method, schedule=args.schedule_name, stages=[dict(f) for f in stages], worst=args.worst,
@@ -444,7 +452,7 @@ def driver_argv(args):
             out += ['--' + name, str(val)]
     for k, path in args.key:
         out += ['--key', '%d:%s' % (k, path)]
-    return out + ['--' + name for name in ('gif', 'atlas', 'glb', 'tracks') if getattr(args, name)]
+    return out + ['--' + name for name in ('gif', 'atlas', 'glb', 'tracks', 'neighbours') if getattr(args, name, False)]
 
 
 def shell_lines(steps, args):

@@ -2,7 +2,8 @@
 """From a folder of frames to a reconstruction and a report, in one resumable command (lasr_amd/pipeline.py).
 
     python scripts/reconstruct.py --frames ~/cat/ --seqname cat --workdir runs/cat [--key 0:first.png | --masks DIR]
-           [--schedule quick|template|FILE] [--glb] [--gif] [--atlas] [--tracks] [--dry_run] [--from S] [--until S] [--force S]
+           [--schedule quick|template|FILE] [--glb] [--gif] [--atlas] [--tracks] [--neighbours] [--dry_run] [--from S] [--until S]
+           [--force S]
            [--timeout_scale 1.0] [-- flags passed through to the preprocessing scripts]
 
 Steps, each a fresh child process with the work directory as its current one, one at a time, each under its own time limit:
@@ -15,6 +16,8 @@ term --ptex_method ssim; for footage whose lighting changes, `-- --vf_gamma 5` h
 the masks and both flow steps, and `-- --vf_match 24` its large-displacement matching stage, for small parts that move further than
 their own size (the report names either among the unverified pieces).  The first step that fails or runs into its limit ends the run (exit status 2 or 3) and nothing is started
 after it; the same command again resumes at the first step whose stamp under <workdir>/reconstruct/steps/ no longer matches.
+--neighbours hands scripts/eval_shape.py its flag of that name: folds between neighbouring faces are scored too (n_pierced, n_creased,
+min_dihedral in the report; the angle threshold is unmeasured on real footage, and the report says so).
 --dry_run prints the plan as shell lines and does nothing else.  The run ends in <workdir>/reconstruct/report.md and report.json.
 """
 import os
