@@ -120,22 +120,23 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
     if (use_far) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            // (v_sqrt_f32, 1 ulp, instead of the 14-instruction IEEE expansion per height: the reject carries 5 % slack on thr,
-            // and flag 16 guarantees a well-scaled argument)
-            const float h = __builtin_amdgcn_sqrtf(rec[R_HK2 + k]);
+            // (the height itself, left in the record by set-up -- v_sqrt_f32 of hk2, 1 ulp: the reject carries 5 % slack on thr, and
+            // flag 16 guarantees a well-scaled argument)
+            const float h = rec[R_HS + k];
             ld[3 * k] = rec[R_INV + 3 * k] * h; ld[3 * k + 1] = rec[R_INV + 3 * k + 1] * h; ld[3 * k + 2] = rec[R_INV + 3 * k + 2] * h;
         }
     }
+    // launch-uniform factors of stage 2's gradient block (formed after the device-side near / far are in): the depth normalisation
+    // zn = zp zn_a + zn_b, the softmax exponent's 1 / gamma with v_exp_f32's log2(e) folded in, and 1 / (gamma (near - far)) of d/dz
+    const float inv_fmn = div_<FM>(1.f, A.far - A.near), inv_gamma = div_<FM>(1.f, A.gamma);
+    const float zn_a = -inv_fmn, zn_b = A.far * inv_fmn;
+    const float ex_k = inv_gamma * 1.44269504088896341f, cz_k = -(inv_gamma * inv_fmn);
     const float tie_scale = rec[R_TIE];          // near_tie_scale(hk2), 0 unless flags bit 4: derived once per face by set-up (sr_device.h)
     // K.cu:599: a fragment the forward pass depth-culled gets no gradient.  A well-conditioned face whose vertex depths lie
     // strictly inside (near, far) cannot be culled anywhere (its clipped barycentrics are >= 0 and sum to 1 within 1e-4, so the
-    // interpolated depth stays within the vertex range up to rounding): one test per face instead of one per fragment
-    bool depth_safe = false;
-    if (flags & 16) {
-        const float z0 = rec[R_FACE + 2], z1 = rec[R_FACE + 5], z2 = rec[R_FACE + 8];
-        const float zlo = fminf(fminf(z0, z1), z2), zhi = fmaxf(fmaxf(z0, z1), z2);
-        depth_safe = zlo > 0.f && zlo * (1.f - 1e-4f) > A.near && zhi * (1.f + 1e-4f) < A.far;
-    }
+    // interpolated depth stays within the vertex range up to rounding): one test per face instead of one per fragment, on the
+    // padded depth range set-up left in the record (sr_device.h: pack_depth_range)
+    const bool depth_safe = (flags & 16) && depth_range_inside(rec[R_ZR], A.near, A.far);
     // The pixel planes a face reads (gcolors and colors: NCH + 1 planes each, aggrs: 2) go through ONE wave-uniform base pointer per
     // (image, tensor) in an SGPR pair and a 32-bit per-lane byte offset: 4 * pn, formed once per batch and stepped by the plane stride
     // with one 32-bit add per plane (gcolors and colors share it).  The loads come out as `global_load_dword v, voffset, s[base:base+1]`;
@@ -275,30 +276,31 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
             reenter();
             const float ssum = ld_plane(aggrs, AG, 2, 0, pn, po);
             const float smax = ld_plane(aggrs, AG, 2, 1, pn, po);
-            const float zn = div_<FM>(A.far - zp, A.far - A.near);
-            const float sm = div_<FM>(D * exp_<FM>(div_<FM>(zn - smax, A.gamma)), ssum);
-            float g[NCH];
+            // zn = (far - zp) / (far - near) as one multiply-add, the softmax exponent (zn - smax) / gamma as one product that
+            // already carries v_exp_f32's log2(e) (the launch-uniform factors above)
+            const float zn = zp * zn_a + zn_b;
+            const float sm = div_<FM>(D * __builtin_amdgcn_exp2f((zn - smax) * ex_k), ssum);
+            float sg[NCH];                       // sm * g[k], formed once: the attribute gradients and Crgb both carry the factor
 #pragma unroll
-            for (int k = 0; k < NCH; k++) g[k] = ld_plane(gcolors, GC, NCH + 1, k, pn, po);
+            for (int k = 0; k < NCH; k++) sg[k] = sm * ld_plane(gcolors, GC, NCH + 1, k, pn, po);
             if (vertex_tex) {
 #pragma unroll
                 for (int k = 0; k < NCH; k++) {
-                    gt[k] += sm * (w0 * g[k]); gt[NCH + k] += sm * (w1 * g[k]); gt[2 * NCH + k] += sm * (w2 * g[k]);
+                    gt[k] += w0 * sg[k]; gt[NCH + k] += w1 * sg[k]; gt[2 * NCH + k] += w2 * sg[k];
                 }
             } else {
                 const int j = surface_texel(w0, w1, A.res);
                 if (j >= 0 && j < A.T) {       // K.cu:620
                     float* gtp = gtex + (size_t)gw * A.T * 3 + 3 * j;
-                    atomicAdd(gtp + 0, sm * g[0]); atomicAdd(gtp + 1, sm * g[1]); atomicAdd(gtp + 2, sm * g[2]);
+                    atomicAdd(gtp + 0, sg[0]); atomicAdd(gtp + 1, sg[1]); atomicAdd(gtp + 2, sg[2]);
                 }
             }
             float Crgb = 0.f;
 #pragma unroll
             for (int k = 0; k < NCH; k++)
-                Crgb += g[k] * (sample_colour(tex, w0, w1, w2, A.res, k, m.tex, lim, NCH) - ld_plane(colors, CO, NCH + 1, k, pn, po));
-            Crgb *= sm;
+                Crgb += sg[k] * (sample_colour(tex, w0, w1, w2, A.res, k, m.tex, lim, NCH) - ld_plane(colors, CO, NCH + 1, k, pn, po));
             C += div_<FM>(Crgb, D);
-            const float Cz = div_<FM>(div_<FM>(Crgb, A.gamma), A.near - A.far) * zp * zp;
+            const float Cz = (Crgb * cz_k) * (zp * zp);       // Crgb / gamma / (near - far) * zp^2
             if (LASR_FAST) {
                 gz0 = Cz * q0 * iz0r; gz1 = Cz * q1 * iz1r; gz2 = Cz * q2 * iz2r;       // q_k = w_k / z_k
             } else {
@@ -332,10 +334,12 @@ void sr_backward_kernel(RasterArgs A, const float* __restrict__ colors,
             }
             gx0 = gxy[0][0]; gy0 = gxy[0][1]; gx1 = gxy[1][0]; gy1 = gxy[1][1]; gx2 = gxy[2][0]; gy2 = gxy[2][1];
         } else if (m.dist == 2) {                                             // K.cu:649-655
+            // k2 dx and k2 dy once: each of the six accumulations below is then one multiply-add on (t_k + u_k)
             const float k2 = 2 * fr.sign * C;
-            gx0 = k2 * (fr.t0 + u0) * fr.dx; gy0 = k2 * (fr.t0 + u0) * fr.dy;
-            gx1 = k2 * (fr.t1 + u1) * fr.dx; gy1 = k2 * (fr.t1 + u1) * fr.dy;
-            gx2 = k2 * (fr.t2 + u2) * fr.dx; gy2 = k2 * (fr.t2 + u2) * fr.dy;
+            const float kx = k2 * fr.dx, ky = k2 * fr.dy;
+            gx0 = (fr.t0 + u0) * kx; gy0 = (fr.t0 + u0) * ky;
+            gx1 = (fr.t1 + u1) * kx; gy1 = (fr.t1 + u1) * ky;
+            gx2 = (fr.t2 + u2) * kx; gy2 = (fr.t2 + u2) * ky;
         }
         gv[0] += gx0; gv[1] += gy0; gv[2] += gz0;
         gv[3] += gx1; gv[4] += gy1; gv[5] += gz1;

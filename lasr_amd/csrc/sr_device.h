@@ -40,10 +40,15 @@ namespace lasr {
 //         [15]     the backward's lane -> (row, column) walk over the pixel rect (build_record)
 //         [31]     tie  : near_tie_scale(hk2), the face's absolute near-tie margin (0 unless flags bit4): a function of the face
 //                         alone, derived once here instead of by an IEEE division in every backward wave
-//         [44..47] padding
+//         [44..46] hs   : sqrt(hk2[k]) (v_sqrt_f32), the heights themselves, for the line coefficients of the backward's stage 1
+//                         (0 unless flags bit4): three v_sqrt_f32 per face here instead of per backward wave
+//         [47]     zr   : the vertices' depth range with the backward's 1e-4 pad, zlo (1 - 1e-4) and zhi (1 + 1e-4), as two bfloat16
+//                         halves rounded OUTWARD (low half: the lower bound, -inf unless zlo > 0; high half: the upper bound): the
+//                         backward's per-face "no fragment can be depth-culled" test is two compares against near / far
+//                         (pack_depth_range / depth_range_inside below)
 constexpr int REC = 48;
 
-constexpr int R_BB = 0, R_FLAGS = 2, R_INV = 3, R_HK2 = 12, R_FACE = 16, R_DEN = 25, R_IDEN = 28, R_TIE = 31, R_E = 32, R_IZ = 41;
+constexpr int R_BB = 0, R_FLAGS = 2, R_INV = 3, R_HK2 = 12, R_FACE = 16, R_DEN = 25, R_IDEN = 28, R_TIE = 31, R_E = 32, R_IZ = 41, R_HS = 44, R_ZR = 47;
 
 // Read-only buffers written by an EARLIER kernel are viewed through the constant address
 // space: with a wave-uniform index the compiler then emits s_load (scalar cache -> SGPRs)
@@ -171,6 +176,26 @@ __device__ __forceinline__ float pix_center_p2(int i, int is, float inv_is, bool
 
 __host__ __device__ __forceinline__ float near_tie_scale(float h2a, float h2b, float h2c);     // (below, with near_tie)
 
+// The depth range of a face's vertices as the record's word R_ZR.  K.cu:599 gives a depth-culled fragment no gradient; a
+// well-conditioned face whose vertex depths lie strictly inside (near, far) cannot be culled anywhere (its clipped barycentrics are
+// >= 0 and sum to 1 within 1e-4, so the interpolated depth stays within the vertex range up to rounding).  The range, padded by that
+// 1e-4, is a function of the face alone; near / far may only be known on the device, so the two bounds are kept, as bfloat16 halves:
+// truncating a positive float's low 16 bits rounds it down, adding 0xffff first rounds it up, so the packed range CONTAINS the
+// padded one (by at most 2^-8 relative: a face that close to a plane takes the per-fragment test, which decides the same).
+__device__ __forceinline__ float pack_depth_range(float z0, float z1, float z2)
+{
+    const float zlo = fminf(fminf(z0, z1), z2), zhi = fmaxf(fmaxf(z0, z1), z2);
+    const float lo = zlo * (1.f - 1e-4f), hi = zhi * (1.f + 1e-4f);
+    const unsigned lo16 = zlo > 0.f ? (unsigned)__float_as_int(lo) >> 16 : 0xff80u;                      // else -inf: never inside
+    const unsigned hi16 = hi > 0.f ? ((unsigned)__float_as_int(hi) + 0xffffu) >> 16 : 0x7f80u;         // else +inf (a NaN stays a NaN)
+    return __int_as_float((int)(lo16 | hi16 << 16));
+}
+__device__ __forceinline__ bool depth_range_inside(float zr, float near, float far)
+{
+    const unsigned u = (unsigned)__float_as_int(zr);
+    return __int_as_float((int)(u << 16)) > near && __int_as_float((int)(u & 0xffff0000u)) < far;
+}
+
 __device__ __forceinline__ void build_record(const float* __restrict__ f, float* __restrict__ rec,
                                              short4* __restrict__ rect, float margin, int IS,
                                              float* __restrict__ info27)
@@ -268,8 +293,13 @@ __device__ __forceinline__ void build_record(const float* __restrict__ f, float*
         // the near-tie margin of the backward's distance code (sr_backward.h read it off hk2 with an IEEE division in every wave):
         // the same expression, once per face
         rec[R_TIE] = (__float_as_int(rec[R_FLAGS]) & 16) ? near_tie_scale(rec[R_HK2], rec[R_HK2 + 1], rec[R_HK2 + 2]) : 0.f;
+        // what every backward wave of the face would derive again (sr_backward.h: prologue): the heights and the padded depth range
+        {
+            const bool well = (__float_as_int(rec[R_FLAGS]) & 16) != 0;
 #pragma unroll
-        for (int k = 44; k < REC; k++) rec[k] = 0.f;                // padding: defined bytes in the workspace
+            for (int k = 0; k < 3; k++) rec[R_HS + k] = well ? __builtin_amdgcn_sqrtf(rec[R_HK2 + k]) : 0.f;
+            rec[R_ZR] = pack_depth_range(f[2], f[5], f[8]);
+        }
     }
     if (info27) {   // reference layout, for callers that still want the tensor
 #pragma unroll
