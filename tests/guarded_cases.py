@@ -613,12 +613,7 @@ FP64_ATOMIC = dict(exact=False, atomic='sr_fp64.hip: backward_kernel', tol=1e-9,
                    tol_from='tests/test_raster_fp64_gpu.py::test_every_mode_combination_against_the_double_oracle')
 
 
-def _raster_batch(N, F):
-    """(face_vertices [N,F,3,3], near, far): the first F faces of the level-4 blob (320 faces), N frames of its turn."""
-    fv, _, near, far = synth.raster_batch(4, max(N, 3), count=N)
-    assert 1 <= F <= fv.shape[1]
-    fv = fv[:, np.linspace(0, fv.shape[1] - 1, F).astype(np.int64)]
-    return np.ascontiguousarray(fv), near, far
+from raster_harness import raster_batch as _raster_batch             # noqa: E402 (the raster tests render the same batch)
 
 
 def _add_raster(N, F, IS, C=3, modes=None, surface=0, dtype=torch.float32, **kw):

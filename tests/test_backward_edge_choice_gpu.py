@@ -26,15 +26,14 @@ import math
 
 import numpy as np
 import pytest
-import torch
 
+import raster_harness as rh
 from lasr_amd import synth
-from lasr_amd.soft_renderer import functional as srf
+from raster_harness import GRAD_REL, rot as _rot, tri as _tri
 
 IS = 32
 SIGMA = 7e-3
 NEAR, FAR = 1.0, 5.0
-GRAD_REL = 1e-3
 MAX_FRAMES = 64
 NEAR_TIE, NEAR_TIE_ABS = 0.985, 2.4e-6      # sr_device.h
 # A pixel is a probe for a face it lies inside of, or outside of at a squared distance below STRONG x threshold: D = sigmoid(-d^2 / sigma)
@@ -45,22 +44,14 @@ NEAR_TIE, NEAR_TIE_ABS = 0.985, 2.4e-6      # sr_device.h
 STRONG = 0.5
 
 
-def _tri(xy, z=(2.5, 3.0, 3.5)):
-    return [[x, y, zz] for (x, y), zz in zip(xy, z)]
-
-
 def _rev(t):
     return [t[0], t[2], t[1]]
 
 
 _AX = 1. / 32 + 2e-4                            # 2e-4 beside a pixel-centre column
 _ACUTE = _tri([(-0.5 + _AX, -0.4), (0.5 + _AX, -0.4), (_AX, 0.55)])
-_OBT = _tri([(0.02, 0.17), (-0.6, -0.15), (0.6, -0.1)])            # obtuse at its FIRST vertex
+_OBT = _tri(rh.OBTUSE)                                             # obtuse at its FIRST vertex
 _SLIVER = _tri([(-0.6, 0.6), (0.6, 0.604), (0.0, 0.607)], (3.2, 3.3, 3.4))
-
-
-def _rot(t, k):                                  # vertex j of the result = vertex (j - k) % 3 of t: the first vertex moves to index k
-    return [t[(j - k) % 3] for j in range(3)]
 
 
 def _shift(t, dx, dy):
@@ -225,25 +216,12 @@ KW = dict(synth.LASR_MODES, near=NEAR, far=FAR, sigma_val=SIGMA)
 
 
 def oracle_grads(oracle, fv, ft, g, nch, dtype=np.float32):
-    """Reference gradients of an nch-channel pass: each attribute triple is an oracle render of its own, the alpha gradient is
-    counted once (tests/test_raster_parity_gpu.py: test_nine_channel_pass_vs_oracle_at_lasr_size)."""
-    gf, gts = 0, []
-    for k in range(nch // 3):
-        ref = oracle.forward(fv, np.ascontiguousarray(ft[..., 3 * k:3 * k + 3]), IS, dtype=dtype, **KW)
-        ga = g[:, nch:nch + 1] if k == 0 else np.zeros_like(g[:, nch:nch + 1])
-        gf_k, gt_k = oracle.backward(ref, np.concatenate([g[:, 3 * k:3 * k + 3], ga], 1), IS, dtype=dtype, **KW)
-        gf = gf + gf_k
-        gts.append(gt_k)
-    return gf, np.concatenate(gts, -1)
+    """Reference gradients of an nch-channel pass (probes() and oracle_spread() call it anew for every set of frames: not cached)."""
+    return rh.oracle_reference(oracle, fv, ft, IS, None, KW, g=g, dtype=dtype)[1:]
 
 
 def hip_grads(dev, fv, ft, g, nch):
-    tfv = torch.from_numpy(fv).to(dev).requires_grad_(True)
-    tft = torch.from_numpy(ft).to(dev).requires_grad_(True)
-    kw = dict(KW, background_color=[1.] * nch) if nch == 9 else KW
-    img = srf.soft_rasterize(tfv, tft, IS, **kw)
-    img.backward(torch.from_numpy(g).to(dev))
-    return tfv.grad.cpu().numpy(), tft.grad.cpu().numpy()
+    return rh.render(dev, (fv, ft, NEAR, FAR), IS, [1.] * nch if nch == 9 else None, grad=g, sigma_val=SIGMA)[1:]
 
 
 def check_per_frame(a, b, what):

@@ -10,21 +10,20 @@ rebuilt by the backward's own set-up launch.  Also: near / far within 5e-5 relat
 that the per-face `every vertex strictly inside (near, far)` shortcut must be off for the faces at those vertices and the
 per-fragment depth test runs; and near / far read on the device.
 """
-import functools
-import importlib
 import itertools
 
 import numpy as np
 import pytest
 import torch
 
+import raster_harness as rh
 from lasr_amd import _lib, synth
 from lasr_amd.soft_renderer import functional as srf
+from raster_harness import check_grad
 
 pytestmark = pytest.mark.gpu
 
 IS = 64
-GRAD_REL = 1e-3
 NEAR, FAR = 1.0, 5.0
 
 
@@ -62,29 +61,12 @@ def inputs(nch):
     return fv, ft, g
 
 
-@functools.lru_cache(maxsize=None)
 def reference(nch, near, far):
-    """(grad_faces, grad_textures) of the float64 oracle: each attribute triple is an oracle render of its own, the alpha gradient
-    counted once."""
+    """(grad_faces, grad_textures) of the float64 oracle; computed once per case."""
     from oracle import sr_oracle
     fv, ft, g = inputs(nch)
-    kw = dict(synth.LASR_MODES, near=near, far=far)
-    gf, gts = 0, []
-    for k in range(nch // 3):
-        ref = sr_oracle.forward(fv.astype(np.float64), ft[..., 3 * k:3 * k + 3].astype(np.float64), IS, dtype=np.float64, **kw)
-        ga = g[:, nch:nch + 1] if k == 0 else np.zeros_like(g[:, nch:nch + 1])
-        gf_k, gt_k = sr_oracle.backward(ref, np.concatenate([g[:, 3 * k:3 * k + 3], ga], 1).astype(np.float64), IS, dtype=np.float64, **kw)
-        gf = gf + gf_k
-        gts.append(gt_k)
-    gf.setflags(write=False)
-    return gf, np.concatenate(gts, -1)
-
-
-def check(what, a, b):
-    scale = float(np.abs(b).max())
-    d = float(np.abs(a - b).max())
-    print('%s: max diff %.3e of largest gradient %.3e (%.2e)' % (what, d, scale, d / scale))
-    assert scale > 0 and np.isfinite(a).all() and d <= GRAD_REL * scale, (what, d, scale)
+    return rh.cached(('gradient block', nch, near, far),
+                     lambda: rh.oracle_reference(sr_oracle, fv, ft, IS, None, dict(synth.LASR_MODES, near=near, far=far), g=g, dtype=np.float64)[1:])
 
 
 def forward(dev, nch, near, far):
@@ -99,7 +81,6 @@ def forward(dev, nch, near, far):
 @pytest.mark.parametrize('overwrite', [True, False], ids=['stored', 'accumulated'])
 @pytest.mark.parametrize('nch', [3, 6, 9])
 def test_gradients_with_every_flag_combination(cuda, nch, overwrite, reuse):
-    sr_mod = importlib.import_module('lasr_amd.soft_renderer.functional.soft_rasterize')
     tfv, tft, img, g = forward(cuda, nch, NEAR, FAR)
     ctx = img.grad_fn
     fv, tx, soft_colors, aggrs_info = ctx.saved_tensors
@@ -108,15 +89,14 @@ def test_gradients_with_every_flag_combination(cuda, nch, overwrite, reuse):
     fill = float('nan') if overwrite else 0.
     grad_faces = torch.full((N, F, 9), fill, dtype=torch.float32, device=cuda)
     grad_textures = torch.full(tuple(tx.shape), fill, dtype=torch.float32, device=cuda)
-    ws = sr_mod._workspaces[(cuda.index, torch.cuda.current_stream(cuda).cuda_stream)]
     flags = (_lib.SR_GRADS_OVERWRITE if overwrite else 0) | (_lib.SR_RECORDS_VALID if reuse else 0)
-    _lib.call('lasr_sr_backward_ex', fv, tx, soft_colors, aggrs_info, grad_faces, grad_textures, g, ws, ws.numel(), N, F, T, nch, IS,
-              *ctx.near_far, ctx.nf, *ctx.tail, flags, on=cuda)
+    assert ctx.nf is None and ctx.C == nch
+    rh.backward(cuda, rh.record(fv, tx, soft_colors, aggrs_info, rh.operator_workspace(cuda)), g, *ctx.near_far, IS, flags=flags,
+                into=(grad_faces, grad_textures), scalars=ctx.tail)
     srf.invalidate_records(cuda)                 # (a direct call wrote into the operator's workspace)
-    torch.cuda.synchronize()
     gf_ref, gt_ref = reference(nch, NEAR, FAR)
-    check('grad_faces', grad_faces.cpu().numpy().reshape(gf_ref.shape), gf_ref)
-    check('grad_textures', grad_textures.cpu().numpy().reshape(gt_ref.shape), gt_ref)
+    check_grad('grad_faces', grad_faces.cpu().numpy().reshape(gf_ref.shape), gf_ref)
+    check_grad('grad_textures', grad_textures.cpu().numpy().reshape(gt_ref.shape), gt_ref)
 
 
 def _tight_planes():
@@ -134,8 +114,8 @@ def test_vertex_depths_next_to_the_planes(cuda, nch):
     tfv, tft, img, g = forward(cuda, nch, near, far)
     img.backward(g)
     gf_ref, gt_ref = reference(nch, near, far)
-    check('grad_faces', tfv.grad.cpu().numpy(), gf_ref)
-    check('grad_textures', tft.grad.cpu().numpy(), gt_ref)
+    check_grad('grad_faces', tfv.grad.cpu().numpy(), gf_ref)
+    check_grad('grad_textures', tft.grad.cpu().numpy(), gt_ref)
 
 
 @pytest.mark.parametrize('planes', ['wide', 'tight'])
@@ -146,5 +126,5 @@ def test_near_far_read_on_the_device(cuda, nch, planes):
     tfv, tft, img, g = forward(cuda, nch, nf[0], nf[1])
     img.backward(g)
     gf_ref, gt_ref = reference(nch, near, far)
-    check('grad_faces', tfv.grad.cpu().numpy(), gf_ref)
-    check('grad_textures', tft.grad.cpu().numpy(), gt_ref)
+    check_grad('grad_faces', tfv.grad.cpu().numpy(), gf_ref)
+    check_grad('grad_textures', tft.grad.cpu().numpy(), gt_ref)

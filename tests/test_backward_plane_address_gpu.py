@@ -14,18 +14,16 @@ interact).  In every case
   * all planes of a tensor differ from each other (asserted), so exchanging two bases moves the gradients;
   * the backward on the forward's records (LASR_SR_RECORDS_VALID) and the backward that rebuilds them agree bit for bit.
 """
-import ctypes
 import functools
-import math
 
 import numpy as np
 import pytest
 import torch
 
+import raster_harness as rh
 from lasr_amd import _lib, synth
-from test_face_constants_gpu import mesh
+from raster_harness import check_grad
 
-GRAD_REL = 1e-3         # tests/test_raster_parity_gpu.py
 NEAR, FAR = 1.0, 5.0
 SIGMA = 1e-4
 N_MAX = 3
@@ -36,7 +34,7 @@ GENERIC = 'alpha_sum'
 
 @functools.lru_cache(maxsize=None)
 def frames(IS):
-    fv = mesh(IS)
+    fv = rh.constants_mesh(IS)
     third = fv[:1].copy()
     third[..., 0] -= 0.021
     third[..., 1] += 0.017
@@ -66,86 +64,30 @@ def modes(kind):
     return kw
 
 
-_refs = {}
-
-
 def reference(oracle, IS, C, kind):
-    """float64 (grad_faces [3, F, 3, 3], grad_textures [3, F, 3, C]), triple by triple with the alpha gradient counted once
-    (tests/test_raster_parity_gpu.py::test_nine_channel_pass_vs_oracle_at_lasr_size); computed once per case and left unchanged."""
-    key = (IS, C, kind)
-    if key not in _refs:
-        dt = np.float64
-        fv, ft, g = frames(IS).astype(dt), textures(C).astype(dt), upstream(IS, C).astype(dt)
-        kw = modes(kind)
-        gf, gts = 0, []
-        for k in range(C // 3):
-            ref = oracle.forward(fv, np.ascontiguousarray(ft[..., 3 * k:3 * k + 3]), IS, dtype=dt, **kw)
-            ga = g[:, C:C + 1] if k == 0 else np.zeros_like(g[:, C:C + 1])
-            gf_k, gt_k = oracle.backward(ref, np.ascontiguousarray(np.concatenate([g[:, 3 * k:3 * k + 3], ga], 1)), IS, dtype=dt, **kw)
-            gf = gf + gf_k
-            gts.append(gt_k)
-        gt = np.concatenate(gts, -1)
-        gf.setflags(write=False)
-        gt.setflags(write=False)
-        _refs[key] = (gf, gt)
-    return _refs[key]
-
-
-def carve(dev, shapes):
-    """Tensors of `shapes` inside one POISON-filled float buffer: the first starts one float behind the (256-byte aligned) allocation,
-    the gaps are odd numbers of floats, so every start is 4-byte aligned and no more."""
-    sizes = [int(np.prod(s)) for s in shapes]
-    buf = torch.full((sum(sizes) + 8 * len(sizes) + 8,), POISON, device=dev)
-    assert buf.data_ptr() % 256 == 0
-    out, at = [], 1
-    for s, n in zip(shapes, sizes):
-        t = buf[at:at + n].view(*s)
-        assert t.data_ptr() % 8 == 4 and t.is_contiguous()
-        out.append(t)
-        at += n + (4 if n % 2 == 0 else 3)                          # the next start stays odd
-    return buf, out
+    """float64 (grad_faces [3, F, 3, 3], grad_textures [3, F, 3, C]); computed once per case and left unchanged."""
+    return rh.cached(('plane address', IS, C, kind),
+                     lambda: rh.oracle_reference(oracle, frames(IS), textures(C), IS, None, modes(kind), g=upstream(IS, C), dtype=np.float64)[1:])
 
 
 def run(dev, IS, N, C, kind):
-    h = _lib.lib()
     fv, ft = frames(IS)[:N], textures(C)[:N]
     F = fv.shape[1]
-    m = synth.LASR_MODES
-    alpha_id = 1 if kind == GENERIC else 2
-    tail = (float(m['eps']), float(SIGMA), 2, float(math.log(1. / m['dist_eps'] - 1.)), float(m['gamma_val']), 1, alpha_id, 1, 1)
-    tfv = torch.from_numpy(np.array(fv)).to(dev).reshape(N, F, 9).contiguous()
-    tft = torch.from_numpy(np.array(ft)).to(dev).reshape(N, F, 3 * C).contiguous()
-    colors = torch.full((N, C + 1, IS, IS), 7., device=dev)
-    aggrs = torch.empty(N, 2, IS, IS, device=dev)
-    ws = torch.zeros(h.lasr_sr_workspace_bytes(N, F, 3, IS), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    bg = (ctypes.c_float * C)(*([1.] * C))
-    _lib.check(h.lasr_sr_forward_opt(tfv.data_ptr(), tft.data_ptr(), None, aggrs.data_ptr(), colors.data_ptr(), ws.data_ptr(), ws.numel(),
-                                     N, F, 3, C, IS, NEAR, FAR, None, *tail, bg, 0, None, st), 'lasr_sr_forward_opt')
+    tail = rh.tail(SIGMA, 'sum' if kind == GENERIC else 'prod')
+    rec = rh.forward(dev, fv, ft, NEAR, FAR, IS, background=[1.] * C, scalars=tail, fill=7.)
     # the three tensors the backward reads, re-housed at 4-byte aligned starts
-    buf, (c_colors, c_aggrs, c_g) = carve(dev, [(N, C + 1, IS, IS), (N, 2, IS, IS), (N, C + 1, IS, IS)])
-    c_colors.copy_(colors)
-    c_aggrs.copy_(aggrs)
+    buf, (c_colors, c_aggrs, c_g) = rh.carve_odd(dev, [(N, C + 1, IS, IS), (N, 2, IS, IS), (N, C + 1, IS, IS)], POISON)
+    c_colors.copy_(rec.colors)
+    c_aggrs.copy_(rec.aggrs)
     c_g.copy_(torch.from_numpy(np.array(upstream(IS, C)[:N])).to(dev))
     for t in (c_colors, c_aggrs, c_g):                                # every plane of a tensor is its own
         planes = t.reshape(-1, IS * IS).cpu().numpy()
         assert all(not np.array_equal(planes[i], planes[j]) for i in range(len(planes)) for j in range(i))
     out = []
     for flags in (_lib.SR_RECORDS_VALID, 0):
-        gf = torch.zeros(N, F, 9, device=dev)
-        gt = torch.zeros(N, F, 3 * C, device=dev)
-        _lib.check(h.lasr_sr_backward_ex(tfv.data_ptr(), tft.data_ptr(), c_colors.data_ptr(), c_aggrs.data_ptr(), gf.data_ptr(), gt.data_ptr(),
-                                         c_g.data_ptr(), ws.data_ptr(), ws.numel(), N, F, 3, C, IS, NEAR, FAR, None, *tail, flags, st),
-                   'lasr_sr_backward_ex')
+        gf, gt = rh.backward(dev, rec, c_g, NEAR, FAR, IS, flags=flags, colors=c_colors, aggrs=c_aggrs, scalars=tail)
         out.append((gf.cpu().numpy().reshape(N, F, 3, 3), gt.cpu().numpy().reshape(N, F, 3, C)))
     return out
-
-
-def check_grad(what, a, b):
-    scale = float(np.abs(b).max())
-    d = float(np.abs(a - b).max())
-    print('%s: max diff %.3e, largest gradient %.3e (%.2e of it)' % (what, d, scale, d / scale))
-    assert np.isfinite(a).all() and scale > 0 and d <= GRAD_REL * scale, '%s: max diff %.3e vs largest gradient %.3e' % (what, d, scale)
 
 
 @pytest.mark.gpu

@@ -18,60 +18,20 @@ Two comparisons are bit for bit: the backward on the forward's records (LASR_SR_
 them, and one frame rendered at two values of sigma in succession through ONE workspace against each rendered in a fresh workspace
 (nothing a record keeps may depend on an earlier launch's sigma).
 """
-import ctypes
 import functools
-import math
 
 import numpy as np
 import pytest
-import torch
 
+import raster_harness as rh
 from lasr_amd import _lib, synth
+from raster_harness import check_grad, constants_mesh as mesh               # (tests/test_face_constants_cases.py checks the same mesh)
 
 IMG_TOL = 1e-4          # tests/test_raster_parity_gpu.py
-GRAD_REL = 1e-3
 NEAR, FAR = 1.0, 5.0
 N_FRAMES, N_FACES = 2, 20
 SIZES = (32, 24)
 SIGMAS = (1e-4, 1e-5)
-
-
-def _tri(xy, z):
-    return [[x, y, zz] for (x, y), zz in zip(xy, z)]
-
-
-def _rot(t, k):                                  # the first vertex moves to index k
-    return [t[(j - k) % 3] for j in range(3)]
-
-
-@functools.lru_cache(maxsize=None)
-def mesh(IS):
-    """face_vertices [2, 20, 3, 3] (the second frame: the first moved a little), float32."""
-    ax = 1. / IS + 2e-4                          # 2e-4 beside the pixel-centre column right of the image centre
-    obt = [(0.02, 0.17), (-0.6, -0.15), (0.6, -0.1)]            # obtuse at its FIRST vertex
-    faces = [_tri([(-0.5 + ax, -0.4), (0.5 + ax, -0.4), (ax, 0.55)], (2.5, 3.0, 3.5))]
-    for k in range(3):
-        t = _rot(_tri(obt, (2.2, 2.8, 3.1)), k)
-        faces.append([[x + 0.1 * (k - 1), y + 0.25 * (k - 1), z + 0.1 * k] for x, y, z in t])
-    # the sliver, around a pixel centre: its apex 0.008 NDC over the long edge -- below the 0.01 of flag 16 -- at an aspect of 7
-    p = (2 * round(0.8 * IS) + 1 - IS) / IS
-    faces.append(_tri([(p - 0.03, p - 0.004), (p + 0.03, p - 0.003), (p + 0.004, p + 0.0045)], (3.2, 3.3, 3.4)))
-    faces.append(_tri([(2.0, -0.2), (2.4, -0.1), (2.1, 0.3)], (3.0, 3.0, 3.0)))                # outside the image
-    rng = np.random.default_rng(20)
-    while len(faces) < N_FACES:
-        c = rng.uniform(-0.75, 0.75, 2)
-        a0 = rng.uniform(0, 2 * math.pi)
-        r = rng.uniform(0.12, 0.25, 3)
-        ang = a0 + np.array([0., 2.1, 4.2]) + rng.uniform(-0.3, 0.3, 3)
-        if rng.uniform() < 0.5:
-            ang = ang[::-1]                                                                        # both windings
-        faces.append(_tri([(c[0] + r[j] * math.cos(ang[j]), c[1] + r[j] * math.sin(ang[j])) for j in range(3)], rng.uniform(2., 4., 3)))
-    f = np.asarray(faces, np.float32)
-    fv = np.stack([f, f])
-    fv[1, :, :, 0] += 0.013
-    fv[1, :, :, 1] -= 0.007
-    fv.setflags(write=False)
-    return fv
 
 
 @functools.lru_cache(maxsize=None)
@@ -88,81 +48,40 @@ def upstream(IS, C):
     return g
 
 
-def modes(sigma):
-    return dict(synth.LASR_MODES, near=NEAR, far=FAR, sigma_val=sigma)
+def reference(oracle, IS, sigma, C):
+    """(image [N, C + 1, IS, IS], grad_faces, grad_textures [N, F, 3, C]) of the oracle; computed once per case."""
+    kw = dict(synth.LASR_MODES, near=NEAR, far=FAR, sigma_val=sigma)
+    return rh.cached(('face constants', IS, sigma, C),
+                     lambda: rh.oracle_reference(oracle, mesh(IS), textures(C), IS, None, kw, g=upstream(IS, C)))
 
 
-_refs = {}
-
-
-def reference(oracle, IS, sigma, C, dtype=np.float32):
-    """(image [N, C + 1, IS, IS], grad_faces, grad_textures [N, F, 3, C]) of the oracle, triple by triple (the alpha gradient counted
-    once: tests/test_raster_parity_gpu.py::test_nine_channel_pass_vs_oracle_at_lasr_size); computed once per case."""
-    key = (IS, sigma, C, np.dtype(dtype).name)
-    if key not in _refs:
-        fv, ft, g = mesh(IS).astype(dtype), textures(C).astype(dtype), upstream(IS, C).astype(dtype)
-        kw = modes(sigma)
-        img, gf, gts = [], 0, []
-        for k in range(C // 3):
-            ref = oracle.forward(fv, np.ascontiguousarray(ft[..., 3 * k:3 * k + 3]), IS, dtype=dtype, **kw)
-            img.append(ref['soft_colors'])
-            ga = g[:, C:C + 1] if k == 0 else np.zeros_like(g[:, C:C + 1])
-            gf_k, gt_k = oracle.backward(ref, np.ascontiguousarray(np.concatenate([g[:, 3 * k:3 * k + 3], ga], 1)), IS, dtype=dtype, **kw)
-            gf = gf + gf_k
-            gts.append(gt_k)
-        _refs[key] = (np.concatenate([p[:, :3] for p in img] + [img[0][:, 3:4]], 1), gf, np.concatenate(gts, -1))
-    return _refs[key]
-
-
-PAIR_WALK = _lib.SrOptions(-1, -1, -1, -1, 0)          # pair_min_tiles = 0: every launch through the pair-walk kernel
+PAIR_WALK = (-1, -1, -1, -1, 0)           # pair_min_tiles = 0: every launch through the pair-walk kernel
 
 
 class Launch:
-    """Device buffers of one case and the two C-ABI calls."""
+    """Device buffers of one case -- inputs, outputs and ONE workspace kept from call to call -- and the two C-ABI calls."""
 
     def __init__(self, dev, IS, sigma, C, frames=slice(None)):
-        self.h = _lib.lib()
-        fv, ft = mesh(IS)[frames], textures(C)[frames]
-        self.N, self.F, self.IS, self.C = fv.shape[0], fv.shape[1], IS, C
-        self.fv = torch.from_numpy(np.ascontiguousarray(fv)).to(dev).reshape(self.N, self.F, 9).contiguous()
-        self.ft = torch.from_numpy(np.ascontiguousarray(ft)).to(dev).reshape(self.N, self.F, 3 * C).contiguous()
-        self.g = torch.from_numpy(np.ascontiguousarray(upstream(IS, C)[frames])).to(dev)
-        self.colors = torch.empty(self.N, C + 1, IS, IS, device=dev)
-        self.aggrs = torch.empty(self.N, 2, IS, IS, device=dev)
-        self.dev = dev
-        self.fresh_workspace()
-        m = synth.LASR_MODES
-        self.tail = lambda s: (float(m['eps']), float(s), 2, float(math.log(1. / m['dist_eps'] - 1.)), float(m['gamma_val']), 1, 2, 1, 1)
-        self.sigma = sigma
-        self.bg = (ctypes.c_float * C)(*([1.] * C))
-        self.st = torch.cuda.current_stream(dev).cuda_stream
+        self.fv, self.ft = mesh(IS)[frames], textures(C)[frames]
+        self.g = np.ascontiguousarray(upstream(IS, C)[frames])
+        self.dev, self.IS, self.C, self.sigma = dev, IS, C, sigma
+        self.rec = None
 
     def fresh_workspace(self):
-        self.ws = torch.zeros(self.h.lasr_sr_workspace_bytes(self.N, self.F, 3, self.IS), dtype=torch.uint8, device=self.dev)
+        self.rec = None
 
     def forward(self, options=None, flags=0, sigma=None):
-        self.colors.fill_(7.)
-        _lib.check(self.h.lasr_sr_forward_opt(self.fv.data_ptr(), self.ft.data_ptr(), None, self.aggrs.data_ptr(), self.colors.data_ptr(),
-                                              self.ws.data_ptr(), self.ws.numel(), self.N, self.F, 3, self.C, self.IS, NEAR, FAR, None,
-                                              *self.tail(self.sigma if sigma is None else sigma), self.bg, flags,
-                                              ctypes.byref(options) if options is not None else None, self.st), 'lasr_sr_forward_opt')
-        return self.colors.cpu().numpy()
+        out = {}
+        if self.rec is not None:
+            out = dict(colors=self.rec.colors.fill_(7.), aggrs=self.rec.aggrs, ws=self.rec.ws)
+        self.rec = rh.forward(self.dev, self.fv, self.ft, NEAR, FAR, self.IS, options=options, flags=flags, background=[1.] * self.C, out=out,
+                              scalars=rh.tail(self.sigma if sigma is None else sigma), fill=7.)
+        return self.rec.colors.cpu().numpy()
 
     def backward(self, flags):
-        gf = torch.zeros(self.N, self.F, 9, device=self.dev)
-        gt = torch.zeros(self.N, self.F, 3 * self.C, device=self.dev)
-        _lib.check(self.h.lasr_sr_backward_ex(self.fv.data_ptr(), self.ft.data_ptr(), self.colors.data_ptr(), self.aggrs.data_ptr(),
-                                              gf.data_ptr(), gt.data_ptr(), self.g.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
-                                              self.N, self.F, 3, self.C, self.IS, NEAR, FAR, None, *self.tail(self.sigma), flags, self.st),
-                   'lasr_sr_backward_ex')
-        return gf.cpu().numpy().reshape(self.N, self.F, 3, 3), gt.cpu().numpy().reshape(self.N, self.F, 3, self.C)
-
-
-def check_grad(what, a, b):
-    scale = float(np.abs(b).max())
-    d = float(np.abs(a - b).max())
-    print('%s: max diff %.3e, largest gradient %.3e (%.2e of it)' % (what, d, scale, d / scale))
-    assert np.isfinite(a).all() and scale > 0 and d <= GRAD_REL * scale, '%s: max diff %.3e vs largest gradient %.3e' % (what, d, scale)
+        N, F = self.fv.shape[:2]
+        gf, gt = rh.backward(self.dev, self.rec, self.g, NEAR, FAR, self.IS, flags=flags, scalars=rh.tail(self.sigma))
+        return gf.cpu().numpy().reshape(N, F, 3, 3), gt.cpu().numpy().reshape(N, F, 3, self.C)
 
 
 @pytest.mark.gpu

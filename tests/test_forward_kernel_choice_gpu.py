@@ -13,18 +13,17 @@ import numpy as np
 import pytest
 import torch
 
+import raster_harness as rh
 from lasr_amd import _lib, synth
 from lasr_amd.soft_renderer import functional as srf
+from raster_harness import BIG, PAIR_TOL, PAIR_WALK, peek_choice
 
 pytestmark = pytest.mark.gpu
 
-BIG = 10 ** 12
 #            coop8_max  coop_max  choose_max   (8x8-pixel tiles)   order_max  pair_min_tiles
 VARIANTS = {'eight waves per 8x8 tile': (BIG, BIG, BIG, -1, BIG),
             'four waves per 8x8 tile': (0, BIG, BIG, -1, BIG),
             'one wave per 8x8 tile': (0, 0, 0, -1, BIG)}
-PAIR_WALK = (0, 0, 0, -1, 0)              # round 6: every launch through the pair-walk kernel
-PAIR_TOL = 1e-6
 DEFAULTS = (2200, 14336, 49152)
 
 
@@ -35,10 +34,7 @@ def thresholds():
 
 
 def render(dev, fv, ft, IS, kw):
-    tfv, tft = torch.from_numpy(fv).to(dev), torch.from_numpy(ft).to(dev)
-    img = srf.soft_rasterize(tfv, tft, IS, **kw)
-    torch.cuda.synchronize()
-    return img.cpu().numpy()
+    return rh.render(dev, (fv, ft), IS, want_aggrs=False, **kw)
 
 
 def all_variants(thresholds, dev, fv, ft, IS, kw):
@@ -73,8 +69,7 @@ def test_every_kernel_gives_the_same_bits_on_ragged_image_sizes(thresholds, orac
 @pytest.mark.parametrize('channels', [6, 9])
 def test_every_kernel_gives_the_same_bits_with_six_and_nine_channels(thresholds, cuda, channels):
     fv, ft, near, far = synth.raster_batch(4, 3, count=2)
-    rng = np.random.default_rng(channels)
-    tex = np.concatenate([ft] + [rng.uniform(-2, 2, ft.shape).astype(np.float32) for _ in range(channels // 3 - 1)], -1)
+    tex = rh.more_channels(ft, channels, np.random.default_rng(channels))
     kw = dict(synth.LASR_MODES, near=near, far=far, background_color=[0.25 * k for k in range(channels)])
     img = all_variants(thresholds, cuda, fv, tex, 72, kw)
     assert img.shape == (2, channels + 1, 72, 72) and np.isfinite(img).all()
@@ -86,15 +81,8 @@ def test_every_kernel_gives_the_same_bits_with_six_and_nine_channels(thresholds,
 
 def test_every_kernel_gives_the_same_bits_when_a_tile_needs_more_than_one_list_round(thresholds, oracle, cuda):
     # 2500 faces in the centre of the image: the tiles there meet more faces than one LDS list holds (1024 / 2048 entries)
-    rng = np.random.default_rng(7)
-    F = 2500
-    c = rng.uniform(-0.15, 0.15, (2, F, 1, 2))
-    tri = c + rng.uniform(-0.08, 0.08, (2, F, 3, 2))
-    z = rng.uniform(2, 4, (2, F, 3, 1))
-    fv = np.concatenate([tri, z], -1).astype(np.float32)
-    fv[0, 0] = [[-1.5, -1.2, 3], [1.4, -1.1, 3.5], [0.1, 1.6, 2.5]]
-    ft = rng.uniform(0, 1, fv.shape).astype(np.float32)
-    kw = dict(synth.LASR_MODES, near=1.0, far=5.0)
+    fv, ft, near, far = rh.long_list()
+    kw = dict(synth.LASR_MODES, near=near, far=far)
     img = all_variants(thresholds, cuda, fv, ft, 64, kw)
     ref = oracle.forward(fv, ft, 64, **kw)
     assert np.abs(img - ref['soft_colors']).max() <= 1e-5
@@ -122,23 +110,16 @@ def test_every_kernel_at_the_launch_sizes_lasr_uses(thresholds, cuda):
 def test_the_device_side_choice_takes_either_kernel_and_the_bits_do_not_change(thresholds, cuda):
     # 6 frames of 64x64 = 384 tiles; the object's bounding boxes cover about half of them.  coop_max between the estimate and
     # the launch size: the device picks four waves per tile; below the estimate: one wave per tile.
-    import importlib
-    sr_mod = importlib.import_module('lasr_amd.soft_renderer.functional.soft_rasterize')
     fv, ft, near, far = synth.raster_batch(4, 3, count=6)
     kw = dict(synth.LASR_MODES, near=near, far=far)
-    h = _lib.lib()
     thresholds('one wave per 8x8 tile')
     want = render(cuda, fv, ft, 64, kw)
-    import ctypes
     seen = {}
     for coop_max in (300, 40):
         srf.set_launch_thresholds(0, coop_max, BIG, 0, BIG)      # fixed tile order: sr_choose_kernel's bounding-box estimate decides
         got = render(cuda, fv, ft, 64, kw)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
-        ws = sr_mod._workspaces[(cuda.index, torch.cuda.current_stream(cuda).cuda_stream)]
-        c = ctypes.c_int(-1)
-        _lib.check(h.lasr_sr_peek_choice(ws.data_ptr(), fv.shape[0], fv.shape[1], ctypes.byref(c), None), 'peek')
-        seen[coop_max] = c.value
+        seen[coop_max] = peek_choice(cuda, fv.shape[0], fv.shape[1])
     assert seen == {300: 1, 40: 0}, seen
 
 
@@ -164,10 +145,8 @@ def test_default_thresholds_pick_by_launch_size(cuda):
 def test_one_and_two_teams_per_tile_agree(cuda):
     # lasr_amd/csrc/sr_forward_pairs.h: SPLIT teams of four waves share a 16x16 tile, team t walks the chunks t, t + SPLIT, ... of the
     # tile's list and the teams' partial states meet at the end -- forced either way by the per-call flags (three and nine channels)
-    from lasr_amd import _lib
     fv, ft, near, far = synth.raster_batch(11, 3, count=5)
-    rng = np.random.default_rng(5)
-    tex9 = np.concatenate([ft] + [rng.uniform(-2, 2, ft.shape).astype(np.float32) for _ in range(2)], -1)
+    tex9 = rh.more_channels(ft, 9, np.random.default_rng(5))
     try:
         srf.set_launch_thresholds(*PAIR_WALK)
         for tex, kw in ((ft, dict(synth.LASR_MODES, near=near, far=far)),
@@ -185,12 +164,7 @@ def test_one_and_two_teams_per_tile_agree(cuda):
 def test_the_pair_walk_handles_faces_that_are_not_tame(thresholds, oracle, cuda):
     # a sliver, a zero-area face, a face in front of the near plane, huge coordinates: records without the tame flag go through
     # the generic arithmetic at the end of each chunk (sr_forward_pairs.h: the slow mask)
-    fv, ft, near, far = synth.raster_batch(4, 3, count=2)
-    fv = fv.copy()
-    fv[0, 0] = [[0, 0, 3], [0.5, 0.5, 3], [1e-7, 0, 3]]
-    fv[0, 1] = [[0.1, 0.1, 3], [0.1, 0.1, 3], [0.1, 0.1, 3]]
-    fv[1, 2, :, 2] = 1e-9
-    fv[1, 3] = [[-3e4, -2e4, 3], [4e4, -1e4, 3], [0, 5e4, 3]]
+    fv, ft, near, far = rh.not_tame()
     kw = dict(synth.LASR_MODES, near=near, far=far)
     img = all_variants(thresholds, cuda, fv, ft, 64, kw)
     ref = oracle.forward(fv, ft, 64, **kw)
@@ -201,26 +175,14 @@ def test_the_pair_walk_handles_faces_that_are_not_tame(thresholds, oracle, cuda)
 
 def _order_table(cuda, N, F, IS):
     """The block -> tile table the last forward call left in the operator's workspace, and the setup kernel's pixel rects."""
-    import importlib
-    sr_mod = importlib.import_module('lasr_amd.soft_renderer.functional.soft_rasterize')
-    ws = sr_mod._workspaces[(cuda.index, torch.cuda.current_stream(cuda).cuda_stream)]
-    up = lambda v: (v + 255) // 256 * 256
-    base = (-ws.data_ptr()) % 256
-    o_rects = base + up(N * F * 48 * 4)
-    o_grects = o_rects + up(N * F * 8)
-    o_order = o_grects + up(N * ((F + 63) // 64) * 8) + 256
-    t8 = (IS + 7) // 8
-    rects = ws[o_rects:o_rects + N * F * 8].view(torch.int16).reshape(N, F, 4).cpu().numpy().astype(np.int64)
-    table = ws[o_order:o_order + N * t8 * t8 * 4].view(torch.int32).cpu().numpy()
-    return table, rects, t8
+    ws = rh.operator_workspace(cuda)
+    return rh.order_table(ws, N, F, IS, 8), rh.pixel_rects(ws, N, F), (IS + 7) // 8
 
 
 @pytest.mark.parametrize('count,IS,channels', [(8, 64, 3), (16, 100, 3), (8, 256, 3), (16, 72, 9), (24, 48, 6), (12, 64, 3), (7, 64, 9)])
 def test_heaviest_first_tile_order_gives_the_same_bits_in_every_kernel(cuda, count, IS, channels):
     fv, ft, near, far = synth.raster_batch(4 if IS < 256 else 8, 5, count=count)
-    rng = np.random.default_rng(count)
-    if channels > 3:
-        ft = np.concatenate([ft] + [rng.uniform(-2, 2, ft.shape).astype(np.float32) for _ in range(channels // 3 - 1)], -1)
+    ft = rh.more_channels(ft, channels, np.random.default_rng(count))
     kw = dict(synth.LASR_MODES, near=near, far=far, background_color=[0.125 * k for k in range(channels)])
     try:
         out = {}
@@ -288,13 +250,9 @@ def test_launches_the_tile_order_does_not_cover_fall_back_to_the_fixed_order(cud
 def test_ordered_launches_choose_on_the_count_of_non_empty_tiles(cuda):
     # 8 frames of 64x64 = 512 tiles.  coop_max x 4/7 below the launch size and choose_max x 7/16 above it: both kernels are launched
     # and decide on the device from sr_order_kernel's count of tiles that meet at least one face (<= coop_max x 3/8: four waves).
-    import ctypes
-    import importlib
-    sr_mod = importlib.import_module('lasr_amd.soft_renderer.functional.soft_rasterize')
     N, IS = 8, 64
     fv, ft, near, far = synth.raster_batch(4, 5, count=N)
     kw = dict(synth.LASR_MODES, near=near, far=far)
-    h = _lib.lib()
     try:
         srf.set_launch_thresholds(0, 0, 0, 0, BIG)
         want = render(cuda, fv, ft, IS, kw)
@@ -303,10 +261,7 @@ def test_ordered_launches_choose_on_the_count_of_non_empty_tiles(cuda):
             srf.set_launch_thresholds(0, coop_max, BIG, BIG, BIG)    # pair walk off: the device-side choice of round 4
             got = render(cuda, fv, ft, IS, kw)
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
-            ws = sr_mod._workspaces[(cuda.index, torch.cuda.current_stream(cuda).cuda_stream)]
-            c = ctypes.c_int(-1)
-            _lib.check(h.lasr_sr_peek_choice(ws.data_ptr(), N, fv.shape[1], ctypes.byref(c), None), 'peek')
-            seen[coop_max] = c.value
+            seen[coop_max] = peek_choice(cuda, N, fv.shape[1])
     finally:
         srf.set_launch_thresholds()
     table, rects, t8 = _order_table(cuda, N, fv.shape[1], IS)
@@ -325,9 +280,7 @@ def test_the_pair_walk_gives_the_same_bits_in_any_tile_order_and_run_after_run(c
     # which workgroup renders which 16x16 tile changes no tile's arithmetic, and nothing in the kernel depends on timing (the
     # lanes' pairing is a function of the pair counts): fixed order, the launch's own order, and a second run are identical
     fv, ft, near, far = synth.raster_batch(4 if IS < 256 else 11, 5, count=count)
-    rng = np.random.default_rng(count)
-    if channels > 3:
-        ft = np.concatenate([ft] + [rng.uniform(-2, 2, ft.shape).astype(np.float32) for _ in range(channels // 3 - 1)], -1)
+    ft = rh.more_channels(ft, channels, np.random.default_rng(count))
     kw = dict(synth.LASR_MODES, near=near, far=far, background_color=[0.125 * k for k in range(channels)])
     try:
         srf.set_launch_thresholds(0, 0, 0, 0, 0)

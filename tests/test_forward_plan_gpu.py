@@ -7,20 +7,16 @@ arithmetic and the generic kernel (another mode combination) within the north-st
 holds them.  Shapes: 2 and 6 frames (6 frames of 64x64 are ordered: 384 tiles, from five frames) of 20x20 (ragged tiles at both
 tile sizes) and 64x64 pixels.  For launches that leave the choice to the device, the plan's source and bound agree with the word
 lasr_sr_peek_choice reads back."""
-import ctypes
-import importlib
-
 import numpy as np
 import pytest
-import torch
 
+import raster_harness as rh
 from lasr_amd import _lib, synth
 from lasr_amd.soft_renderer import functional as srf
+from raster_harness import BIG, PAIR_TOL
 
 pytestmark = pytest.mark.gpu
 
-BIG = 10 ** 12
-PAIR_TOL = 1e-6
 IMG_TOL = 1e-4
 NO_PAIRS = (-1, BIG)                    # order_max_tiles (default), pair_min_tiles
 #  form: (options, flags, same bits as the one-wave kernel?)      `T` stands for the launch's 8x8 tile count
@@ -45,24 +41,18 @@ def settings():
     srf.set_launch_thresholds()
 
 
-def planned(N, F, IS, channels, options, flags, dist=2):
-    o = _lib.SrOptions(*options)
-    p = _lib.SrPlan()
-    _lib.check(_lib.lib().lasr_sr_plan_forward(N, F, 3, channels, IS, dist, 1, 2, 1, 1, flags, ctypes.byref(o), ctypes.byref(p)), 'plan')
-    return p
+def planned(N, F, IS, channels, options, flags, dist='euclidean'):
+    return rh.plan(N, F, channels, IS, options, flags, rh.tail(dist_func=dist))
 
 
 def render(dev, fv, ft, IS, kw):
-    img = srf.soft_rasterize(torch.from_numpy(fv).to(dev), torch.from_numpy(ft).to(dev), IS, **kw)
-    torch.cuda.synchronize()
-    return img.cpu().numpy()
+    return rh.render(dev, (fv, ft), IS, want_aggrs=False, **kw)
 
 
 def batch(N, channels):
     fv, ft, near, far = synth.raster_batch(4, 3, count=N)
-    rng = np.random.default_rng(channels)
-    if channels > 3:                    # attributes of the colours' magnitude: the 1e-6 bars are those of values in [0, 1]
-        ft = np.concatenate([ft] + [rng.uniform(-1, 1, ft.shape).astype(np.float32) for _ in range(channels // 3 - 1)], -1)
+    # attributes of the colours' magnitude: the 1e-6 bars are those of values in [0, 1]
+    ft = rh.more_channels(ft, channels, np.random.default_rng(channels), -1, 1)
     kw = dict(synth.LASR_MODES, near=near, far=far, background_color=[0.125 * k for k in range(channels)])
     return fv, ft, kw
 
@@ -107,7 +97,7 @@ def test_relaxed_arithmetic_and_the_generic_kernel(settings, oracle, cuda, N, IS
     # another mode combination (barycentric distance): the generic kernel, 256 threads per 16x16 tile, whatever the options and flags
     kwg = dict(kw, dist_func='barycentric')
     for options, flags in (((-1,) * 5, 0), ((BIG, BIG, BIG, BIG, 0), _lib.SR_SEGMENTED)):
-        p = planned(N, fv.shape[1], IS, 3, options, flags, dist=1)
+        p = planned(N, fv.shape[1], IS, 3, options, flags, dist='barycentric')
         assert (p.form, p.threads, p.grid, p.ordered, p.both) == (_lib.SR_FORM_GENERIC, 256, N * ((IS + 15) // 16) ** 2, 0, 0)
         settings(options, flags)
         img = render(cuda, fv, ft, IS, kwg)
@@ -116,17 +106,12 @@ def test_relaxed_arithmetic_and_the_generic_kernel(settings, oracle, cuda, N, IS
 
 def test_the_plan_s_device_side_choice_is_what_the_workspace_holds(settings, cuda):
     # 6 frames of 64x64 = 384 tiles (test_forward_kernel_choice_gpu.py: the bounding boxes cover about half of them)
-    sr_mod = importlib.import_module('lasr_amd.soft_renderer.functional.soft_rasterize')
     N, IS = 6, 64
     fv, ft, kw = batch(N, 3)
     F = fv.shape[1]
-    h = _lib.lib()
 
     def peek():
-        ws = sr_mod._workspaces[(cuda.index, torch.cuda.current_stream(cuda).cuda_stream)]
-        c = ctypes.c_int(-1)
-        _lib.check(h.lasr_sr_peek_choice(ws.data_ptr(), N, F, ctypes.byref(c), None), 'peek')
-        return c.value
+        return rh.peek_choice(cuda, N, F)
 
     settings(*FORMS[_lib.SR_FORM_ONE_WAVE][:2])
     want = render(cuda, fv, ft, IS, kw)

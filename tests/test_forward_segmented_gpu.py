@@ -6,13 +6,13 @@ and within 1e-4 of the oracle, gradients of a backward pass that reads the segme
 largest entry; launches outside the small-launch range and other mode combinations ignore the flag bit for bit."""
 import numpy as np
 import pytest
-import torch
 
+import raster_harness as rh
 from lasr_amd import _lib, synth
 from lasr_amd.soft_renderer import functional as srf
+from raster_harness import BIG
 
 pytestmark = pytest.mark.gpu
-BIG = 10 ** 12
 
 
 @pytest.fixture
@@ -23,13 +23,7 @@ def flags():
 
 
 def render(dev, fv, ft, IS, kw, g=None):
-    a = torch.from_numpy(fv).to(dev).requires_grad_(g is not None)
-    b = torch.from_numpy(ft).to(dev).requires_grad_(g is not None)
-    img = srf.soft_rasterize(a, b, IS, **kw)
-    if g is None:
-        return img.detach().cpu().numpy()
-    img.backward(torch.from_numpy(g).to(dev))
-    return img.detach().cpu().numpy(), a.grad.cpu().numpy(), b.grad.cpu().numpy()
+    return rh.render(dev, (fv, ft), IS, want_aggrs=False, grad=g, **kw)
 
 
 @pytest.mark.parametrize('waves', [8, 4])
@@ -58,8 +52,7 @@ def test_segmented_forward_stays_within_1e6_of_the_default_order(flags, oracle, 
 @pytest.mark.parametrize('channels', [6, 9])
 def test_segmented_forward_with_six_and_nine_channels(flags, cuda, channels):
     fv, ft, near, far = synth.raster_batch(8, 3, count=2)
-    rng = np.random.default_rng(channels)
-    tex = np.concatenate([ft] + [rng.uniform(-2, 2, ft.shape).astype(np.float32) for _ in range(channels // 3 - 1)], -1)
+    tex = rh.more_channels(ft, channels, np.random.default_rng(channels))
     kw = dict(synth.LASR_MODES, near=near, far=far, background_color=[0.25 * k for k in range(channels)])
     flags(0)
     want = render(cuda, fv, tex, 128, kw)
@@ -69,13 +62,8 @@ def test_segmented_forward_with_six_and_nine_channels(flags, cuda, channels):
 
 
 def test_segmented_forward_when_a_tile_needs_more_than_one_list_round(flags, cuda):
-    rng = np.random.default_rng(7)
-    F = 2500
-    c = rng.uniform(-0.15, 0.15, (2, F, 1, 2))
-    tri = c + rng.uniform(-0.06, 0.06, (2, F, 3, 2))
-    fv = np.concatenate([tri, rng.uniform(2, 4, (2, F, 3, 1))], -1).astype(np.float32)
-    ft = rng.uniform(0, 1, fv.shape).astype(np.float32)
-    kw = dict(synth.LASR_MODES, near=1.0, far=5.0)
+    fv, ft, near, far = rh.long_list(spread=0.06, big_face=False)
+    kw = dict(synth.LASR_MODES, near=near, far=far)
     flags(0)
     want = render(cuda, fv, ft, 64, kw)
     flags(_lib.SR_SEGMENTED)

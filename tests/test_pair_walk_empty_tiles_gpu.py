@@ -9,90 +9,40 @@ launch's own tile order and once with order_max_tiles = 0: that launch has no ta
 the plan (so the ordered call did have a table), the number of flagged entries found in the table afterwards (so the case is what
 its name says), torch.equal on soft_colors and aggrs_info, no NaN left, and the pair walk's bar against oracle/sr_oracle (1e-6,
 tests/test_forward_kernel_choice_gpu.py)."""
-import ctypes
-import math
-
 import numpy as np
 import pytest
 import torch
 
+import raster_harness as rh
 from lasr_amd import _lib, synth
+from raster_harness import BIG, PAIR_TOL
 
 pytestmark = pytest.mark.gpu
 
-PAIR_TOL = 1e-6
 ONE, TWO = _lib.SR_PAIR_ONE_TEAM, _lib.SR_PAIR_TWO_TEAMS
-BIG = 10 ** 12
-
-
-def _tail():
-    m = synth.LASR_MODES
-    return (float(m['eps']), float(m['sigma_val']), 2, float(math.log(1. / m['dist_eps'] - 1.)), float(m['gamma_val']), 1, 2, 1, 1)
-
-
-_meshes = {}
+#  kind -> (scale, shift) of the level-4 blob (320 faces)
+MESHES = {'small': (0.3, (0.35, -0.3)),                        # a blob a third of the frame wide, off-centre
+          'right of the frame': (None, (5., 0.)),
+          'below the frame': (None, (0., -7.)),
+          'everywhere': (3.5, (0., 0.)),                       # every tile meets a face
+          'plain': (None, (0., 0.))}
 
 
 def mesh(kind, N):
     """(face_vertices [N, F, 3, 3], near, far) of the level-4 blob (320 faces), N frames of its turn."""
-    if (kind, N) not in _meshes:
-        fv, _, near, far = synth.raster_batch(4, max(N, 3), count=N)
-        fv = fv.copy()
-        if kind == 'small':                                    # a blob a third of the frame wide, off-centre
-            fv[..., :2] = fv[..., :2] * 0.3 + np.array([0.35, -0.3], np.float32)
-        elif kind == 'right of the frame':
-            fv[..., 0] += 5.
-        elif kind == 'below the frame':
-            fv[..., 1] -= 7.
-        elif kind == 'everywhere':                             # every tile meets a face
-            fv[..., :2] *= 3.5
-        else:
-            assert kind == 'plain'
-        _meshes[kind, N] = (np.ascontiguousarray(fv), float(near), float(far))
-    return _meshes[kind, N]
-
-
-def carve(dev, shape, offset_floats):
-    """A NaN-filled float tensor of `shape` that starts `offset_floats` floats into its (256-byte aligned) buffer."""
-    n = int(np.prod(shape))
-    buf = torch.full((n + offset_floats,), float('nan'), dtype=torch.float32, device=dev)
-    t = buf[offset_floats:].view(*shape)
-    assert t.data_ptr() % 16 == (4 * offset_floats) % 16
-    return t
+    return rh.cached(('empty tiles', kind, N), lambda: rh.blob(N, *MESHES[kind]))
 
 
 def forward(dev, fv, tex, near, far, IS, C, order_max, flags, bg, offset=0, plain_entry=False):
-    h = _lib.lib()
     N, F = fv.shape[:2]
-    tfv = torch.from_numpy(fv).reshape(N, F, 9).to(dev).contiguous()
-    tft = torch.from_numpy(tex).to(dev).contiguous()
-    colors, aggrs = carve(dev, (N, C + 1, IS, IS), offset), carve(dev, (N, 2, IS, IS), offset)
-    if bg is None:                                             # no background argument: the caller's image is the background
-        for k in range(C):
-            colors[:, k] = 0.25 + 0.0625 * k
-    nbytes = h.lasr_sr_workspace_bytes(N, F, 3, IS)
-    ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    t = _tail()
+    out = dict(colors=rh.carve_at_offset(dev, (N, C + 1, IS, IS), offset), aggrs=rh.carve_at_offset(dev, (N, 2, IS, IS), offset))
+    prefill = [0.25 + 0.0625 * k for k in range(C)] if bg is None else None
     if plain_entry:
-        assert C == 3 and bg is None
-        _lib.check(h.lasr_sr_forward(tfv.data_ptr(), tft.data_ptr(), None, aggrs.data_ptr(), colors.data_ptr(), ws.data_ptr(), nbytes,
-                                     N, F, 3, IS, near, far, *t, st), 'lasr_sr_forward')
-        p = None
+        assert bg is None
+        rec = rh.forward(dev, fv, tex, near, far, IS, prefill=prefill, out=out, plain_entry=True)
     else:
-        options = _lib.SrOptions(0, 0, 0, order_max, 0)
-        p = _lib.SrPlan()
-        assert h.lasr_sr_plan_forward(N, F, 3, C, IS, 2, 1, 2, 1, 1, flags, ctypes.byref(options), ctypes.byref(p)) == 0
-        cbg = (ctypes.c_float * C)(*bg) if bg is not None else None
-        _lib.check(h.lasr_sr_forward_opt(tfv.data_ptr(), tft.data_ptr(), None, aggrs.data_ptr(), colors.data_ptr(), ws.data_ptr(), nbytes,
-                                         N, F, 3, C, IS, near, far, None, *t, cbg, flags, ctypes.byref(options), st), 'lasr_sr_forward_opt')
-    torch.cuda.synchronize()
-    # the order table the call left in its workspace (sr_raster.hip: sr_layout), in 16x16 tiles
-    up = lambda v: (v + 255) // 256 * 256                      # noqa: E731
-    o_order = (-ws.data_ptr()) % 256 + up(N * F * 48 * 4) + up(N * F * 8) + up(N * ((F + 63) // 64) * 8) + 256
-    t16 = (IS + 15) // 16
-    table = ws[o_order:o_order + N * t16 * t16 * 4].view(torch.int32).cpu().numpy()
-    return colors, aggrs, p, table
+        rec = rh.forward(dev, fv, tex, near, far, IS, options=(0, 0, 0, order_max, 0), flags=flags, background=bg, prefill=prefill, out=out)
+    return rec.colors, rec.aggrs, rec.plan, rh.order_table(rec.ws, N, F, IS, 16)
 
 
 def textures(F, N, C, seed=5):

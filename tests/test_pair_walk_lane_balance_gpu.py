@@ -11,49 +11,28 @@ half of a tile (64 candidates against none: the largest transfer, all inside pai
 shrunk to a sliver beside one pixel column (all outside-but-near: the walk moves the maximum); one face, no face; tame and
 non-tame records in one chunk (slow-mask bits stay with their lane); six and nine channels; one and two teams per tile.
 tests/test_pair_walk_lane_balance_cases.py checks on the CPU that these scenes are not background only."""
-import importlib
-
 import numpy as np
 import pytest
-import torch
 
+import raster_harness as rh
 from lasr_amd import _lib, synth
 from lasr_amd.soft_renderer import functional as srf
-
-PAIR_WALK = (0, 0, 0, -1, 0)              # every launch through the pair-walk kernel
-ONE_WAVE = (0, 0, 0, -1, 10 ** 12)        # one wave per 8x8 tile, faces in index order
-PAIR_TOL = 1e-6
+from raster_harness import ONE_WAVE, PAIR_TOL, PAIR_WALK
 
 
 def _stack(shrunk):
     """70 identical triangles at distinct depths in one 16x16 image.  Whole: the vertical edge at x = -0.03 puts the pixel centres
     of columns 0..7 inside and leaves columns 8..15 outside the faces' pixel rect (threshold radius 0.0304).  Shrunk: a sliver
     0.0275 left of column 7's centres (x = -0.0625) and 0.0775 right of column 6's: column 7 is outside but near, nothing else is."""
-    tri = [[-0.09, -0.9], [-0.09, 0.9], [-0.11, 0.]] if shrunk else [[-0.03, -2.5], [-0.03, 2.5], [-3., 0.]]
-    fv = np.zeros((1, 70, 3, 3), np.float32)
-    fv[0, :, :, :2] = np.asarray(tri, np.float32)
-    fv[0, :, :, 2] = (2. + 0.02 * np.arange(70, dtype=np.float32))[:, None]
-    ft = np.random.default_rng(70).uniform(0, 1, fv.shape).astype(np.float32)
-    return fv, ft, 1.0, 5.0
-
-
-def _not_tame():
-    # as tests/test_forward_kernel_choice_gpu.py::test_the_pair_walk_handles_faces_that_are_not_tame: a sliver, a zero-area face,
-    # a face in front of the near plane, huge coordinates -- among the tame faces of the same chunks
-    fv, ft, near, far = synth.raster_batch(4, 3, count=2)
-    fv = fv.copy()
-    fv[0, 0] = [[0, 0, 3], [0.5, 0.5, 3], [1e-7, 0, 3]]
-    fv[0, 1] = [[0.1, 0.1, 3], [0.1, 0.1, 3], [0.1, 0.1, 3]]
-    fv[1, 2, :, 2] = 1e-9
-    fv[1, 3] = [[-3e4, -2e4, 3], [4e4, -1e4, 3], [0, 5e4, 3]]
+    fv, ft, near, far = rh.stack(70)
+    if shrunk:
+        fv[0, :, :, :2] = np.asarray([[-0.09, -0.9], [-0.09, 0.9], [-0.11, 0.]], np.float32)
     return fv, ft, near, far
 
 
 def _channels(C):
     fv, ft, near, far = synth.raster_batch(4, 3, count=2)
-    rng = np.random.default_rng(C)
-    tex = np.concatenate([ft] + [rng.uniform(-2, 2, ft.shape).astype(np.float32) for _ in range(C // 3 - 1)], -1)
-    return fv, tex, near, far
+    return fv, rh.more_channels(ft, C, np.random.default_rng(C)), near, far
 
 
 def _one_face():
@@ -75,12 +54,11 @@ CASES = {
     'stack shrunk to a sliver': (lambda: _stack(True), 16),
     'one face': (_one_face, 16),
     'empty mesh': (_empty, 16),
-    'tame and not tame': (_not_tame, 64),
+    'tame and not tame': (rh.not_tame, 64),
     'six channels': (lambda: _channels(6), 48),
     'nine channels': (lambda: _channels(9), 48),
     'three frames': (lambda: synth.raster_batch(4, 3, count=3), 64),
 }
-_refs = {}
 
 
 def background(C):
@@ -88,48 +66,18 @@ def background(C):
 
 
 def oracle_image(oracle, name):
-    """The oracle's image of a case, [N, C + 1, IS, IS] (alpha last); computed once, triple by triple for six and nine channels."""
-    if name not in _refs:
-        build, IS = CASES[name]
-        fv, ft, near, far = build()
-        C = ft.shape[-1]
-        bg = background(C)
-        if fv.shape[1] == 0:                # (the oracle's wrapper cannot shape zero faces: K.cu:458-482 with no fragment)
-            img = np.zeros((fv.shape[0], C + 1, IS, IS), np.float32)
-            img[:, :C] = np.asarray(bg, np.float32)[None, :, None, None]
-            img.setflags(write=False)
-            _refs[name] = img
-            return img
-        parts = [oracle.forward(fv, np.ascontiguousarray(ft[..., k:k + 3]), IS,
-                                **dict(synth.LASR_MODES, near=near, far=far, background_color=bg[k:k + 3]))['soft_colors']
-                 for k in range(0, C, 3)]
-        img = np.concatenate([p[:, :3] for p in parts] + [parts[0][:, 3:4]], 1)
-        img.setflags(write=False)
-        _refs[name] = img
-    return _refs[name]
-
-
-class _Ctx:                                 # what SoftRasterizeFunction.forward needs of an autograd context: it keeps aggrs_info
-    def save_for_backward(self, *t):
-        self.saved = t
-
-    def mark_non_differentiable(self, *t):
-        pass
+    """The oracle's image of a case, [N, C + 1, IS, IS] (alpha last); computed once."""
+    def compute():
+        fv, ft, near, far = CASES[name][0]()
+        return rh.oracle_reference(oracle, fv, ft, CASES[name][1], background(ft.shape[-1]), dict(synth.LASR_MODES, near=near, far=far))[0]
+    return rh.cached(('lane balance', name), compute)
 
 
 def render(dev, name):
     """(soft_colors, aggrs_info) of a case through the operator's forward, with the launch options and flags in force."""
-    sr_mod = importlib.import_module('lasr_amd.soft_renderer.functional.soft_rasterize')
     build, IS = CASES[name]
-    fv, ft, near, far = build()
-    m = synth.LASR_MODES
-    ctx = _Ctx()
-    img = sr_mod.SoftRasterizeFunction.forward(
-        ctx, torch.from_numpy(fv).to(dev), torch.from_numpy(ft).to(dev), IS, background(ft.shape[-1]), near, far, m['fill_back'],
-        m['eps'], m['sigma_val'], m['dist_func'], m['dist_eps'], m['gamma_val'], m['aggr_func_rgb'], m['aggr_func_alpha'],
-        m['texture_type'])
-    torch.cuda.synchronize()
-    return img.cpu().numpy(), ctx.saved[3].cpu().numpy()
+    scene = build()
+    return rh.render(dev, scene, IS, background(scene[1].shape[-1]))
 
 
 @pytest.fixture

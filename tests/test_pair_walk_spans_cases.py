@@ -17,6 +17,7 @@ import pytest
 import bench
 import pair_spans_restated as ps
 from lasr_amd import synth
+from raster_harness import hand_made
 
 BENCH_FRAMES = (0, 37, 101)
 EXTRA_SHARE_MEASURED = 0.00074           # spans beyond the per-pixel test on the bench frames, as a share of that test's pairs
@@ -56,20 +57,6 @@ def test_bench_frames_lose_no_pair_and_gain_few(fr):
     assert int((real & ~pixel).sum()) == 0                      # (the line test itself keeps every exact pair)
     assert not (span & ~rect).any()
     assert extra <= 2 * EXTRA_SHARE_MEASURED * pixel.sum()
-
-
-def hand_made():
-    """name -> one face [3, 3]; coordinates chosen for 32 pixels (centres at odd multiples of 1/32)."""
-    z = 3.
-    return {
-        'sliver': [[-0.8, -0.31, z], [0.7, -0.29, z], [0.7, -0.315, z]],                                  # 0.02 high: well conditioned, barely
-        'edge-on, flag 16 clear': [[0., 0., z], [0.5, 0.5, z], [1e-7, 0., z]],
-        'A == 0 on a pixel-centre row': [[-0.4, 0.03125, z], [0.5, 0.03125, z], [0.1, 0.6, z]],
-        'edge through pixel centres': [[-0.46875, -0.46875, z], [0.53125, 0.53125, z], [-0.5, 0.5, z]],
-        'half outside the image': [[0.6, -0.3, z], [1.8, 0.2, z], [0.7, 0.9, z]],
-        'cut by the ragged edge': [[0.55, -0.95, z], [0.98, -0.6, z], [0.7, -0.2, z]],
-        'rect covers a whole tile': [[-1.1, -0.5, z], [0.45, -0.45, z], [-0.5, 1.2, z]],
-    }
 
 
 @pytest.mark.parametrize('IS', [32, 24])

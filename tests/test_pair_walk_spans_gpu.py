@@ -13,49 +13,29 @@ channels, one and two teams, with and without the background argument.
 Asserted: soft_colors within the pair walk's 1e-6 of oracle/sr_oracle; the running-maximum plane torch.equal to the one-wave
 kernel's; no NaN left; lasr_sr_backward_ex on that forward within 1e-3 (of the largest reference magnitude) of the oracle's
 gradients.  One case runs the transpose's selftest entry point on random words, the identity, all-ones and single-bit rows."""
-import ctypes
-import math
-
 import numpy as np
 import pytest
 import torch
 
-from lasr_amd import _lib, synth
-from test_pair_walk_chunk_deal_gpu import stack
-from test_pair_walk_spans_cases import hand_made
 import pair_spans_restated as ps
+import raster_harness as rh
+from lasr_amd import _lib, synth
+from raster_harness import GRAD_REL, ONE_WAVE, PAIR_TOL, PAIR_WALK, hand_made
 
 pytestmark = pytest.mark.gpu
 
-PAIR_TOL = 1e-6
-GRAD_REL = 1e-3
 ONE, TWO = _lib.SR_PAIR_ONE_TEAM, _lib.SR_PAIR_TWO_TEAMS
-BIG = 10 ** 12
-PAIR_WALK = (0, 0, 0, -1, 0)              # lasr_sr_options: every launch through the pair walk
-ONE_WAVE = (0, 0, 0, -1, BIG)             # one wave per 8x8 tile, faces in index order
-
-
-def _tail():
-    m = synth.LASR_MODES
-    return (float(m['eps']), float(m['sigma_val']), 2, float(math.log(1. / m['dist_eps'] - 1.)), float(m['gamma_val']), 1, 2, 1, 1)
-
-
-def _blob(N, scale=1.):
-    fv, _, near, far = synth.raster_batch(4, max(N, 3), count=N)
-    fv = fv.copy()
-    fv[..., :2] *= scale
-    return np.ascontiguousarray(fv), float(near), float(far)
 
 
 def _stack(K):
-    fv, _, near, far = stack(K)
+    fv, _, near, far = rh.stack(K)
     return fv, near, far
 
 
 def _hand_made():
     """One frame: the hand-made faces, two records that are not tame (a zero-area face, huge coordinates) and 40 tame faces of the
     blob -- 49 entries, one chunk wherever they meet."""
-    blob, near, far = _blob(3)
+    blob, near, far = rh.blob(3, 1.)
     hm = np.asarray(list(hand_made().values()), np.float32)
     hm[:, :, 2] = 0.5 * (near + far) + 0.01 * np.arange(len(hm), dtype=np.float32)[:, None]
     odd = np.asarray([[[0.1, 0.1, 0], [0.1, 0.1, 0], [0.1, 0.1, 0]], [[-3e4, -2e4, 0], [4e4, -1e4, 0], [0, 5e4, 0]]], np.float32)
@@ -64,25 +44,24 @@ def _hand_made():
 
 
 SCENES = {
-    'plain, 3 frames': lambda: _blob(3),
-    'plain, 8 frames': lambda: _blob(8),
-    'scaled x 3.5, 3 frames': lambda: _blob(3, 3.5),
-    'scaled x 3.5, 8 frames': lambda: _blob(8, 3.5),
+    'plain, 3 frames': lambda: rh.blob(3, 1.),
+    'plain, 8 frames': lambda: rh.blob(8, 1.),
+    'scaled x 3.5, 3 frames': lambda: rh.blob(3, 3.5),
+    'scaled x 3.5, 8 frames': lambda: rh.blob(8, 3.5),
     'stack of 65': lambda: _stack(65),
     'stack of 128': lambda: _stack(128),
     'stack of 129': lambda: _stack(129),
     'stack of 130': lambda: _stack(130),
     'hand-made faces among tame ones': _hand_made,
 }
-_scenes, _refs = {}, {}
 
 
 def scene(name):
-    if name not in _scenes:
+    def build():
         fv, near, far = SCENES[name]()
         fv.setflags(write=False)
-        _scenes[name] = (fv, near, far)
-    return _scenes[name]
+        return fv, near, far
+    return rh.cached(('spans scene', name), build)
 
 
 def textures(F, N, C):
@@ -98,80 +77,44 @@ def upstream(N, C, IS):
 
 
 def reference(oracle, name, IS, C, with_bg):
-    """The oracle's image [N, C + 1, IS, IS] and gradients of a scene, triple by triple (the channels are independent; alpha's
-    upstream gradient goes with the first triple); computed once."""
-    key = (name, IS, C, with_bg)
-    if key not in _refs:
+    """The oracle's image [N, C + 1, IS, IS] and gradients of a scene; computed once."""
+    def compute():
         fv, near, far = scene(name)
         N, F = fv.shape[:2]
-        tex, g, bg = textures(F, N, C), upstream(N, C, IS), background(C, with_bg)
-        kw = dict(synth.LASR_MODES, near=near, far=far)
-        img = np.zeros((N, C + 1, IS, IS), np.float32)
-        gf, gt = 0., np.zeros((N, F, 3, C), np.float32)
-        for k in range(0, C, 3):
-            kw['background_color'] = bg[k:k + 3]
-            ref = oracle.forward(fv, np.ascontiguousarray(tex[..., k:k + 3]), IS, **kw)
-            img[:, k:k + 3], img[:, C] = ref['soft_colors'][:, :3], ref['soft_colors'][:, 3]
-            gk = np.concatenate([g[:, k:k + 3], g[:, C:C + 1] if k == 0 else np.zeros_like(g[:, C:C + 1])], 1)
-            gf_k, gt_k = oracle.backward(ref, np.ascontiguousarray(gk), IS, **kw)
-            gf = gf + gf_k
-            gt[..., k:k + 3] = gt_k.reshape(N, F, 3, 3)
-        _refs[key] = (img, np.asarray(gf).reshape(N, F, 9), gt)
-    return _refs[key]
+        return rh.oracle_reference(oracle, fv, textures(F, N, C), IS, background(C, with_bg), dict(synth.LASR_MODES, near=near, far=far),
+                                   g=upstream(N, C, IS))
+    return rh.cached(('spans reference', name, IS, C, with_bg), compute)
 
 
 def forward(dev, fv, tex, near, far, IS, C, options, flags, with_bg):
-    h = _lib.lib()
-    N, F = fv.shape[:2]
-    tfv = torch.from_numpy(np.array(fv, np.float32)).reshape(N, F, 9).to(dev).contiguous()
-    tft = torch.from_numpy(tex).to(dev).contiguous()
-    colors = torch.full((N, C + 1, IS, IS), float('nan'), device=dev)
-    aggrs = torch.full((N, 2, IS, IS), float('nan'), device=dev)
-    bg = background(C, with_bg)
-    if not with_bg:                                            # no background argument: the caller's image is the background
-        for k in range(C):
-            colors[:, k] = bg[k]
-    nbytes = h.lasr_sr_workspace_bytes(N, F, 3, IS)
-    ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    opt = _lib.SrOptions(*options)
-    p = _lib.SrPlan()
-    assert h.lasr_sr_plan_forward(N, F, 3, C, IS, 2, 1, 2, 1, 1, flags, ctypes.byref(opt), ctypes.byref(p)) == 0
-    cbg = (ctypes.c_float * C)(*bg) if with_bg else None
-    _lib.check(h.lasr_sr_forward_opt(tfv.data_ptr(), tft.data_ptr(), None, aggrs.data_ptr(), colors.data_ptr(), ws.data_ptr(), nbytes,
-                                     N, F, 3, C, IS, near, far, None, *_tail(), cbg, flags, ctypes.byref(opt), st), 'lasr_sr_forward_opt')
-    torch.cuda.synchronize()
-    return tfv, tft, colors, aggrs, ws, p
+    bg = background(C, with_bg)                                # no background argument: the caller's image is the background
+    return rh.forward(dev, fv, tex, near, far, IS, options=options, flags=flags, background=bg if with_bg else None,
+                      prefill=None if with_bg else bg)
 
 
 @pytest.mark.parametrize('IS', [32, 24])
 @pytest.mark.parametrize('name', list(SCENES))
 def test_span_classified_pair_walk_against_the_oracle(oracle, cuda, name, IS):
-    h = _lib.lib()
     fv, near, far = scene(name)
     N, F = fv.shape[:2]
-    st = torch.cuda.current_stream(cuda).cuda_stream
     for C in (3, 6, 9):
         tex = textures(F, N, C)
         g = torch.from_numpy(upstream(N, C, IS)).to(cuda)
         for with_bg in (True, False):
             img_ref, gf_ref, gt_ref = reference(oracle, name, IS, C, with_bg)
-            _, _, _, aggr_one, _, p1 = forward(cuda, fv, tex, near, far, IS, C, ONE_WAVE, 0, with_bg)
-            assert p1.form == _lib.SR_FORM_ONE_WAVE
+            one = forward(cuda, fv, tex, near, far, IS, C, ONE_WAVE, 0, with_bg)
+            aggr_one = one.aggrs
+            assert one.plan.form == _lib.SR_FORM_ONE_WAVE
             for flags, form in ((ONE, _lib.SR_FORM_PAIRS_ONE_TEAM), (TWO, _lib.SR_FORM_PAIRS_TWO_TEAMS)):
                 what = '%s, %d px, %d channels, %s, %s background' % (name, IS, C, 'one team' if flags == ONE else 'two teams',
                                                                       'with' if with_bg else 'no')
-                tfv, tft, colors, aggrs, ws, p = forward(cuda, fv, tex, near, far, IS, C, PAIR_WALK, flags, with_bg)
-                assert p.form == form, what
+                rec = forward(cuda, fv, tex, near, far, IS, C, PAIR_WALK, flags, with_bg)
+                colors, aggrs = rec.colors, rec.aggrs
+                assert rec.plan.form == form, what
                 assert not torch.isnan(colors).any() and not torch.isnan(aggrs).any(), what
                 err = float(np.abs(colors.cpu().numpy() - img_ref).max())
-                gf = torch.zeros(N, F, 9, device=cuda)
-                gt = torch.zeros(N, F, 3, C, device=cuda)
-                _lib.check(h.lasr_sr_backward_ex(tfv.data_ptr(), tft.data_ptr(), colors.data_ptr(), aggrs.data_ptr(), gf.data_ptr(),
-                                                 gt.data_ptr(), g.data_ptr(), ws.data_ptr(), ws.numel(), N, F, 3, C, IS, near, far, None,
-                                                 *_tail(), 0, st), 'lasr_sr_backward_ex')
-                torch.cuda.synchronize()
-                egf = float(np.abs(gf.cpu().numpy() - gf_ref).max() / np.abs(gf_ref).max())
+                gf, gt = rh.backward(cuda, rec, g, near, far, IS)
+                egf = float(np.abs(gf.cpu().numpy().reshape(gf_ref.shape) - gf_ref).max() / np.abs(gf_ref).max())
                 egt = float(np.abs(gt.cpu().numpy() - gt_ref).max() / np.abs(gt_ref).max())
                 print('%s: image %.3e, grad_faces %.3e, grad_textures %.3e (relative to the largest)' % (what, err, egf, egt))
                 assert err <= PAIR_TOL, '%s: %.3e from the oracle' % (what, err)

@@ -24,13 +24,14 @@ import numpy as np
 import pytest
 import torch
 
-from lasr_amd import _lib, synth
+import raster_harness as rh
+from lasr_amd import synth
 from lasr_amd.soft_renderer import functional as srf
 from oracle import sr_ref
+from raster_harness import BIG
 
 pytestmark = pytest.mark.gpu
 
-BIG = 10 ** 12
 VARIANTS = {'default thresholds': (2200, 14336, 49152),
             'eight waves per 8x8 tile': (BIG, BIG, BIG),
             'four waves per 8x8 tile': (0, BIG, BIG),
@@ -47,19 +48,11 @@ def thresholds():
 
 
 def hip_forward(dev, fv, ft, IS, kw):
-    a = torch.from_numpy(fv).to(dev) if isinstance(fv, np.ndarray) else fv
-    b = torch.from_numpy(ft).to(dev) if isinstance(ft, np.ndarray) else ft
-    return srf.soft_rasterize_raw(a, b, IS, kw['background_color'], kw['near'], kw['far'], kw['fill_back'], kw['eps'],
-                                  kw['sigma_val'], kw['dist_func'], kw['dist_eps'], kw['gamma_val'], kw['aggr_func_rgb'],
-                                  kw['aggr_func_alpha'], kw['texture_type'])
+    return rh.render(dev, (fv, ft), IS, raw=True, numpy=False, **kw)
 
 
 def hip_fwd_bwd(dev, fv, ft, IS, kw, g):
-    a = torch.from_numpy(fv).to(dev).requires_grad_(True)
-    b = torch.from_numpy(ft).to(dev).requires_grad_(True)
-    img = srf.soft_rasterize(a, b, IS, **kw)
-    img.backward(g)
-    return img.detach(), a.grad, b.grad
+    return rh.render(dev, (fv, ft), IS, grad=g, numpy=False, **kw)
 
 
 def check_against(img, aggr, gf, gt, ref_img, ref_aggr, ref_gf, ref_gt, hard):

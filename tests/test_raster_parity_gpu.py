@@ -12,28 +12,20 @@ import numpy as np
 import pytest
 import torch
 
+import raster_harness as rh
 from lasr_amd import synth
 from lasr_amd.soft_renderer import functional as srf
+from raster_harness import GRAD_REL
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IMG_TOL = 1e-4
-GRAD_REL = 1e-3
 
 
 def run_hip(dev, fv, ft, IS, g=None, **kw):
-    tfv = torch.from_numpy(fv).to(dev).requires_grad_(g is not None)
-    tft = torch.from_numpy(ft).to(dev).requires_grad_(g is not None)
-    if g is None:
-        img, aggr = srf.soft_rasterize_raw(tfv, tft, IS, kw['background_color'], kw['near'], kw['far'],
-                                           kw['fill_back'], kw['eps'], kw['sigma_val'], kw['dist_func'],
-                                           kw['dist_eps'], kw['gamma_val'], kw['aggr_func_rgb'],
-                                           kw['aggr_func_alpha'], kw['texture_type'])
-        return img.cpu().numpy(), aggr.cpu().numpy()
-    img = srf.soft_rasterize(tfv, tft, IS, **kw)
-    img.backward(torch.from_numpy(g).to(dev))
-    return img.detach().cpu().numpy(), tfv.grad.cpu().numpy(), tft.grad.cpu().numpy()
+    """(image, aggrs_info) of the raw forward, or with g (image, grad_faces, grad_textures) through autograd."""
+    return rh.render(dev, (fv, ft), IS, raw=g is None, grad=g, **kw)
 
 
 def compare(oracle, dev, fv, ft, IS, kw, seed=2, check_grad=True):
@@ -431,8 +423,7 @@ def test_backward_on_the_forwards_records_equals_a_rebuild(cuda):
     h = _lib.lib()
     fv, ft, near, far = synth.raster_batch(8, 5, count=3)
     N, F, IS = fv.shape[0], fv.shape[1], 96
-    m = synth.LASR_MODES
-    tail = (float(m['eps']), float(m['sigma_val']), 2, float(math.log(1. / m['dist_eps'] - 1.)), float(m['gamma_val']), 1, 2, 1, 1)
+    tail = rh.tail()
     tfv = torch.from_numpy(fv).to(cuda).reshape(N, F, 9).contiguous()
     tft = torch.from_numpy(ft).to(cuda).reshape(N, F, 9).contiguous()
     g = torch.from_numpy(synth.upstream_grad(N, IS, 5)).to(cuda)
@@ -442,12 +433,10 @@ def test_backward_on_the_forwards_records_equals_a_rebuild(cuda):
     st = torch.cuda.current_stream().cuda_stream
     _lib.check(h.lasr_sr_forward_ex(tfv.data_ptr(), tft.data_ptr(), None, aggrs.data_ptr(), colors.data_ptr(), ws.data_ptr(),
                                     ws.numel(), N, F, 3, 3, IS, float(near), float(far), None, *tail, 0, st), 'forward_ex')
+    rec = rh.record(tfv, tft, colors, aggrs, ws)
     out = []
     for flags in (_lib.SR_RECORDS_VALID, 0):
-        gf, gt = torch.zeros(N, F, 9, device=cuda), torch.zeros(N, F, 9, device=cuda)
-        _lib.check(h.lasr_sr_backward_ex(tfv.data_ptr(), tft.data_ptr(), colors.data_ptr(), aggrs.data_ptr(), gf.data_ptr(),
-                                         gt.data_ptr(), g.data_ptr(), ws.data_ptr(), ws.numel(), N, F, 3, 3, IS, float(near),
-                                         float(far), None, *tail, flags, st), 'backward_ex')
+        gf, gt = rh.backward(cuda, rec, g, near, far, IS, flags=flags)
         out.append((gf.cpu().numpy(), gt.cpu().numpy()))
     assert np.abs(out[0][0]).max() > 0
     assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
@@ -456,14 +445,9 @@ def test_backward_on_the_forwards_records_equals_a_rebuild(cuda):
     small = h.lasr_sr_workspace_bytes(N, F, 3, 0)
     assert small < ws.numel()
     ws2 = torch.empty(small, dtype=torch.uint8, device=cuda)
-    gf, gt = torch.zeros(N, F, 9, device=cuda), torch.zeros(N, F, 9, device=cuda)
-    _lib.check(h.lasr_sr_backward_ex(tfv.data_ptr(), tft.data_ptr(), colors.data_ptr(), aggrs.data_ptr(), gf.data_ptr(),
-                                     gt.data_ptr(), g.data_ptr(), ws2.data_ptr(), ws2.numel(), N, F, 3, 3, IS, float(near),
-                                     float(far), None, *tail, 0, st), 'backward_ex on a records-only workspace')
+    gf, gt = rh.backward(cuda, rec, g, near, far, IS, ws=ws2)
     assert np.array_equal(gf.cpu().numpy(), out[1][0]) and np.array_equal(gt.cpu().numpy(), out[1][1])
-    assert h.lasr_sr_backward_ex(tfv.data_ptr(), tft.data_ptr(), colors.data_ptr(), aggrs.data_ptr(), gf.data_ptr(), gt.data_ptr(),
-                                 g.data_ptr(), ws2.data_ptr(), small - 1, N, F, 3, 3, IS, float(near), float(far), None, *tail, 0,
-                                 st) == -3
+    assert rh.backward(cuda, rec, g, near, far, IS, ws=ws2, nbytes=small - 1, into=(gf, gt), check=False) == -3
 
 
 def test_invalidate_records_accepts_a_device_without_an_index(cuda):
@@ -495,8 +479,7 @@ def test_backward_may_overwrite_uninitialised_gradient_buffers(cuda, channels):
     N, F, IS, C = fv.shape[0], fv.shape[1], 96, channels
     rng = np.random.default_rng(C)
     attrs = rng.uniform(0, 1, (N, F, 3, C)).astype(np.float32)
-    m = synth.LASR_MODES
-    tail = (float(m['eps']), float(m['sigma_val']), 2, float(math.log(1. / m['dist_eps'] - 1.)), float(m['gamma_val']), 1, 2, 1, 1)
+    tail = rh.tail()
     tfv = torch.from_numpy(fv).to(cuda).reshape(N, F, 9).contiguous()
     tft = torch.from_numpy(attrs).to(cuda).contiguous()
     g = torch.from_numpy(rng.standard_normal((N, C + 1, IS, IS)).astype(np.float32) / (IS * IS)).to(cuda)
@@ -506,13 +489,11 @@ def test_backward_may_overwrite_uninitialised_gradient_buffers(cuda, channels):
     st = torch.cuda.current_stream().cuda_stream
     _lib.check(h.lasr_sr_forward_ex(tfv.data_ptr(), tft.data_ptr(), None, aggrs.data_ptr(), colors.data_ptr(), ws.data_ptr(),
                                     ws.numel(), N, F, 3, C, IS, float(near), float(far), None, *tail, 0, st), 'forward_ex')
+    rec = rh.record(tfv, tft, colors, aggrs, ws)
     out = []
     for flags, init in ((0, 0.0), (_lib.SR_GRADS_OVERWRITE, float('nan'))):
-        gf = torch.full((N, F, 9), init, device=cuda)
-        gt = torch.full((N, F, 3, C), init, device=cuda)
-        _lib.check(h.lasr_sr_backward_ex(tfv.data_ptr(), tft.data_ptr(), colors.data_ptr(), aggrs.data_ptr(), gf.data_ptr(),
-                                         gt.data_ptr(), g.data_ptr(), ws.data_ptr(), ws.numel(), N, F, 3, C, IS, float(near),
-                                         float(far), None, *tail, flags, st), 'backward_ex')
+        gf, gt = rh.backward(cuda, rec, g, near, far, IS, flags=flags,
+                             into=(torch.full((N, F, 9), init, device=cuda), torch.full((N, F, 3, C), init, device=cuda)))
         out.append((gf.cpu().numpy(), gt.cpu().numpy()))
     assert np.abs(out[0][0]).max() > 0 and not out[0][0][1, :40].any()
     assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])

@@ -14,22 +14,19 @@ own.
 Every output starts as poison: faces_info and aggrs_info are pure outputs in both precisions.  Only what include/lasr_sr.h has
 the caller pre-fill is pre-filled, for the float64 entry points: soft_colors with the background, the gradients with zeros.
 The generic 16x16 kernel runs at three channels only: six and nine channels exist in LASR's mode combination alone."""
-import ctypes
-import math
-
 import numpy as np
 import pytest
 import torch
 
 import guarded
-from guarded_cases import _raster_batch
-from lasr_amd import _lib, synth
+import raster_harness as rh
+from lasr_amd import _lib
+from raster_harness import BIG
 
 pytestmark = pytest.mark.gpu
 
-BIG = 10 ** 12
 SIZES = [(1, 1, 8), (3, 65, 24), (2, 257, 33), (8, 65, 64)]
-LASR, HARD = (2, 1, 2), (0, 0, 0)                           # (dist, rgb, alpha) ids of LASR's modes and of the all-hard combination
+LASR, HARD = {}, dict(dist_func='hard', aggr_func_rgb='hard', aggr_func_alpha='hard')       # LASR's modes and the all-hard combination
 #             name: (coop8_max, coop_max, choose_max, pair_min_tiles), forward flags, modes, plan forms accepted
 KERNELS = {'one wave': ((0, 0, 0, BIG), 0, LASR, (_lib.SR_FORM_ONE_WAVE,)),
            'four waves': ((0, BIG, BIG, BIG), 0, LASR, (_lib.SR_FORM_FOUR_WAVES,)),
@@ -40,26 +37,13 @@ KERNELS = {'one wave': ((0, 0, 0, BIG), 0, LASR, (_lib.SR_FORM_ONE_WAVE,)),
 FP64_GRAD_REL = 1e-9                                         # tests/test_raster_fp64_gpu.py
 
 
-def tail(modes):
-    m = synth.LASR_MODES
-    return (float(m['eps']), float(m['sigma_val']), modes[0], float(math.log(1. / m['dist_eps'] - 1.)), float(m['gamma_val']), modes[1],
-            modes[2], 1, 1)
-
-
 def inputs(dev, N, F, IS, C, dtype=torch.float32):
-    fv, near, far = _raster_batch(N, F)
+    fv, near, far = rh.raster_batch(N, F)
     g = torch.Generator().manual_seed(60 + C)
     tfv = torch.from_numpy(fv).reshape(N, F, 9).to(dtype).to(dev).contiguous()
     tft = torch.rand(N, F, 3 * C, generator=g).to(dtype).to(dev)
     up = (torch.randn(N, C + 1, IS, IS, generator=g) / (IS * IS)).to(dtype).to(dev)
     return tfv, tft, up, float(near), float(far)
-
-
-def plan(N, F, C, IS, modes, flags, options):
-    out = _lib.SrPlan()
-    rc = _lib.lib().lasr_sr_plan_forward(N, F, 3, C, IS, modes[0], modes[1], modes[2], 1, 1, flags, ctypes.byref(options), ctypes.byref(out))
-    assert rc == 0
-    return out
 
 
 def run_fp32(dev, fill, N, F, IS, C, options, flags, modes, ws_is=None, with_faces_info=False):
@@ -69,19 +53,15 @@ def run_fp32(dev, fill, N, F, IS, C, options, flags, modes, ws_is=None, with_fac
     tfv, tft, up, near, far = inputs(dev, N, F, IS, C)
     new = lambda *s: g.allocate(s, torch.float32, dev)                                            # noqa: E731
     nbytes = h.lasr_sr_workspace_bytes(N, F, 3, IS)
-    ws = g.allocate((nbytes,), torch.uint8, dev)
-    colors, aggrs = new(N, C + 1, IS, IS), new(N, 2, IS, IS)
-    finfo = new(N, F, 27) if with_faces_info else None
-    st = torch.cuda.current_stream(dev).cuda_stream
-    bg = (ctypes.c_float * C)(*([1.] * C))
-    t = tail(modes)
-    _lib.check(h.lasr_sr_forward_opt(tfv.data_ptr(), tft.data_ptr(), finfo.data_ptr() if finfo is not None else None, aggrs.data_ptr(),
-                                     colors.data_ptr(), ws.data_ptr(), nbytes, N, F, 3, C, IS, near, far, None, *t, bg, flags,
-                                     ctypes.byref(options), st), 'lasr_sr_forward_opt')
-    out = {'soft_colors': colors, 'aggrs_info': aggrs}
-    if finfo is not None:
-        out['faces_info'] = finfo
-    bws, bbytes = ws, nbytes
+    bufs = dict(ws=g.allocate((nbytes,), torch.uint8, dev), colors=new(N, C + 1, IS, IS), aggrs=new(N, 2, IS, IS))
+    if with_faces_info:
+        bufs['faces_info'] = new(N, F, 27)
+    t = rh.tail(**modes)
+    rec = rh.forward(dev, tfv, tft.view(N, F, 3, C), near, far, IS, options=options, flags=flags, background=[1.] * C, out=bufs, scalars=t)
+    out = {'soft_colors': rec.colors, 'aggrs_info': rec.aggrs}
+    if rec.faces_info is not None:
+        out['faces_info'] = rec.faces_info
+    bws = None
     if ws_is is not None:                                     # the backward-only size: records and rects, no tile-order table
         bbytes = h.lasr_sr_workspace_bytes(N, F, 3, ws_is)
         assert bbytes < nbytes
@@ -89,15 +69,12 @@ def run_fp32(dev, fill, N, F, IS, C, options, flags, modes, ws_is=None, with_fac
     for name, bflags in (('records', _lib.SR_RECORDS_VALID | _lib.SR_GRADS_OVERWRITE), ('rebuild', _lib.SR_GRADS_OVERWRITE)):
         if ws_is is not None and name == 'records':
             continue                                          # (the small workspace holds no forward's records)
-        gf, gt = new(N, F, 9), new(N, F, 3 * C)
-        _lib.check(h.lasr_sr_backward_ex(tfv.data_ptr(), tft.data_ptr(), colors.data_ptr(), aggrs.data_ptr(), gf.data_ptr(), gt.data_ptr(),
-                                         up.data_ptr(), bws.data_ptr(), bbytes, N, F, 3, C, IS, near, far, None, *t, bflags, st),
-                   'lasr_sr_backward_ex (%s)' % name)
+        gf, gt = rh.backward(dev, rec, up, near, far, IS, flags=bflags, into=(new(N, F, 9), new(N, F, 3 * C)), scalars=t, ws=bws)
         out['grad_faces, ' + name], out['grad_textures, ' + name] = gf, gt
     return out, g.violations(), len(g.allocations)
 
 
-def same_bits(what, a, b):
+def same_outputs(what, a, b):
     assert sorted(a) == sorted(b)
     for k in a:
         x, y = guarded._bits(a[k]), guarded._bits(b[k])
@@ -107,7 +84,7 @@ def same_bits(what, a, b):
 def check_fp32(dev, N, F, IS, C, name, order_max, **kw):
     th, flags, modes, forms = KERNELS[name]
     options = _lib.SrOptions(th[0], th[1], th[2], order_max, th[3])
-    p = plan(N, F, C, IS, modes, flags, options)
+    p = rh.plan(N, F, C, IS, options, flags, rh.tail(**modes))
     what = 'N=%d F=%d IS=%d C=%d, %s, order_max_tiles=%d' % (N, F, IS, C, name, order_max)
     assert p.form in forms, '%s: planned form %d' % (what, p.form)
     runs = []
@@ -115,7 +92,7 @@ def check_fp32(dev, N, F, IS, C, name, order_max, **kw):
         out, bad, n_alloc = run_fp32(dev, fill, N, F, IS, C, options, flags, modes, **kw)
         assert n_alloc >= 6 and not bad, '%s, fill 0x%02X: guard band touched: %s' % (what, fill, bad)
         runs.append(out)
-    same_bits(what, runs[0], runs[1])
+    same_outputs(what, runs[0], runs[1])
     assert bool((runs[0]['soft_colors'] != runs[0]['soft_colors'].reshape(-1)[0]).any())
     return p
 
@@ -153,7 +130,7 @@ def run_fp64(dev, fill, N, F, IS, modes, with_faces_info):
     info_ptr = finfo.data_ptr() if finfo is not None else None
     gf, gt = new(N, F, 9).zero_(), new(N, F, 9).zero_()
     st = torch.cuda.current_stream(dev).cuda_stream
-    t = tail(modes)
+    t = rh.tail(**modes)
     _lib.check(h.lasr_sr_forward_f64(tfv.data_ptr(), tft.data_ptr(), info_ptr, aggrs.data_ptr(), colors.data_ptr(), ws.data_ptr(),
                                      nbytes, N, F, 3, IS, near, far, *t, st), 'lasr_sr_forward_f64')
     _lib.check(h.lasr_sr_backward_f64(tfv.data_ptr(), tft.data_ptr(), colors.data_ptr(), info_ptr, aggrs.data_ptr(), gf.data_ptr(),
@@ -178,7 +155,7 @@ def test_the_float64_entry_points_inside_an_exact_workspace(cuda, N, F, IS, mode
         exact, grads, bad = run_fp64(cuda, fill, N, F, IS, modes, with_faces_info)
         assert not bad, 'fill 0x%02X: guard band touched: %s' % (fill, bad)
         runs.append((exact, grads))
-    same_bits('float64 N=%d F=%d IS=%d' % (N, F, IS), runs[0][0], runs[1][0])
+    same_outputs('float64 N=%d F=%d IS=%d' % (N, F, IS), runs[0][0], runs[1][0])
     for k in runs[0][1]:                                      # double atomics: another order of the same sums
         a, b = runs[0][1][k].cpu().numpy(), runs[1][1][k].cpu().numpy()
         assert np.isfinite(a).all() and np.isfinite(b).all()
