@@ -1443,6 +1443,67 @@ int lasr_meshnbr_test(const void* workspace, size_t workspace_bytes, const unsig
                       void* hip_stream);
 
 /*
+ * ---- Fold penalty of the optimiser: optimize.py --fold_wt / --pierce_wt (lasr_amd/csrc/foldpen.hip, scripts/fold_penalty.py,
+ *      DESIGN.md section 4.21) ----
+ * This project's own addition, as the two blocks above: the reference has no counterpart, nothing of it is restated here, and parity
+ * is to the restatement in tests/foldpen_restated.py and to closed forms only.  A loss on the posed meshes of a step that follows
+ * the two criteria of the neighbour pass above, so that "the penalty is zero" and "eval_shape.py --neighbours reports nothing" mean
+ * the same thing.  x [N,V,3] fp32, the N meshes of a step on one topology; faces [F,3] int32; list: the sorted keys of
+ * lasr_meshnbr_list (layout and ca, cb, kind, same as above); phi: the penalty's angle in radians, 0 < phi <= pi / 2.  The callers'
+ * defaults (weights 0: off; fold_deg 30) are derived from nothing measured on a real reconstruction.
+ *
+ * Crease term, per EDGE pair (i, j): nA, nB, d, qa, qb exactly as the neighbour pass defines them (d negated when `same` is set),
+ *   s = |nA x nB| (the component order of orient's cross product, the dot as there, one square root), theta = atan2(s, -d) in
+ *   [0, pi]: the interior dihedral angle, 0 a complete fold, pi flat.  The value is max(0, phi - theta)^2.  A pair with qa qb = 0 or
+ *   not finite has value 0 and gradient 0, as the evaluation does not count it.  The penalty is a function of the angle, not of its
+ *   cosine: d cos / d theta is 0 at theta = 0, so any function of the cosine alone has no gradient at the complete fold.
+ *   d theta / d x is the closed-form hinge gradient of discrete shells: with x0 = A[(ca+1)%3], x1 = A[(ca+2)%3] (the shared edge),
+ *   x2 = A[ca], x3 = B[cb] (the apexes), e = x1 - x0, GA = -sign(orient(A0, A1, A2, x3)) |e| nA / qa,
+ *   GB = -sign(orient(B0, B1, B2, x2)) |e| nB / qb, tA = ((x2 - x0) . e) / |e|^2, tB = ((x3 - x0) . e) / |e|^2: by x2 GA, by x3 GB,
+ *   by x0 -(1 - tA) GA - (1 - tB) GB, by x1 -tA GA - tB GB.  It is finite and of length 1 / height at the complete fold's
+ *   neighbourhood; at exactly theta = 0 both signs are 0: the kink of the unsigned angle gets gradient 0.
+ * Pierce term, per VERTEX pair: both directed tests of the neighbour pass, with orient and PIERCES as above, strict and without
+ *   contraction.  For a test that holds, with edge (p, q) and triangle (a, b, c) in stored order and n = (b - a) x (c - a):
+ *   delta = min(|orient(a,b,c,p)|, |orient(a,b,c,q)|) / |n|, the distance of the shallower end point from the plane.  The value is
+ *   delta, the depth itself and not its square (with the square the depth decays geometrically and the end point never crosses the
+ *   plane).  The gradient goes to that end point r (p on a tie), sign(orient(a,b,c,r)) n / |n|, and to a, b, c: minus that times the
+ *   barycentric coordinates of r's foot in the plane, l_b = ((r - a) x (c - a)) . n / |n|^2, l_c = ((b - a) x (r - a)) . n / |n|^2,
+ *   l_a = (1 - l_b) - l_c.  The value of the pair is the sum over the directed tests that hold.
+ * loss [N,2] fp32: the crease sum and the pierce sum of each mesh.  Per-entry values are fp32; each sum is accumulated in fp64 over
+ *   the entries in list order (blocks of 256 entries: the lanes of a wave by shuffles, the four waves in order; then the blocks in
+ *   order, as lasr_meshcheck_faces folds its terms) and rounded once.
+ *
+ * lasr_foldpen_forward: the grid is lasr_meshnbr_test's, (list blocks, meshes), one lane per (entry, mesh), which reads the three
+ *   vertices of both faces through `faces`.  Writes values [N,n_list] fp32 (0 for an entry that is not charged) and loss; scratch:
+ *   lasr_foldpen_scratch_bytes(N, n_list) bytes (the block partials).  rows NULL: nothing more.  rows [N,n_list,5,3] fp32: the
+ *   entry's contribution row d value / d vertex is written for lasr_foldpen_backward, zeros for an entry that is not charged (no
+ *   result depends on what the buffer held).  The roles of the five slots:
+ *     vertex pair: 0 the shared vertex; 1, 2 = A[(ca+1)%3], A[(ca+2)%3]; 3, 4 = B[(cb+1)%3], B[(cb+2)%3]
+ *     edge pair:   0 = A[ca]; 1, 2 = A[(ca+1)%3], A[(ca+2)%3]; 3 = B[cb]; 4 unused (zeros)
+ *   Two launches (entries, fold).  A key that names a face outside [0, F) is skipped (value 0, a row of zeros), and so is a pair
+ *   with a face whose index is outside [0, V).
+ * lasr_foldpen_backward: one thread per (mesh, vertex) gathers its rows through an inverted index, a CSR from vertex to
+ *   incidences that the Python layer builds once per topology: vstart int32 [V+1] ascending, inc int32 [n_inc] with
+ *   inc[k] = (entry 5 + slot) 2 + (1 for an edge pair, 0 for a vertex pair), ascending within a vertex.  gverts [N,V,3] is
+ *   OVERWRITTEN with the sum over the vertex's incidences, in that order and in fp32 without contraction, of grad_loss[mesh, plane]
+ *   times the row's 3-vector (plane 0 for an edge pair, 1 for a vertex pair).  An incidence outside the rows is skipped.  One launch.
+ * No floating-point atomics anywhere: two runs give the same bits.  Both are launch-only with static shapes (capturable into a graph).
+ * Checked on the host before any launch (LASR_E_BADARG): 0 <= N <= LASR_MESHCHECK_MAX_FRAMES, V >= 0, 3 V <= INT_MAX,
+ *   0 <= n_list <= LASR_FOLDPEN_MAX_LIST (10 n_list <= INT_MAX), N n_list <= INT_MAX, 0 <= F <= LASR_MESHCHECK_MAX_FACES and
+ *   0 < phi <= pi / 2 (forward), 0 <= n_inc <= 5 n_list (backward); then N == 0, F == 0 or n_list == 0 (forward) is LASR_OK with
+ *   nothing launched and nothing written, and N == 0 or V == 0 (backward) likewise; n_list == 0 or n_inc == 0 (backward) zeroes
+ *   gverts and launches nothing; then V >= 1, every pointer but rows (forward) non-NULL and no two buffers the same;
+ *   LASR_E_WORKSPACE when scratch_bytes < lasr_foldpen_scratch_bytes(N, n_list), which is 0 for sizes outside these limits.  Device
+ *   contents are not read on the host.  These launches are not in the lasr_prof_* kernel table.
+ */
+#define LASR_FOLDPEN_MAX_LIST 214748364
+size_t lasr_foldpen_scratch_bytes(int N, int n_list);
+int lasr_foldpen_forward(const float* x, const int* faces, const unsigned long long* list, int n_list, float phi, float* values,
+                         float* rows, void* scratch, size_t scratch_bytes, float* loss, int N, int V, int F, void* hip_stream);
+int lasr_foldpen_backward(const float* rows, const int* vstart, const int* inc, int n_inc, const float* grad_loss, float* gverts, int N,
+                          int V, int n_list, void* hip_stream);
+
+/*
  * ---- Structural similarity as the texture term of optimize.py --ptex_method ssim (lasr_amd/csrc/ssim.hip,
  *      lasr_amd/nnutils/fused_ops.py: ssim_distance) ----
  * This project's own addition: the reference has no counterpart (its texture term is an AlexNet feature distance that needs

@@ -166,6 +166,10 @@ SIGNATURES = {
     # lasr_amd/csrc/meshnbr.hip
     'lasr_meshnbr_list': (_i, [_p] * 3 + [_i] * 2 + [_p]),
     'lasr_meshnbr_test': (_i, [_p, _sz, _p, _i, _f] + [_p] * 5 + [_i] * 3 + [_p]),
+    # lasr_amd/csrc/foldpen.hip
+    'lasr_foldpen_scratch_bytes': (_sz, [_i, _i]),
+    'lasr_foldpen_forward': (_i, [_p, _p, _p, _i, _f, _p, _p, _p, _sz, _p] + [_i] * 3 + [_p]),
+    'lasr_foldpen_backward': (_i, [_p, _p, _p, _i, _p, _p] + [_i] * 3 + [_p]),
     # lasr_amd/csrc/ssim.hip
     'lasr_ssim_scratch_floats': (_sz, [_i] * 4),
     'lasr_ssim_forward': (_i, [_p] * 5 + [_i] * 4 + [_f, _p]),
@@ -240,6 +244,7 @@ FLOWMATCH_MAX_R, FLOWMATCH_MAX_PATCH = 32, 3        # LASR_FLOWMATCH_* of includ
 MOTIONSEG_MAX_SIZE, MOTIONSEG_BLOCKS, MOTIONSEG_MOMENTS, MOTIONSEG_BINS, MOTIONSEG_STATE = 16384, 256, 28, 1024, 12   # LASR_MOTIONSEG_*
 MESHCHECK_TILE, MESHCHECK_MAX_FACES, MESHCHECK_MAX_FRAMES = 256, 1 << 20, 65535   # LASR_MESHCHECK_* of include/lasr_ops.h
 MESHNBR_COUNTERS = 4                                # LASR_MESHNBR_COUNTERS of include/lasr_ops.h: n_list, n_duplicate, n_degenerate, n_same
+FOLDPEN_MAX_LIST = 214748364                        # LASR_FOLDPEN_MAX_LIST of include/lasr_ops.h: 10 n_list <= INT_MAX
 SSIM_MIN_SIZE, SSIM_MAX_SIZE, SSIM_TILE_W, SSIM_TILE_H = 11, 4096, 32, 16         # LASR_SSIM_* of include/lasr_ops.h
 
 

@@ -589,6 +589,7 @@ class LASR(MeshNet):
         self.optim_idx = 0
         # criteria attached by the trainer in the reference (train_utils.py:113-123); None until then
         self.triangle_loss_fn_sr = self.arap_loss_fn = self.flatten_loss = self.ptex_loss = None
+        self.fold_loss = None                       # --fold_wt / --pierce_wt: scripts/fold_penalty.py's criterion, this project's own
 
     def __setattr__(self, name, value):
         # a new connectivity (load_network, re-meshing) may land on the old tensor's address with the old shape: drop the
@@ -873,7 +874,15 @@ class LASR(MeshNet):
             # 100 * (0.1 * mean(joints) + 0.1 * mean(control points)) = 20 * mean over both sets (equal sizes), one sampling call
             both = F.grid_sample(barrier, proj[:, :, :2].reshape(-1, 2 * (K - 1), 1, 2), padding_mode='border', align_corners=False)
             terms.append((both, 20., G_AUX))
-        total, sums = fused_ops.weighted_mean_sum(terms, 10)
+        n_groups = 10
+        if self.fold_loss is not None:
+            # 9) folds between neighbouring faces of the posed meshes (--fold_wt, --pierce_wt; this project's own addition,
+            # scripts/fold_penalty.py): the last entries, so that the accumulation of every earlier term keeps its bits
+            G_FOLD, n_groups = 10, 11
+            fold = self.fold_loss(self.deform_v.reshape(-1, self.deform_v.shape[-2], 3))
+            terms.append((fold[:, 0], float(opts.fold_wt), G_FOLD))
+            terms.append((fold[:, 1], float(opts.pierce_wt), G_FOLD))
+        total, sums = fused_ops.weighted_mean_sum(terms, n_groups)
         self.total_loss = total
         self.mask_loss, self.flow_rd_loss, self.texture_loss = sums[G_MASK], sums[G_FLOW], sums[G_TEX]
         self.triangle_loss, self.cam_loss = sums[G_TRI], sums[G_CAM]
@@ -886,6 +895,8 @@ class LASR(MeshNet):
         if K > 1:
             aux['lmotion_loss'] = self.lmotion_loss
             aux['ctl_proj'] = self.ctl_proj
+        if self.fold_loss is not None:
+            self.fold_loss_value = aux['fold_loss'] = sums[G_FOLD]
         # per-hypothesis scores (:532-541): mean over the images of each table, and their sum (texture + flow + mask)
         per_hypo = torch.stack([self.mask_loss_sub, self.flow_rd_loss_sub, self.texture_loss_sub], 0).detach().mean(1)   # [3,H]
         aux['current_nscore'] = per_hypo.sum(0)

@@ -8,6 +8,7 @@ Differences, all behind the same calls:
   * k-means bone initialisation (:243-251, kmeans_pytorch) is a small Lloyd iteration with farthest-point seeding.
 """
 import ctypes
+import math
 import os
 import sys
 from types import SimpleNamespace
@@ -102,6 +103,22 @@ class LASRTrainer:
         m.triangle_loss_fn_sr = loss_utils.LaplacianLoss(mean_v[0].cpu(), faces[0].cpu()).to(self.device)
         m.arap_loss_fn = loss_utils.ARAPLoss(mean_v[0].cpu(), faces[0].cpu()).to(self.device)
         m.flatten_loss = loss_utils.FlattenLoss(faces[0].cpu()).to(self.device)
+        # --fold_wt / --pierce_wt: the fold penalty on the posed meshes (scripts/fold_penalty.py, this project's own addition), built
+        # for this topology only when a weight asks for it; refused here, when the trainer is built, like a mistyped --ptex_method
+        fold_wt, pierce_wt = float(getattr(self.opts, 'fold_wt', 0.)), float(getattr(self.opts, 'pierce_wt', 0.))
+        fold_deg = float(getattr(self.opts, 'fold_deg', 30.))
+        for name, wt in (('fold_wt', fold_wt), ('pierce_wt', pierce_wt)):
+            if not (math.isfinite(wt) and wt >= 0.):
+                raise ValueError('--%s %s: a finite weight of at least 0' % (name, wt))
+        if not (math.isfinite(fold_deg) and 0. < fold_deg <= 90.):
+            raise ValueError('--fold_deg %s: an angle inside (0, 90] degrees' % fold_deg)
+        m.fold_loss = None
+        if fold_wt > 0. or pierce_wt > 0.:
+            folder = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), 'scripts')
+            if folder not in sys.path:
+                sys.path.insert(0, folder)
+            import fold_penalty                                                    # (scripts/: its launch sites live there)
+            m.fold_loss = fold_penalty.FoldPenalty(faces[0].to(self.device), fold_deg, n_verts=mean_v.shape[-2])
         # --ptex_method: which texture term beside L1.  'alexnet' (default): the reference's feature distance; 'ssim': structural
         # similarity, this project's own addition, which needs no weights (mesh_net.StructuralDistance).  Refused here, when the
         # trainer is built, also under --noperceptual: a mistyped method must not pass because the term happens to be off.

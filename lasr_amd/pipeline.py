@@ -102,6 +102,9 @@ CAVEATS = collections.OrderedDict([
     ('ssim', 'Texture term --ptex_method ssim (no AlexNet weights): its weight is derived, not measured, and quality on real '
              'footage is unverified.'),
     ('alexnet_random', 'Texture term alexnet without --alexnet_weights: the features are a random projection.'),
+    ('fold_penalty', 'Fold penalty on the posed meshes (--fold_wt, --pierce_wt; scripts/fold_penalty.py): its weights and its angle '
+                     'of 30 degrees are derived from nothing measured on a real reconstruction: unmeasured, and its effect on real '
+                     'footage is unverified.'),
     ('encoder_random', 'The ResNet-18 encoder starts from random weights (no --encoder_weights); the reference starts from '
                        'ImageNet weights.'),
     ('one_gpu', 'Stages run on one GPU (--ngpu 1).  The reference\'s scripts/template.sh runs two processes with its batch size '
@@ -202,6 +205,10 @@ def build_parser():
         p.add_argument('--' + name, action='store_true', help='also run ' + text)
     p.add_argument('--neighbours', action='store_true',
                    help='scripts/eval_shape.py --neighbours: also score folds between neighbouring faces (n_pierced, n_creased, min_dihedral)')
+    p.add_argument('--fold_wt', type=float, default=0., help='optimize.py --fold_wt for every stage: the weight of the crease term of the '
+                   'fold penalty on the posed meshes (default 0: off)')
+    p.add_argument('--pierce_wt', type=float, default=0., help='optimize.py --pierce_wt for every stage: the weight of its pierce term '
+                   '(default 0: off)')
     p.add_argument('--worst', type=int, default=5, help='frames listed as worst by each score (default 5)')
     p.add_argument('--dry_run', action='store_true', help='print the plan as shell lines; run nothing, write nothing')
     p.add_argument('--from', dest='start', default=None, metavar='STEP', help='first step to run')
@@ -230,6 +237,9 @@ def parse_args(argv, cwd=None):
         p.error('--masks and --key exclude each other: the silhouettes are given or they are propagated')
     if args.timeout_scale <= 0:
         p.error('--timeout_scale must be positive')
+    for name in ('fold_wt', 'pierce_wt'):
+        if not (math.isfinite(getattr(args, name)) and getattr(args, name) >= 0.):
+            p.error('--%s must be finite and at least 0' % name)
     if args.flow_method is None:
         args.flow_method = 'vcn' if args.loadmodel else 'variational'
     if args.flow_method == 'variational' and args.loadmodel:
@@ -313,6 +323,9 @@ def stage_flags(args, stage):
         flags.setdefault('ptex_method', 'ssim')
     if args.encoder_weights:
         flags.setdefault('encoder_weights', args.encoder_weights)
+    for key in ('fold_wt', 'pierce_wt'):                                           # named only when asked for: the default plan keeps its bytes
+        if getattr(args, key, 0.):
+            flags.setdefault(key, getattr(args, key))
     if int(flags['ngpu']) != 1:
         raise PipelineError('a stage with --ngpu %s: the driver runs every stage on one GPU' % flags['ngpu'])
     return flags
@@ -432,6 +445,8 @@ def describe(args):
         used.append('large_displacement')
     used += ['ssim' if f.get('ptex_method', 'alexnet') == 'ssim' else ('alexnet_random' if not f.get('alexnet_weights') else None)
              for f in stages[:1]]
+    if any(float(f.get(key, 0.)) != 0. for f in stages for key in ('fold_wt', 'pierce_wt')):
+        used.append('fold_penalty')
     used += [None if args.encoder_weights else 'encoder_random', 'one_gpu', 'eval_reproj',
              'eval_shape_neighbours' if getattr(args, 'neighbours', False) else 'eval_shape',
              'bake_texture' if args.atlas else None, 'export_tracks' if args.tracks else None]
@@ -446,7 +461,7 @@ def driver_argv(args):
     p = build_parser()
     out = []
     for name in ('frames', 'seqname', 'workdir', 'masks', 'loadmodel', 'flow_method', 'alexnet_weights', 'encoder_weights', 'schedule',
-                 'dframe', 'init_frame', 'end_frame', 'can_frame', 'worst', 'timeout_scale'):
+                 'dframe', 'init_frame', 'end_frame', 'can_frame', 'fold_wt', 'pierce_wt', 'worst', 'timeout_scale'):
         val = getattr(args, name)
         if val != p.get_default(name) and not (name == 'flow_method' and val == ('vcn' if args.loadmodel else 'variational')):
             out += ['--' + name, str(val)]

@@ -52,7 +52,14 @@ DEFAULTS = dict(
     # ssim_scales levels of an average-pooled pyramid, on the ssim.hip kernels: no weights needed.  ssim_wt 0.125 is derived, not
     # measured: the term is the sum of two distances (the object on black and on white), so 2 x 0.125 = 0.25 of the L1 term's
     # weight, the 0.8 : 0.2 ratio of L1 to D-SSIM of 3D Gaussian splatting.  --noperceptual switches either term off.
-    ptex_method='alexnet', ssim_wt=0.125, ssim_scales=3)
+    ptex_method='alexnet', ssim_wt=0.125, ssim_scales=3,
+    # fold_wt, pierce_wt: the weights of the fold penalty on the posed meshes of every step (scripts/fold_penalty.py, the
+    # foldpen.hip kernels; this project's own addition): per pair of faces that share an edge max(0, fold_deg - dihedral angle)^2 in
+    # radians, per pair that share a vertex the depth of an opposite edge that passes through the other face, the criteria
+    # scripts/eval_shape.py --neighbours reports.  0 (the default) = off: not a launch, not a bit of any loss changes.  All three
+    # are derived from nothing measured on a real reconstruction; fold_deg 30 sits above the evaluation's default of 20 so that a
+    # shape the penalty has released clears the report's threshold.
+    fold_wt=0.0, pierce_wt=0.0, fold_deg=30.0)
 
 
 def parse_flags(argv, defaults=DEFAULTS):

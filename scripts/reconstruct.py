@@ -3,7 +3,7 @@
 
     python scripts/reconstruct.py --frames ~/cat/ --seqname cat --workdir runs/cat [--key 0:first.png | --masks DIR]
            [--schedule quick|template|FILE] [--glb] [--gif] [--atlas] [--tracks] [--neighbours] [--dry_run] [--from S] [--until S]
-           [--force S]
+           [--force S] [--fold_wt W] [--pierce_wt W]
            [--timeout_scale 1.0] [-- flags passed through to the preprocessing scripts]
 
 Steps, each a fresh child process with the work directory as its current one, one at a time, each under its own time limit:
@@ -18,6 +18,9 @@ their own size (the report names either among the unverified pieces).  The first
 after it; the same command again resumes at the first step whose stamp under <workdir>/reconstruct/steps/ no longer matches.
 --neighbours hands scripts/eval_shape.py its flag of that name: folds between neighbouring faces are scored too (n_pierced, n_creased,
 min_dihedral in the report; the angle threshold is unmeasured on real footage, and the report says so).
+--fold_wt W and --pierce_wt W hand every optimize.py stage the weights of the fold penalty on the posed meshes
+(scripts/fold_penalty.py), which acts on what --neighbours reports; both are 0 by default (off) and unmeasured on real footage, and
+the report says so.
 --dry_run prints the plan as shell lines and does nothing else.  The run ends in <workdir>/reconstruct/report.md and report.json.
 """
 import os

@@ -70,6 +70,11 @@ def main(argv=None):
     ap.add_argument('--ptex_method', default='alexnet', choices=['alexnet', 'ssim'],
                     help='optimize.py --ptex_method for both stages: the AlexNet feature distance (default) or structural similarity')
     ap.add_argument('--noperceptual', action='store_true', help='optimize.py --noperceptual for both stages: no texture term beside L1')
+    ap.add_argument('--fold_wt', type=float, default=0., help='optimize.py --fold_wt for both stages (default 0: the fold penalty is off)')
+    ap.add_argument('--pierce_wt', type=float, default=0., help='optimize.py --pierce_wt for both stages (default 0: off)')
+    ap.add_argument('--fold_deg', type=float, default=30., help='optimize.py --fold_deg, used when a weight above is not 0')
+    ap.add_argument('--folds', action='store_true',
+                    help='also count the folds between neighbouring faces of the exported shapes (scripts/eval_shape.py --neighbours)')
     args = ap.parse_args(argv)
     root = tempfile.mkdtemp(prefix='lasr_demo_')
     name = 'syn-blob%df' % args.nframes
@@ -82,6 +87,9 @@ def main(argv=None):
               '--batch_size', '1', '--opt_tex', 'yes', '--nouse_gtpose', '--subdivide', '3', '--img_size', str(args.img_size)] + \
         (['--nouse_graph'] if args.no_graph else ['--use_graph']) + (['--deterministic'] if args.deterministic else []) + \
         ['--ptex_method', args.ptex_method] + (['--noperceptual'] if args.noperceptual else [])
+    penalised = args.fold_wt != 0. or args.pierce_wt != 0.
+    if penalised:
+        common += ['--fold_wt', str(args.fold_wt), '--pierce_wt', str(args.pierce_wt), '--fold_deg', str(args.fold_deg)]
     # scripts/spot3.sh:24-25
     tr0, steps0, dt0 = run_stage(['--name', 'demo-0', '--only_mean_sym', '--n_bones', '21', '--n_hypo', str(args.n_hypo),
                                   '--num_epochs', str(args.epochs0)] + common)
@@ -89,8 +97,14 @@ def main(argv=None):
     gts = [load_obj(os.path.join(root, 'database', 'DAVIS', 'Meshes', 'Full-Resolution', name, '%05d.obj' % i), device=dev)
            for i in range(args.nframes)]
 
+    folds = {}
+
     def score(tr):
         shapes, faces = export_shapes(tr)
+        if args.folds or penalised:
+            res = _load('shape_neighbours').evaluate(torch.stack([shapes[i].float() for i in sorted(shapes)]), faces)
+            folds[tr.opts.name] = {'n_creased': res['n_creased'].tolist(), 'n_pierced': res['n_pierced'].tolist(),
+                                   'n_pairs': res['n_pairs'].tolist(), 'min_dihedral': res['min_dihedral'].tolist()}
         return [ev.evaluate_pair((shapes[i].float(), faces.long()), (gts[i][0].float(), gts[i][1].long()))
                 for i in sorted(shapes)]
     from lasr_amd import synth
@@ -109,6 +123,9 @@ def main(argv=None):
            'stage0': {'iterations': steps0, 'seconds': dt0, 'iters_per_s': steps0 / dt0, 'chamfer': float(np.mean(cd0)), 'per_frame': cd0},
            'stage1': {'iterations': steps1, 'seconds': dt1, 'iters_per_s': steps1 / dt1, 'chamfer': float(np.mean(cd1)), 'per_frame': cd1},
            'protocol': 'scripts/eval_mesh.py: centred, diameter 10, rigid ICP, symmetric squared Chamfer of 10k samples'}
+    if folds:                                                # eval_shape.py --neighbours at its default of 20 degrees, per exported frame
+        out['stage0']['folds'], out['stage1']['folds'] = folds['demo-0'], folds['demo-1']
+        out['fold_penalty'] = {'fold_wt': args.fold_wt, 'pierce_wt': args.pierce_wt, 'fold_deg': args.fold_deg}
     print(json.dumps(out))
     if args.out:
         with open(args.out, 'w') as fh:
