@@ -1504,6 +1504,49 @@ int lasr_foldpen_backward(const float* rows, const int* vstart, const int* inc, 
                           int V, int n_list, void* hip_stream);
 
 /*
+ * ---- Intersection penalty of the optimiser: optimize.py --isect_wt (lasr_amd/csrc/isectpen.hip, scripts/isect_penalty.py,
+ *      DESIGN.md section 4.22) ----
+ * This project's own addition, as the blocks above: the reference has no counterpart, and parity is to the restatement in
+ * tests/isectpen_restated.py and to closed forms only.  A loss on the posed meshes of a step that is zero exactly where
+ * scripts/eval_shape.py reports n_pairs = 0: the third line of the shape report, beside the two the fold penalty above acts on.
+ * x [N,V,3] fp32, the N meshes of a step on one topology; faces [F,3] int32.  Nothing is new except the set of pairs and the
+ * accumulation.  The caller's weight (default 0: off) is derived from nothing measured, and the effect on real footage is unverified.
+ *
+ * Pairs: CANDIDATE and INTERSECTS of lasr_meshcheck_pairs above, unchanged: faces i < j that share no vertex index and whose closed
+ *   fp32 boxes overlap, put to the six directed edge-against-triangle tests (the edges (0,1), (1,2), (2,0) of i against j, then those
+ *   of j against i) with orient and PIERCES, strict and without contraction.  A face with an index outside [0, V) or with a repeated
+ *   index is not gathered: it has the empty box and takes part in nothing.
+ * Value of a pair: the sum over its directed tests that hold of the pierce depth of the fold penalty above, with edge (p, q),
+ *   triangle (a, b, c) in stored order and n = (b - a) x (c - a): delta = min(|orient(a,b,c,p)|, |orient(a,b,c,q)|) / |n|; the
+ *   gradient goes to the shallower end r (p on a tie), sign(orient(a,b,c,r)) n / |n|, and to a, b, c: minus that times l_a, l_b, l_c
+ *   of r's foot, in that block's operation order (one device function, lasr_amd/csrc/foldpen_geom.h, serves both).  Linear in the
+ *   depth, so that a descent step carries the end across the plane.
+ * Accumulation: the pair set depends on the geometry, so there is no list to gather through, and the project uses no floating-point
+ *   atomics: FIXED POINT with Q = 2^40.  Every fp32 contribution c of a test (its depth, or one coordinate of one of its four vertex
+ *   contributions) is added as llrint((double)c Q) by a 64-bit integer atomicAdd, to acc_loss [N] and acc_grad [N,V,3], both int64
+ *   in scratch.  A test whose |n|^2 is 0 or not finite, or with any contribution that is not finite or >= 2^20 in magnitude, is
+ *   dropped as a whole, before its first atomic is issued, and counted in n_dropped [N].  Integer sums commute: the result has the same
+ *   bits on every run and under any permutation of the rows of faces.  Each rounding is at most 2^-41; an accumulator wraps beyond a
+ *   sum of 2^23, which is not checked.
+ * lasr_isectpen_forward: zeroes the accumulators and the counts itself (nothing depends on what any buffer held); the grid of
+ *   lasr_meshcheck_pairs, (tile pair I <= J, mesh), 256 threads, tiles of LASR_MESHCHECK_TILE faces staged in LDS straight from x
+ *   and faces (nine coordinates, the box, the three indices); box rejection, per-wave compaction, the exact test 64 at a time; a hit
+ *   lane evaluates its tests that hold and issues its atomics.  Then loss [N] = (float)((double)acc_loss 2^-40), gunit [N,V,3]
+ *   likewise: the gradient of loss[n] by x[n]; n_pairs [N] uint64: the intersecting pairs as lasr_meshcheck_pairs counts them (one
+ *   atomic per wave).  gunit NULL: no gradient is wanted, only acc_loss and the counts are touched; loss and the counts are the
+ *   same.  There is no backward entry point: loss[n] is a plain sum, so the gradient by x is grad_loss[n] gunit[n].  Three launches
+ *   (zero, pairs, finalise), static shapes, no host read: capturable into a graph.
+ * Checked on the host before any launch (LASR_E_BADARG): 0 <= N <= LASR_MESHCHECK_MAX_FRAMES, 0 <= F <= LASR_MESHCHECK_MAX_FACES,
+ *   N F <= INT_MAX, V >= 0, N V 3 <= INT_MAX; then N == 0 or F == 0 is LASR_OK with nothing launched and nothing written; then
+ *   V >= 1, every pointer but gunit non-NULL and no two buffers the same; LASR_E_WORKSPACE when scratch_bytes <
+ *   lasr_isectpen_scratch_bytes(N, V) = 8 (N + N V 3), which is 0 for sizes outside these limits.  Device contents are not read on
+ *   the host.  These launches are not in the lasr_prof_* kernel table.
+ */
+size_t lasr_isectpen_scratch_bytes(int N, int V);
+int lasr_isectpen_forward(const float* x, const int* faces, void* scratch, size_t scratch_bytes, float* loss, float* gunit,
+                          unsigned long long* n_pairs, unsigned long long* n_dropped, int N, int V, int F, void* hip_stream);
+
+/*
  * ---- Structural similarity as the texture term of optimize.py --ptex_method ssim (lasr_amd/csrc/ssim.hip,
  *      lasr_amd/nnutils/fused_ops.py: ssim_distance) ----
  * This project's own addition: the reference has no counterpart (its texture term is an AlexNet feature distance that needs

@@ -170,6 +170,9 @@ SIGNATURES = {
     'lasr_foldpen_scratch_bytes': (_sz, [_i, _i]),
     'lasr_foldpen_forward': (_i, [_p, _p, _p, _i, _f, _p, _p, _p, _sz, _p] + [_i] * 3 + [_p]),
     'lasr_foldpen_backward': (_i, [_p, _p, _p, _i, _p, _p] + [_i] * 3 + [_p]),
+    # lasr_amd/csrc/isectpen.hip
+    'lasr_isectpen_scratch_bytes': (_sz, [_i, _i]),
+    'lasr_isectpen_forward': (_i, [_p, _p, _p, _sz] + [_p] * 4 + [_i] * 3 + [_p]),
     # lasr_amd/csrc/ssim.hip
     'lasr_ssim_scratch_floats': (_sz, [_i] * 4),
     'lasr_ssim_forward': (_i, [_p] * 5 + [_i] * 4 + [_f, _p]),

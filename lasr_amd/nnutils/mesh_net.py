@@ -25,7 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import soft_renderer as sr
-from .. import synth
+from .. import _lib, synth
 from . import fused_ops, image_losses
 from .geom_utils import obj_to_cam, obj_to_cam_both, pinhole_cam
 
@@ -590,6 +590,7 @@ class LASR(MeshNet):
         # criteria attached by the trainer in the reference (train_utils.py:113-123); None until then
         self.triangle_loss_fn_sr = self.arap_loss_fn = self.flatten_loss = self.ptex_loss = None
         self.fold_loss = None                       # --fold_wt / --pierce_wt: scripts/fold_penalty.py's criterion, this project's own
+        self.isect_loss = None                      # --isect_wt: scripts/isect_penalty.py's criterion, this project's own
 
     def __setattr__(self, name, value):
         # a new connectivity (load_network, re-meshing) may land on the old tensor's address with the old shape: drop the
@@ -882,6 +883,14 @@ class LASR(MeshNet):
             fold = self.fold_loss(self.deform_v.reshape(-1, self.deform_v.shape[-2], 3))
             terms.append((fold[:, 0], float(opts.fold_wt), G_FOLD))
             terms.append((fold[:, 1], float(opts.pierce_wt), G_FOLD))
+        if self.isect_loss is not None:
+            # 10) intersections between faces of the posed meshes that share no vertex (--isect_wt; this project's own addition,
+            # scripts/isect_penalty.py): the last entry and a group of its own, after the fold terms, so that every earlier term and
+            # group keeps its index and its bits
+            G_ISECT, n_groups = n_groups, n_groups + 1
+            terms.append((self.isect_loss(self.deform_v.reshape(-1, self.deform_v.shape[-2], 3)), float(opts.isect_wt), G_ISECT))
+            if len(terms) > _lib.MEANS_MAX_TERMS:
+                raise RuntimeError('LASR.forward: %d loss terms exceed LASR_MEANS_MAX_TERMS = %d' % (len(terms), _lib.MEANS_MAX_TERMS))
         total, sums = fused_ops.weighted_mean_sum(terms, n_groups)
         self.total_loss = total
         self.mask_loss, self.flow_rd_loss, self.texture_loss = sums[G_MASK], sums[G_FLOW], sums[G_TEX]
@@ -897,6 +906,8 @@ class LASR(MeshNet):
             aux['ctl_proj'] = self.ctl_proj
         if self.fold_loss is not None:
             self.fold_loss_value = aux['fold_loss'] = sums[G_FOLD]
+        if self.isect_loss is not None:
+            self.isect_loss_value = aux['isect_loss'] = sums[G_ISECT]
         # per-hypothesis scores (:532-541): mean over the images of each table, and their sum (texture + flow + mask)
         per_hypo = torch.stack([self.mask_loss_sub, self.flow_rd_loss_sub, self.texture_loss_sub], 0).detach().mean(1)   # [3,H]
         aux['current_nscore'] = per_hypo.sum(0)

@@ -119,6 +119,18 @@ class LASRTrainer:
                 sys.path.insert(0, folder)
             import fold_penalty                                                    # (scripts/: its launch sites live there)
             m.fold_loss = fold_penalty.FoldPenalty(faces[0].to(self.device), fold_deg, n_verts=mean_v.shape[-2])
+        # --isect_wt: the intersection penalty between faces of the posed meshes that share no vertex (scripts/isect_penalty.py, this
+        # project's own addition), built only when the weight asks for it and refused here like the weights above
+        isect_wt = float(getattr(self.opts, 'isect_wt', 0.))
+        if not (math.isfinite(isect_wt) and isect_wt >= 0.):
+            raise ValueError('--isect_wt %s: a finite weight of at least 0' % isect_wt)
+        m.isect_loss = None
+        if isect_wt > 0.:
+            folder = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), 'scripts')
+            if folder not in sys.path:
+                sys.path.insert(0, folder)
+            import isect_penalty                                                   # (scripts/: its launch site lives there)
+            m.isect_loss = isect_penalty.IsectPenalty(faces[0].to(self.device), n_verts=mean_v.shape[-2])
         # --ptex_method: which texture term beside L1.  'alexnet' (default): the reference's feature distance; 'ssim': structural
         # similarity, this project's own addition, which needs no weights (mesh_net.StructuralDistance).  Refused here, when the
         # trainer is built, also under --noperceptual: a mistyped method must not pass because the term happens to be off.

@@ -105,6 +105,9 @@ CAVEATS = collections.OrderedDict([
     ('fold_penalty', 'Fold penalty on the posed meshes (--fold_wt, --pierce_wt; scripts/fold_penalty.py): its weights and its angle '
                      'of 30 degrees are derived from nothing measured on a real reconstruction: unmeasured, and its effect on real '
                      'footage is unverified.'),
+    ('isect_penalty', 'Intersection penalty on the posed meshes (--isect_wt; scripts/isect_penalty.py): its weight is derived from '
+                      'nothing measured: unmeasured, and its effect on real footage is unverified; it clears shallow pass-throughs and '
+                      'does not separate two bodies that overlap wholesale.'),
     ('encoder_random', 'The ResNet-18 encoder starts from random weights (no --encoder_weights); the reference starts from '
                        'ImageNet weights.'),
     ('one_gpu', 'Stages run on one GPU (--ngpu 1).  The reference\'s scripts/template.sh runs two processes with its batch size '
@@ -209,6 +212,8 @@ def build_parser():
                    'fold penalty on the posed meshes (default 0: off)')
     p.add_argument('--pierce_wt', type=float, default=0., help='optimize.py --pierce_wt for every stage: the weight of its pierce term '
                    '(default 0: off)')
+    p.add_argument('--isect_wt', type=float, default=0., help='optimize.py --isect_wt for every stage: the weight of the intersection '
+                   'penalty between faces of the posed meshes that share no vertex (default 0: off)')
     p.add_argument('--worst', type=int, default=5, help='frames listed as worst by each score (default 5)')
     p.add_argument('--dry_run', action='store_true', help='print the plan as shell lines; run nothing, write nothing')
     p.add_argument('--from', dest='start', default=None, metavar='STEP', help='first step to run')
@@ -237,7 +242,7 @@ def parse_args(argv, cwd=None):
         p.error('--masks and --key exclude each other: the silhouettes are given or they are propagated')
     if args.timeout_scale <= 0:
         p.error('--timeout_scale must be positive')
-    for name in ('fold_wt', 'pierce_wt'):
+    for name in ('fold_wt', 'pierce_wt', 'isect_wt'):
         if not (math.isfinite(getattr(args, name)) and getattr(args, name) >= 0.):
             p.error('--%s must be finite and at least 0' % name)
     if args.flow_method is None:
@@ -323,7 +328,7 @@ def stage_flags(args, stage):
         flags.setdefault('ptex_method', 'ssim')
     if args.encoder_weights:
         flags.setdefault('encoder_weights', args.encoder_weights)
-    for key in ('fold_wt', 'pierce_wt'):                                           # named only when asked for: the default plan keeps its bytes
+    for key in ('fold_wt', 'pierce_wt', 'isect_wt'):                               # named only when asked for: the default plan keeps its bytes
         if getattr(args, key, 0.):
             flags.setdefault(key, getattr(args, key))
     if int(flags['ngpu']) != 1:
@@ -447,6 +452,8 @@ def describe(args):
              for f in stages[:1]]
     if any(float(f.get(key, 0.)) != 0. for f in stages for key in ('fold_wt', 'pierce_wt')):
         used.append('fold_penalty')
+    if any(float(f.get('isect_wt', 0.)) != 0. for f in stages):
+        used.append('isect_penalty')
     used += [None if args.encoder_weights else 'encoder_random', 'one_gpu', 'eval_reproj',
              'eval_shape_neighbours' if getattr(args, 'neighbours', False) else 'eval_shape',
              'bake_texture' if args.atlas else None, 'export_tracks' if args.tracks else None]
@@ -461,7 +468,7 @@ def driver_argv(args):
     p = build_parser()
     out = []
     for name in ('frames', 'seqname', 'workdir', 'masks', 'loadmodel', 'flow_method', 'alexnet_weights', 'encoder_weights', 'schedule',
-                 'dframe', 'init_frame', 'end_frame', 'can_frame', 'fold_wt', 'pierce_wt', 'worst', 'timeout_scale'):
+                 'dframe', 'init_frame', 'end_frame', 'can_frame', 'fold_wt', 'pierce_wt', 'isect_wt', 'worst', 'timeout_scale'):
         val = getattr(args, name)
         if val != p.get_default(name) and not (name == 'flow_method' and val == ('vcn' if args.loadmodel else 'variational')):
             out += ['--' + name, str(val)]

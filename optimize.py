@@ -59,7 +59,13 @@ DEFAULTS = dict(
     # scripts/eval_shape.py --neighbours reports.  0 (the default) = off: not a launch, not a bit of any loss changes.  All three
     # are derived from nothing measured on a real reconstruction; fold_deg 30 sits above the evaluation's default of 20 so that a
     # shape the penalty has released clears the report's threshold.
-    fold_wt=0.0, pierce_wt=0.0, fold_deg=30.0)
+    fold_wt=0.0, pierce_wt=0.0, fold_deg=30.0,
+    # isect_wt: the weight of the intersection penalty on the posed meshes of every step (scripts/isect_penalty.py, the isectpen.hip
+    # kernels; this project's own addition): per pair of faces that share no vertex and pass through each other, the pairs
+    # scripts/eval_shape.py counts as n_pairs, the depth of the shallower end of every piercing edge.  0 (the default) = off: not a
+    # launch, not a bit of any loss changes.  The weight is derived from nothing measured, and the effect on real footage is
+    # unverified; the term clears shallow pass-throughs and does not separate two bodies that overlap wholesale.
+    isect_wt=0.0)
 
 
 def parse_flags(argv, defaults=DEFAULTS):

@@ -3,7 +3,7 @@
 
     python scripts/reconstruct.py --frames ~/cat/ --seqname cat --workdir runs/cat [--key 0:first.png | --masks DIR]
            [--schedule quick|template|FILE] [--glb] [--gif] [--atlas] [--tracks] [--neighbours] [--dry_run] [--from S] [--until S]
-           [--force S] [--fold_wt W] [--pierce_wt W]
+           [--force S] [--fold_wt W] [--pierce_wt W] [--isect_wt W]
            [--timeout_scale 1.0] [-- flags passed through to the preprocessing scripts]
 
 Steps, each a fresh child process with the work directory as its current one, one at a time, each under its own time limit:
@@ -21,6 +21,9 @@ min_dihedral in the report; the angle threshold is unmeasured on real footage, a
 --fold_wt W and --pierce_wt W hand every optimize.py stage the weights of the fold penalty on the posed meshes
 (scripts/fold_penalty.py), which acts on what --neighbours reports; both are 0 by default (off) and unmeasured on real footage, and
 the report says so.
+--isect_wt W hands every optimize.py stage the weight of the intersection penalty between faces that share no vertex
+(scripts/isect_penalty.py), which acts on the n_pairs of the shape report; 0 by default (off) and unmeasured on real footage, and the
+report says so.
 --dry_run prints the plan as shell lines and does nothing else.  The run ends in <workdir>/reconstruct/report.md and report.json.
 """
 import os

@@ -73,6 +73,8 @@ def main(argv=None):
     ap.add_argument('--fold_wt', type=float, default=0., help='optimize.py --fold_wt for both stages (default 0: the fold penalty is off)')
     ap.add_argument('--pierce_wt', type=float, default=0., help='optimize.py --pierce_wt for both stages (default 0: off)')
     ap.add_argument('--fold_deg', type=float, default=30., help='optimize.py --fold_deg, used when a weight above is not 0')
+    ap.add_argument('--isect_wt', type=float, default=0.,
+                    help='optimize.py --isect_wt for both stages (default 0: the intersection penalty between non-neighbouring faces is off)')
     ap.add_argument('--folds', action='store_true',
                     help='also count the folds between neighbouring faces of the exported shapes (scripts/eval_shape.py --neighbours)')
     args = ap.parse_args(argv)
@@ -90,6 +92,8 @@ def main(argv=None):
     penalised = args.fold_wt != 0. or args.pierce_wt != 0.
     if penalised:
         common += ['--fold_wt', str(args.fold_wt), '--pierce_wt', str(args.pierce_wt), '--fold_deg', str(args.fold_deg)]
+    if args.isect_wt != 0.:
+        common += ['--isect_wt', str(args.isect_wt)]
     # scripts/spot3.sh:24-25
     tr0, steps0, dt0 = run_stage(['--name', 'demo-0', '--only_mean_sym', '--n_bones', '21', '--n_hypo', str(args.n_hypo),
                                   '--num_epochs', str(args.epochs0)] + common)
@@ -101,7 +105,7 @@ def main(argv=None):
 
     def score(tr):
         shapes, faces = export_shapes(tr)
-        if args.folds or penalised:
+        if args.folds or penalised or args.isect_wt != 0.:
             res = _load('shape_neighbours').evaluate(torch.stack([shapes[i].float() for i in sorted(shapes)]), faces)
             folds[tr.opts.name] = {'n_creased': res['n_creased'].tolist(), 'n_pierced': res['n_pierced'].tolist(),
                                    'n_pairs': res['n_pairs'].tolist(), 'min_dihedral': res['min_dihedral'].tolist()}
@@ -126,6 +130,8 @@ def main(argv=None):
     if folds:                                                # eval_shape.py --neighbours at its default of 20 degrees, per exported frame
         out['stage0']['folds'], out['stage1']['folds'] = folds['demo-0'], folds['demo-1']
         out['fold_penalty'] = {'fold_wt': args.fold_wt, 'pierce_wt': args.pierce_wt, 'fold_deg': args.fold_deg}
+        if args.isect_wt != 0.:
+            out['isect_penalty'] = {'isect_wt': args.isect_wt}
     print(json.dumps(out))
     if args.out:
         with open(args.out, 'w') as fh:
